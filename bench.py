@@ -19,6 +19,14 @@ Multi-GPU: one process per GPU (torch.distributed, backend nccl = RCCL).  Channe
 shard with NO data-path collective ("weak" scaling); the RCCL gather of demodulated audio is timed separately, outside the
 timed region (all-gather, gather-to-root, and the double-buffered schedule that overlaps gather k with compute k + 1), and
 reported under "gather".  The CPU baseline runs on rank 0 whatever N is.
+
+A plain run (no --full) does only what its headline figure needs: it sets up, runs the W warm-up steps and the K timed steps of
+the selected record, writes that record's outputs if --dump-outputs is given, and prints the line.  --full adds everything else
+listed above: the sub-records under "also", the in-run parity check, the CPU baseline, the power probe, the front end's wide
+layout and the multi-GPU gather figures.
+--dump-outputs DIR writes what the timed path handed back in its LAST timed step as DIR/<name>.npy (float32), at most 32 MB per
+output: a larger output is sampled as a fixed, seeded choice of contiguous stretches (dump_outputs).  The inputs are seeded, so
+two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -393,6 +401,7 @@ def bench_frontend(args, torch, msdr, ctx, dev, rank, world, dist):
     if dist is not None:
         import msdr_dist
         dt = msdr_dist.max_over_ranks(dt, args.cdev)
+    dump_outputs(args, rank, torch, {"frontend_out": y})
     if rank != 0:
         return None
     value = world * ch * n * args.steps / dt / 1e6
@@ -406,7 +415,7 @@ def bench_frontend(args, torch, msdr, ctx, dev, rank, world, dist):
            "roofline": {"bound": "hbm", "achieved": round(4.0 * ch * n / (ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                         "frac": round(4.0 * ch * n / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4), "traffic": None,
                         "note": "one lane per channel: serial integer recurrences, latency-bound by construction"}}
-    if not (args.channels or args.samples):
+    if args.full and not (args.channels or args.samples):
         # The same number of conversions as 4x the channels: a workgroup (64 channels) walks its stream alone, so 4096 channels keep 64 of the
         # 256 CUs busy and the step time is the per-channel latency (2^18 dependent recursion steps); 16 384 channels fill the chip.
         chw, nw = 4 * ch, n // 4
@@ -482,6 +491,7 @@ def bench_spectrum(args, torch, msdr, ctx, dev, rank, world, dist):
     if dist is not None:
         import msdr_dist
         dt = msdr_dist.max_over_ranks(dt, args.cdev)
+    dump_outputs(args, rank, torch, {"fft_out": o, "columns": c})
     if rank != 0:
         return None
     ms = dt / args.steps * 1e3
@@ -586,6 +596,28 @@ def timed_steps(args, torch, dev, dist, step, after_warmup=None):
     return dt
 
 
+DUMP_VALUES = 8 << 20          # --dump-outputs: at most this many values per output (32 MB as float32)
+DUMP_STRETCH = 1 << 16         # ... taken as contiguous stretches of this many samples of one row
+
+
+def dump_outputs(args, rank, torch, outputs):
+    """--dump-outputs DIR: each (rows, n) device array of `outputs` as DIR/<name>.npy in float32 (integer outputs convert exactly).
+    One that holds more than DUMP_VALUES values is sampled: its rows are cut into stretches of min(n, DUMP_STRETCH) samples and a
+    fixed choice of them (numpy generator seeded with 0, kept in order) is stacked -- the same positions on every run with the same
+    arguments.  Called right after the timed region, before anything else steps the record again; rank 0 writes its own shard."""
+    if not args.dump_outputs or rank != 0:
+        return
+    os.makedirs(args.dump_outputs, exist_ok=True)
+    for name, t in outputs.items():
+        rows, n = t.shape
+        if rows * n > DUMP_VALUES:
+            seg = min(n, DUMP_STRETCH)
+            per_row = n // seg
+            picks = np.sort(np.random.default_rng(0).choice(rows * per_row, min(rows * per_row, DUMP_VALUES // seg), replace=False))
+            t = torch.stack([t[int(p) // per_row, (int(p) % per_row) * seg:(int(p) % per_row + 1) * seg] for p in picks])
+        np.save(os.path.join(args.dump_outputs, name + ".npy"), t.to(torch.float32).cpu().numpy())
+
+
 def bench_fir_stage(args, torch, msdr, ctx, dev, rank, world, dist, do_cpu):
     """The FIR STAGE on its own (rows A4 / A6): arm_fir_f32 (fp32 in / fp32 out, 8 B per sample) or, with --arith q15,
     arm_fir_fast_q15 (int16 in / out, 4 B per sample), 256 taps, batched over 4096 channels x 2^18 samples."""
@@ -624,7 +656,8 @@ def bench_fir_stage(args, torch, msdr, ctx, dev, rank, world, dist, do_cpu):
     dt = timed_steps(args, torch, dev, dist, step, after_warmup=ctx.kernel_time)
     k_total, launches = ctx.kernel_time()
     ctx.enable_kernel_timing(False)
-    power = power_probe(step, torch, dev, dev.index or 0, world) if rank == 0 else None
+    dump_outputs(args, rank, torch, {"fir_out": y})
+    power = power_probe(step, torch, dev, dev.index or 0, world) if (rank == 0 and args.full) else None
     x_cpu = None
     if rank == 0 and do_cpu:                                     # rows of the same input for the timed CPU leg (two per thread of its team)
         x_cpu = x[:min(ch, max(2 * usable_cores()[0], 16)), :min(n, 1 << 18)].cpu().numpy()
@@ -899,6 +932,7 @@ def bench_chain(args, name, torch, msdr, ctx, dev, rank, world, dist, do_cpu, do
         # that on the host -- the K timed steps run WITHOUT them (ms_per_step / value = the tick as a caller sees it), the kernel's own time
         # comes from K more steps with the events on
         dt = timed_steps(args, torch, dev, dist, lambda: chain.process(x.data_ptr(), y.data_ptr(), n))
+        dump_outputs(args, rank, torch, {"audio": y})
         # device time per tick: ONE event pair around K more back-to-back calls on the launch stream (kernel + the dispatch gap to the next
         # one; per-call event pairs cost ~3 us each at this size and would time themselves); rocprofv3's per-kernel average: profiles/r05
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -931,7 +965,8 @@ def bench_chain(args, name, torch, msdr, ctx, dev, rank, world, dist, do_cpu, do
         dt = timed_steps(args, torch, dev, dist, lambda: chain.process(x.data_ptr(), y.data_ptr(), n), after_warmup=chain.kernel_time)
         kernel_ms, launches = chain.kernel_time()
         chain.enable_timing(False)
-    power = power_probe(lambda: chain.process(x.data_ptr(), y.data_ptr(), n), torch, dev, dev.index or 0, world) if rank == 0 else None
+        dump_outputs(args, rank, torch, {"audio": y})
+    power = power_probe(lambda: chain.process(x.data_ptr(), y.data_ptr(), n), torch, dev, dev.index or 0, world) if (rank == 0 and args.full) else None
     if captured is not None:
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import orclib
@@ -940,7 +975,7 @@ def bench_chain(args, name, torch, msdr, ctx, dev, rank, world, dist, do_cpu, do
             gpu_first = gpu_first.cpu().numpy()
 
     gather = None
-    if dist is not None and do_gather:                         # RCCL gather of demodulated audio, timed on its own
+    if dist is not None and do_gather and args.full:           # RCCL gather of demodulated audio, timed on its own
         import msdr_dist
         esz = y.element_size()
         rows = max(1, min(ch, (1 << 24) // n)) if n <= (1 << 24) else 1
@@ -1259,7 +1294,13 @@ def main():
     ap.add_argument("--lowpass", default="numpy", choices=["designer", "numpy"],
                     help="the AM low-pass of c3 / c5: designer = the reference's calc_FIR_coeffs (linear phase about an integer index); numpy = a windowed sinc "
                          "centred on a half sample (rounds 1-3)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the sub-records, parity check, CPU baseline, power probe, wide front-end layout and gather figures (a plain run times the record alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the record's last timed step as DIR/<name>.npy (float32, sampled above 32 MB per output)")
     args = ap.parse_args()
+    if not args.full:              # a plain run: the timed record alone (module docstring)
+        args.no_cpu, args.parity = True, False
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: start the N ranks as a CHILD torch.distributed.run job (one process per GPU),
@@ -1320,8 +1361,11 @@ def main():
         out = bench_chain(args, args.workload, torch, msdr, ctx, dev, rank, world, dist, do_cpu, True)
         if out is not None:
             out["warmup_steps_run"] = args.warmup_steps_run
+    elif not args.full:
+        out = bench_chain(args, "c3", torch, msdr, ctx, dev, rank, world, dist, do_cpu, True)      # the headline alone
     else:
         out = bench_chain(args, "c3", torch, msdr, ctx, dev, rank, world, dist, do_cpu, True)      # the headline, with the CPU baseline
+        args.dump_outputs = None                 # the dump is the headline's: the sub-records below reuse its output names
         also = {}
         args.min_warm_s = 0.2                    # sub-records: warm up by time as well as by count (see timed_steps)
         if args.arith == "f32":

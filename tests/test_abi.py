@@ -14,6 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "minimal-sdr_amd", "python"))
 import msdr  # noqa: E402
 import orclib  # noqa: E402
+import reflive  # noqa: E402
 
 
 def declared_functions():
@@ -94,18 +95,18 @@ def test_designer_fir_matches_oracle_random(orc):
     assert differ >= 3             # the two PIs are distinguishable: this test would notice a swapped flag
 
 
-def test_designer_fir_both_pi_variants_match_the_compiled_reference(ref):
+def test_designer_fir_both_pi_variants_match_the_compiled_reference():
     """msdr_calc_FIR_coeffs = the sketch with the vendored header's float PI; msdr_calc_FIR_coeffs_pid = with Arduino.h's
-    double literal (what the Teensy binary computes).  Both against the reference's own source built with that PI."""
-    rng = np.random.default_rng(22)
-    for _ in range(60):
-        n = int(rng.integers(4, 520)) & ~1
-        fc, a = float(rng.integers(100, 9000)), float(rng.choice([20.0, 45.5, 70.0, 90.0]))
-        t, dfc = int(rng.integers(0, 5)), float(rng.integers(50, 2000))
-        for pid in (False, True):
-            want = ref.calc_fir_coeffs(n, fc, a, t, dfc, 24000.0, pi_double=pid)
-            got = msdr.calc_fir_coeffs(n, fc, a, t, dfc, 24000.0, room=want.size, pi_double=pid)
-            assert np.array_equal(got, want), (n, fc, a, t, dfc, pid)
+    double literal (what the Teensy binary computes).  Both against the reference's own source built with that PI: its recorded
+    answers (tests/reflive.py), and the compiled reference itself where it is built."""
+    for d in reflive.answers("designer_wide"):
+        assert len(d["params"]) == 60
+        for i, (n, fc, a, t, dfc) in enumerate(d["params"]):
+            n, t = int(n), int(t)
+            for pid in (False, True):
+                want = d["c%d_%s" % (i, reflive.PI[pid])]
+                got = msdr.calc_fir_coeffs(n, fc, a, t, dfc, 24000.0, room=want.size, pi_double=pid)
+                assert np.array_equal(got, want), (n, fc, a, t, dfc, pid)
 
 
 def test_designer_biquad_matches_oracle_and_survey(orc):

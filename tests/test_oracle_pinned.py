@@ -1,8 +1,9 @@
 """Pin the CPU oracle (oracle/msdr_oracle.c) against the reference.
 
 Two anchors:
-  * `ref`    -- oracle/_ref/libmsdr_ref.so, the reference's own sources compiled in this container
-               (skipped where /root/reference is absent, e.g. on the GPU box if not prebuilt);
+  * `*_live` -- the reference's own sources compiled by oracle/build_ref.sh (oracle/_ref/libmsdr_ref.so), asked about random
+               inputs: its recorded answers (tests/golden/ref_live*.npz, tests/reflive.py) everywhere, and the compiled
+               reference itself as well where it is built;
   * `golden` -- tests/golden/golden.npz, outputs of that compiled reference, committed.
 Bit-exact everywhere (integer path)."""
 import numpy as np
@@ -10,6 +11,7 @@ import pytest
 
 import goldenlib
 import orclib
+import reflive
 
 B = orclib.BLOCK
 
@@ -35,28 +37,27 @@ def test_designer_known_answers_from_survey(orc):
     assert c.sum() == 32761 and np.abs(c).sum() == 59529
 
 
-def test_designer_matches_reference_live(orc, ref):
-    rng = np.random.default_rng(11)
-    for _ in range(60):
-        n = int(rng.integers(4, 300)) & ~1
-        fc = float(rng.integers(100, 9000))
-        a = float(rng.choice([10.0, 30.0, 45.5, 50.0, 70.0, 90.0]))
-        t = int(rng.integers(0, 4))
-        dfc = float(rng.integers(50, 2000))
-        for pid in (False, True):
-            want = ref.calc_fir_coeffs(n, fc, a, t, dfc, 24000.0, pi_double=pid)
-            got = orc.calc_fir_coeffs(n, fc, a, t, dfc, 24000.0, pi_double=pid)
-            assert np.array_equal(got, want), (n, fc, a, t, dfc, pid)
-    for n in (8, 32, 64):  # Hilbert branch (type 4), never used by the app
-        assert np.array_equal(orc.calc_fir_coeffs(n, 0, 70, 4), ref.calc_fir_coeffs(n, 0, 70, 4))
+def test_designer_matches_reference_live(orc):
+    for d in reflive.answers("designer"):
+        assert len(d["params"]) == 60
+        for i, (n, fc, a, t, dfc) in enumerate(d["params"]):
+            n, t = int(n), int(t)
+            for pid in (False, True):
+                want = d["c%d_%s" % (i, reflive.PI[pid])]
+                got = orc.calc_fir_coeffs(n, fc, a, t, dfc, 24000.0, pi_double=pid)
+                assert np.array_equal(got, want), (n, fc, a, t, dfc, pid)
+        for n in (8, 32, 64):  # Hilbert branch (type 4), never used by the app
+            assert np.array_equal(orc.calc_fir_coeffs(n, 0, 70, 4), d["hilbert_n%d" % n])
 
 
-def test_izero_msinc_match_reference_live(orc, ref):
-    for x in np.linspace(0, 12, 97, dtype=np.float32):
-        assert orc.lib.orc_izero(float(x)) == ref.lib.Izero(float(x))
-    for m in range(-40, 41, 2):
-        for fc in (0.01, 0.2333, 0.5):
-            assert orc.lib.orc_m_sinc(m, fc) == ref.lib.m_sinc(m, fc)
+def test_izero_msinc_match_reference_live(orc):
+    for d in reflive.answers("izero_msinc"):
+        assert d["x"].size == 97 and d["m_sinc"].shape == (41, 3)
+        for x, want in zip(d["x"], d["izero"]):
+            assert orc.lib.orc_izero(float(x)) == float(want)
+        for m, row in zip(d["m"], d["m_sinc"]):
+            for fc, want in zip(d["fc"], row):
+                assert orc.lib.orc_m_sinc(int(m), float(fc)) == float(want)
 
 
 # ---------------------------------------------------------------- A3/A4 q15 FIR -----------
@@ -92,18 +93,14 @@ def test_fir_q15_init_rejects_odd_taps(orc, golden):
     assert rc == -1
 
 
-def test_fir_q15_matches_reference_live(orc, ref):
-    rng = np.random.default_rng(5)
-    for _ in range(40):
-        n = int(rng.integers(2, 140)) * 2
-        amp = int(rng.choice([300, 8000, 32767]))
-        taps = rng.integers(-amp, amp + 1, n).astype(np.int16)
-        blk = int(rng.choice([1, 2, 3, 4, 5, 64, 127, 128, 129, 256]))
-        x = rng.integers(-32768, 32768, blk * int(rng.integers(1, 5))).astype(np.int16)
-        rc_o, y_o = orc.fir_q15_blocks(taps, x, blk)
-        rc_r, y_r = ref.fir_q15_blocks(taps, x, blk)
-        assert rc_o == rc_r == 0
-        assert np.array_equal(y_o, y_r), (n, amp, blk)
+def test_fir_q15_matches_reference_live(orc):
+    for d in reflive.answers("fir_q15"):
+        assert int(d["cases"]) == 40
+        for i in range(int(d["cases"])):
+            taps, x, blk = d["c%d_taps" % i], d["c%d_x" % i], int(d["c%d_block" % i])
+            rc_o, y_o = orc.fir_q15_blocks(taps, x, blk)
+            assert rc_o == 0
+            assert np.array_equal(y_o, d["c%d_y" % i]), (taps.size, blk)
 
 
 def test_copy_and_sqrt_q31(orc, golden):
@@ -112,11 +109,11 @@ def test_copy_and_sqrt_q31(orc, golden):
         assert orc.sqrt_q31(int(v))[1] == int(want), int(v)
 
 
-def test_sqrt_q31_matches_reference_live(orc, ref):
-    rng = np.random.default_rng(9)
-    vals = list(rng.integers(-5, 2 ** 31, 3000)) + [2 ** 31 - 1, 1, 0, -2 ** 31] + [2 ** k for k in range(31)]
-    for v in vals:
-        assert orc.sqrt_q31(int(v)) == ref.sqrt_q31(int(v)), int(v)
+def test_sqrt_q31_matches_reference_live(orc):
+    for d in reflive.answers("sqrt_q31"):
+        assert d["in"].size == 3035
+        for v, rc, want in zip(d["in"], d["rc"], d["out"]):
+            assert orc.sqrt_q31(int(v)) == (int(rc), int(want)), int(v)
 
 
 # ---------------------------------------------------------------- A1+A4+A5 chain ----------
@@ -164,17 +161,12 @@ def test_rfft128_matches_golden(orc, golden):
         assert np.array_equal(out, want)     # split stage
 
 
-def test_rfft128_matches_reference_live(orc, ref):
-    rng = np.random.default_rng(128)
-    for case in range(300):
-        amp = (300, 8000, 32767, 32767)[case % 4]
-        x = rng.integers(-amp, amp + 1, 128).astype(np.int16)
-        if case % 4 == 3:
-            x[rng.integers(0, 128, 40)] = -32768
-            x[rng.integers(0, 128, 40)] = 32767
-        want, work = ref.rfft128_q15(x)
-        out, w = orc.rfft128_q15(x)
-        assert np.array_equal(w, work) and np.array_equal(out, want), case
+def test_rfft128_matches_reference_live(orc):
+    for d in reflive.answers("rfft128"):
+        assert d["x"].shape == (300, 128)
+        for case, (x, want, work) in enumerate(zip(d["x"], d["out"], d["work"])):
+            out, w = orc.rfft128_q15(x)
+            assert np.array_equal(w, work) and np.array_equal(out, want), case
 
 
 def test_rfft128_is_a_dft(orc):
@@ -244,44 +236,28 @@ def test_dspinst_primitives_match_golden(orc):
         assert L.orc_prim_pack_hist(x, int(b[i])) == int(g["pack_bb"][i]), (x, y)
 
 
-def test_dspinst_primitives_match_reference_live(orc, ref):
-    import ctypes as C
-    L, R = _prims(orc), ref.lib
-    for n in ("dspinst_signed_multiply_32x16b", "dspinst_signed_multiply_32x16t"):
-        getattr(R, n).restype = C.c_int32
-        getattr(R, n).argtypes = [C.c_int32, C.c_uint32]
-    R.dspinst_signed_saturate_rshift.restype = C.c_int32
-    R.dspinst_signed_saturate_rshift.argtypes = [C.c_int32, C.c_int, C.c_int]
-    R.dspinst_pack_16b_16b.restype = C.c_uint32
-    R.dspinst_pack_16b_16b.argtypes = [C.c_int32, C.c_int32]
-    rng = np.random.default_rng(77)
-    a = rng.integers(-2 ** 31, 2 ** 31, 30000).astype(np.int32)
-    b = rng.integers(-2 ** 31, 2 ** 31, 30000).astype(np.int32)
-    a[:8] = [0x7FFFFFFF, -0x80000000, 0x40000000, -0x40000000, -1, 1, 0x3FFF, -0x4000]
-    b[:8] = [-0x80000000, 0x7FFFFFFF, 0x80008000 - (1 << 32), 0x7FFF7FFF, -1, 0x00010001, 0x8000, 0x7FFF]
-    for x, y in zip(a, b):
-        x, yu = int(x), int(y) & 0xFFFFFFFF
-        assert L.orc_prim_mulw16b(x, yu) == R.dspinst_signed_multiply_32x16b(x, yu)
-        assert L.orc_prim_mulw16t(x, yu) == R.dspinst_signed_multiply_32x16t(x, yu)
-        for sh in (0, 1, 14, 15, 16):
-            assert L.orc_prim_ssat16_rshift(x, sh) == R.dspinst_signed_saturate_rshift(x, 16, sh)
-        assert L.orc_prim_pack_hist(x, int(y)) == R.dspinst_pack_16b_16b(x, int(y))
+def test_dspinst_primitives_match_reference_live(orc):
+    L = _prims(orc)
+    for d in reflive.answers("dspinst"):
+        assert d["a"].size == 30000 and d["ssat16"].shape == (len(reflive.SSAT_SHIFTS), 30000)
+        for i, (x, y) in enumerate(zip(d["a"], d["b"])):
+            x, yu = int(x), int(y) & 0xFFFFFFFF
+            assert L.orc_prim_mulw16b(x, yu) == int(d["mulwb"][i])
+            assert L.orc_prim_mulw16t(x, yu) == int(d["mulwt"][i])
+            for k, sh in enumerate(reflive.SSAT_SHIFTS):
+                assert L.orc_prim_ssat16_rshift(x, sh) == int(d["ssat16"][k, i])
+            assert L.orc_prim_pack_hist(x, int(y)) == int(d["pack_bb"][i])
 
 
-def test_am_sqrt_f32_matches_reference_live(orc, ref):
+def test_am_sqrt_f32_matches_reference_live(orc):
     """arm_sqrt_f32 (a static inline of the reference's arm_math.h, :5733-5758) as the Teensy-3.6 AM / CW branch calls it (Minimal-SDR.ino:611-612):
     every int32 the sum I*I + Q*Q can take goes through (float): negative sums (int overflow at full scale) give 0, not NaN."""
     import ctypes as C
     orc.lib.orc_prim_sqrt_f32.restype = C.c_float
     orc.lib.orc_prim_sqrt_f32.argtypes = [C.c_float]
-    ref.lib.cmsis_arm_sqrt_f32.restype = C.c_int
-    ref.lib.cmsis_arm_sqrt_f32.argtypes = [C.c_float, C.POINTER(C.c_float)]
-    rng = np.random.default_rng(5)
-    vals = np.concatenate([rng.integers(-2 ** 31, 2 ** 31, 20000).astype(np.float32), np.arange(0, 4096, dtype=np.float32) ** 2,
-                           np.array([0.0, -0.0, 1e-45, -1e-45, 2147483648.0, -2147483648.0, 2.0 * 32768.0 ** 2, np.inf], np.float32)])
-    for v in vals:
-        out = C.c_float(-1.0)
-        rc = ref.lib.cmsis_arm_sqrt_f32(float(v), C.byref(out))
-        got = orc.lib.orc_prim_sqrt_f32(float(v))
-        assert np.float32(got).tobytes() == np.float32(out.value).tobytes(), float(v)
-        assert rc == (0 if v >= 0 else -1)
+    for d in reflive.answers("am_sqrt_f32"):
+        assert d["in"].size == 20000 + 4096 + 8
+        for v, want, rc in zip(d["in"], d["out"], d["rc"]):
+            got = orc.lib.orc_prim_sqrt_f32(float(v))
+            assert np.float32(got).tobytes() == want.tobytes(), float(v)
+            assert rc == (0 if v >= 0 else -1)

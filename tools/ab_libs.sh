@@ -6,13 +6,14 @@ cd "${GRAFT_REPO_ROOT:-$(pwd)}"
 mkdir -p gpurun_out
 OUT=gpurun_out/ab_$TAG.txt
 : > $OUT
+J=$(mktemp)                        # one run's JSON line
 for wl in "$@"; do
   for rep in 1 2 3; do for lib in "$A" "$B"; do
-    MSDR_LIB=$PWD/$lib python bench.py --workload $wl --no-cpu ${AB_ARGS:-} > gpurun_out/ab_x.json 2>/dev/null
-    python - "$wl" "$lib" >> $OUT <<'PY'
+    MSDR_LIB=$PWD/$lib python bench.py --full --workload $wl --no-cpu ${AB_ARGS:-} > "$J" 2>/dev/null
+    python - "$wl" "$lib" "$J" >> $OUT <<'PY'
 import json, sys
 try:
-    d = json.load(open('gpurun_out/ab_x.json'))
+    d = json.load(open(sys.argv[3]))
     r = d['roofline']; p = d.get('parity', {})
     print('%-4s %-40s step_ms %.4f kernel_ms %.4f frac %.4f sclk %s W %s parity %s' % (sys.argv[1], sys.argv[2].split('/')[-1], d['ms_per_step'], r['kernel_ms'], r['frac'], r.get('sclk_mhz'), r.get('power_w'),
           p.get('rel_rms_worst', p.get('mismatching_samples'))))

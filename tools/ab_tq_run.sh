@@ -4,7 +4,7 @@ set -u
 O=gpurun_out/tq_run; mkdir -p $O
 for round in 1 2 3; do
  for rs in 0 1 2 3; do
-  MSDR_TQ_RUN_SHIFT=$rs python bench.py --workload fir --no-cpu > $O/fir_rs${rs}_r${round}.json 2> $O/err.txt
+  MSDR_TQ_RUN_SHIFT=$rs python bench.py --full --workload fir --no-cpu > $O/fir_rs${rs}_r${round}.json 2> $O/err.txt
   python - <<PY
 import json
 d=json.load(open("$O/fir_rs${rs}_r${round}.json"))

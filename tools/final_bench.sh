@@ -3,7 +3,7 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(pwd)}"
 O=gpurun_out/final; mkdir -p $O
-run() { name=$1; shift; python bench.py "$@" > $O/$name.json 2> $O/$name.err; python - "$O/$name.json" "$name" <<'PY'
+run() { name=$1; shift; python bench.py --full "$@" > $O/$name.json 2> $O/$name.err; python - "$O/$name.json" "$name" <<'PY'
 import json, sys
 try:
     d = json.load(open(sys.argv[1]))

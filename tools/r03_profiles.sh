@@ -19,7 +19,7 @@ for p in $PARTS; do
                STEPS=$(case $w in c4) echo 30000;; c5) echo 12000;; *) echo 4000;; esac) bash tools/smi_probe.sh $w -- --workload $w 2>&1 | grep -E "sclk|ms " | sed 's/GPU\[0\]\s*: //g; s/=\+ Power Consumption =\+//'
              done; } > $O/power_clock_samples.txt 2>&1 ;;
     final) bash tools/final_bench.sh > $O/final_bench_table.txt 2>&1; mkdir -p $O/final && cp gpurun_out/final/*.json $O/final/ 2>/dev/null ;;
-    default) python bench.py > $O/bench_default.json 2> $O/bench_default.err ;;
+    default) python bench.py --full > $O/bench_default.json 2> $O/bench_default.err ;;
   esac
   echo "$p done"
 done

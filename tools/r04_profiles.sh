@@ -16,7 +16,7 @@ for p in $PARTS; do
     pmc_fir) bash tools/pmc.sh fir --workload fir --no-parity > $O/fir_f32_sq_counters.txt 2>&1 ;;
     pmc_*) w=${p#pmc_}; bash tools/pmc.sh $w --workload $w --no-parity > $O/${w}_sq_counters.txt 2>&1 ;;
     final) bash tools/final_bench.sh > $O/final_bench_table.txt 2>&1; mkdir -p $O/final && cp gpurun_out/final/*.json $O/final/ 2>/dev/null ;;
-    default) python bench.py > $O/bench_default.json 2> $O/bench_default.err ;;
+    default) python bench.py --full > $O/bench_default.json 2> $O/bench_default.err ;;
   esac
   echo "$p done"
 done

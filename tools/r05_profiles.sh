@@ -21,7 +21,7 @@ for p in $PARTS; do
     prof_*) w=${p#prof_}; $G bash tools/profile.sh $w --workload $w --no-parity > $O/${w}_rocprof_summary.txt 2>&1 ;;
     pmc_c3_b128) $G bash tools/pmc.sh c3_b128 --workload c3 --samples 128 --channels 65536 --no-parity > $O/c3_b128_64k_sq_counters.txt 2>&1 ;;
     pmc_*) w=${p#pmc_}; $G bash tools/pmc.sh $w --workload $w --no-parity > $O/${w}_sq_counters.txt 2>&1 ;;
-    default) tools/memguard.sh -m 40 -t 600 python3 bench.py > $O/bench_default.json 2> $O/bench_default.err; cp bench_full.json $O/bench_full.json 2>/dev/null ;;
+    default) tools/memguard.sh -m 40 -t 600 python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err; cp bench_full.json $O/bench_full.json 2>/dev/null ;;
   esac
   echo "$p done"
 done

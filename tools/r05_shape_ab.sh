@@ -11,7 +11,7 @@ for round in 1 2 3; do
       lib=$P/lib/libmsdr.so; par=""
       [ $v = shape1 ] && lib=$P/lib_shape1/libmsdr.so
       [ $v = shape2 ] && { lib=$P/lib_shape2/libmsdr.so; par="--no-parity"; }
-      MSDR_LIB=$lib tools/memguard.sh -m 24 -t 200 python3 bench.py --workload $wl --steps 30 --warmup 10 --no-cpu $par 2>/dev/null | python3 -c "
+      MSDR_LIB=$lib tools/memguard.sh -m 24 -t 200 python3 bench.py --full --workload $wl --steps 30 --warmup 10 --no-cpu $par 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']
 print('round $round $wl $v kernel_ms', r['kernel_ms'], 'frac', r['frac'], 'sclk', r.get('sclk_mhz'), 'W', r.get('power_w'), 'parity', (d.get('parity') or {}).get('rel_rms_worst'))"
