@@ -306,6 +306,9 @@ int msdr_anr_destroy(msdr_anr *A);
  *                              d_columns[f][128] = the 127 column heights showSpectrum draws,
  *                              y_new[x] = min(abs(FFT_out[127 - x]) / 200, 16) (UI.cpp:557-572), entry 127 = 0.
  *                              Either output may be NULL.  Unlike the reference, d_src is NOT transformed in place.
+ *   msdr_rfft128_q15_inplace   the same, and like the reference (arm_rfft_q15.c:103-107) each transform also overwrites its
+ *                              128 samples of d_src with the buffer CMSIS leaves there: the complex FFT's output after the
+ *                              bit reversal (interleaved re, im of 64 bins).  Both outputs may be NULL; d_src is always written.
  *   msdr_rfft_q15_init_check   the argument check of arm_rfft_init_q15 (arm_rfft_init_q15.c:2154-2225): SUCCESS for
  *                              fftLenReal in {32 .. 8192} powers of two, else ARGUMENT_ERROR; this library runs 128 forward
  *                              with bit reversal only (what initSpectrum asks for) and reports other valid sizes as
@@ -320,6 +323,7 @@ int msdr_anr_destroy(msdr_anr *A);
 void msdr_rfft128_tables(int16_t tables[352]);
 int msdr_rfft_q15_init_check(uint32_t fftLenReal, uint32_t ifftFlagR, uint32_t bitReverseFlag);
 int msdr_rfft128_q15(msdr_ctx *ctx, const q15_t *d_src, uint64_t src_stride, q15_t *d_fft_out, uint8_t *d_columns, uint32_t nfft);
+int msdr_rfft128_q15_inplace(msdr_ctx *ctx, q15_t *d_src, uint64_t src_stride, q15_t *d_fft_out, uint8_t *d_columns, uint32_t nfft);
 typedef struct msdr_spectrum msdr_spectrum;
 int msdr_spectrum_create(msdr_ctx *ctx, uint32_t channels, msdr_spectrum **out);
 int msdr_spectrum_set_on(msdr_spectrum *S, int spectrum_on);
@@ -339,6 +343,20 @@ int msdr_freqconv_q15(msdr_ctx *ctx, q15_t *d_i, q15_t *d_q, const q15_t *osc_i,
                       int dir, int pass, uint32_t channels, uint32_t blockSize);
 int msdr_freqconv_f32(msdr_ctx *ctx, float32_t *d_i, float32_t *d_q, const float32_t *osc_i, const float32_t *osc_q,
                       uint32_t osc_len, int dir, int pass, uint32_t channels, uint32_t blockSize);
+/* arm_mult_q15 / arm_add_q15 / arm_sub_q15 (freq_conv.cpp:70-96) and arm_copy_q15 (Minimal-SDR.ino:577-578) over a block batch,
+ * one kernel per call, asynchronous on the context's stream:
+ *   d_dst[c][n] = op(d_a[c * a_stride + n], d_b[c * b_stride + n])    c < channels, n < blockSize; d_dst is dense [channels][blockSize]
+ *   mult: ssat16((a * b) >> 15)   add: ssat16(a + b)   sub: ssat16(a - b)   copy: a
+ * A source stride of 0 means ONE row of blockSize samples shared by every channel (an oscillator table); blockSize makes a source
+ * dense [channels][blockSize].  All pointers are device pointers, 2-byte aligned (16-byte aligned rows take 16-byte accesses).  d_dst
+ * may be d_a or d_b exactly (not a partial overlap, and not a shared row when channels > 1).  channels x blockSize < 2^31. */
+int msdr_mult_q15(msdr_ctx *ctx, const q15_t *d_a, uint64_t a_stride, const q15_t *d_b, uint64_t b_stride, q15_t *d_dst,
+                  uint32_t channels, uint32_t blockSize);
+int msdr_add_q15(msdr_ctx *ctx, const q15_t *d_a, uint64_t a_stride, const q15_t *d_b, uint64_t b_stride, q15_t *d_dst,
+                 uint32_t channels, uint32_t blockSize);
+int msdr_sub_q15(msdr_ctx *ctx, const q15_t *d_a, uint64_t a_stride, const q15_t *d_b, uint64_t b_stride, q15_t *d_dst,
+                 uint32_t channels, uint32_t blockSize);
+int msdr_copy_q15(msdr_ctx *ctx, const q15_t *d_src, uint64_t src_stride, q15_t *d_dst, uint32_t channels, uint32_t blockSize);
 /* demod switch, Minimal-SDR.ino:589-627.  d_mode: device int32 [channels] or NULL (then `mode` for all). */
 int msdr_demod_q15(msdr_ctx *ctx, int mode, const int32_t *d_mode, int sqrt_kind, const q15_t *d_i, const q15_t *d_q,
                    q15_t *d_out, uint32_t channels, uint32_t blockSize);

@@ -23,6 +23,7 @@
 #include "msdr_cascade_state.h"
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <complex>
 #include <cstdarg>
@@ -199,13 +200,33 @@ extern "C" int msdr_malloc(msdr_ctx *ctx, size_t bytes, void **d_ptr)
     HIP_TRY(hipMalloc(d_ptr, bytes ? bytes : 16));
     return 0;
 }
+static std::atomic<unsigned> g_free_generation{0};
 extern "C" int msdr_free(msdr_ctx *ctx, void *d_ptr)
 {
     if (int rc = bind(ctx)) return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    g_free_generation.fetch_add(1, std::memory_order_relaxed);      // msdr_cmsis.cpp's cache of device address ranges starts over
     HIP_TRY(hipFree(d_ptr));
     return 0;
 }
+// Not part of the C ABI (msdr_cmsis.cpp's operand rules).  What p points into: 1 = device memory of ctx's device (then [*base, *base +
+// *size) is its allocation), 0 = memory the host reads (pageable, pinned, registered or managed), -1 = device memory of another device.
+__attribute__((visibility("hidden"))) int msdr_ptr_query(msdr_ctx *ctx, const void *p, uintptr_t *base, size_t *size)
+{
+    *base = 0; *size = 0;
+    hipPointerAttribute_t a;
+    if (hipPointerGetAttributes(&a, p) != hipSuccess) { (void)hipGetLastError(); return 0; }     // not known to HIP: plain host memory
+    if (a.type != hipMemoryTypeDevice) return 0;
+    if (a.device != ctx->device) return -1;
+    hipDeviceptr_t b = nullptr;
+    size_t n = 0;
+    if (hipMemGetAddressRange(&b, &n, (hipDeviceptr_t)p) != hipSuccess) { (void)hipGetLastError(); *base = (uintptr_t)p; *size = 2; return 1; }
+    *base = (uintptr_t)b; *size = n;
+    return 1;
+}
+__attribute__((visibility("hidden"))) unsigned msdr_free_generation(void) { return g_free_generation.load(std::memory_order_relaxed); }
+// msdr_cmsis.cpp's refusals: the text msdr_last_error() returns
+__attribute__((visibility("hidden"))) int msdr_cmsis_fail(int code, const char *text) { return fail(code, "%s", text); }
 extern "C" int msdr_memcpy_h2d(msdr_ctx *ctx, void *d_dst, const void *src, size_t bytes)
 {
     if (int rc = bind(ctx)) return rc;
@@ -1540,6 +1561,44 @@ extern "C" int msdr_mix_fs4_q15(msdr_ctx *ctx, const q15_t *d_x, q15_t *d_i, q15
     return launch_check("mix_fs4_q15_kernel");
 }
 
+// arm_mult_q15 / arm_add_q15 / arm_sub_q15 / arm_copy_q15 over a block batch (msdr_q15_elementwise.hip)
+static int q15_elementwise(msdr_ctx *ctx, int op, const q15_t *d_a, uint64_t a_stride, const q15_t *d_b, uint64_t b_stride, q15_t *d_dst,
+                           uint32_t channels, uint32_t blockSize)
+{
+    if (int rc = bind(ctx)) return rc;
+    const long long n = (long long)channels * blockSize;
+    if (n == 0) return 0;
+    if (!d_a || !d_dst || (op != kQ15Copy && !d_b)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null buffer");
+    if (n >= (1LL << 31)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "q15 element-wise: channels x blockSize = %lld samples (limit 2^31 - 1)", n);
+    if ((a_stride | b_stride) >= (1ULL << 40)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "q15 element-wise: source row stride out of range");
+    if (((reinterpret_cast<uintptr_t>(d_a) | reinterpret_cast<uintptr_t>(d_dst) | (op != kQ15Copy ? reinterpret_cast<uintptr_t>(d_b) : 0)) & 1))
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "q15 element-wise: buffers must be 2-byte aligned");
+    const char *name = nullptr;
+    const hipError_t e = launch_q15_elementwise(ctx->stream, op, 256 * 8, d_a, (long long)a_stride, d_b, (long long)b_stride, d_dst,
+                                                channels, (int)blockSize, &name);
+    if (e != hipSuccess) return fail(MSDR_STATUS_HIP_ERROR, "launch of %s failed: %s", name ? name : "q15_elementwise_kernel", hipGetErrorString(e));
+    return 0;
+}
+extern "C" int msdr_mult_q15(msdr_ctx *ctx, const q15_t *d_a, uint64_t a_stride, const q15_t *d_b, uint64_t b_stride, q15_t *d_dst,
+                             uint32_t channels, uint32_t blockSize)
+{
+    return q15_elementwise(ctx, kQ15Mult, d_a, a_stride, d_b, b_stride, d_dst, channels, blockSize);
+}
+extern "C" int msdr_add_q15(msdr_ctx *ctx, const q15_t *d_a, uint64_t a_stride, const q15_t *d_b, uint64_t b_stride, q15_t *d_dst,
+                            uint32_t channels, uint32_t blockSize)
+{
+    return q15_elementwise(ctx, kQ15Add, d_a, a_stride, d_b, b_stride, d_dst, channels, blockSize);
+}
+extern "C" int msdr_sub_q15(msdr_ctx *ctx, const q15_t *d_a, uint64_t a_stride, const q15_t *d_b, uint64_t b_stride, q15_t *d_dst,
+                            uint32_t channels, uint32_t blockSize)
+{
+    return q15_elementwise(ctx, kQ15Sub, d_a, a_stride, d_b, b_stride, d_dst, channels, blockSize);
+}
+extern "C" int msdr_copy_q15(msdr_ctx *ctx, const q15_t *d_src, uint64_t src_stride, q15_t *d_dst, uint32_t channels, uint32_t blockSize)
+{
+    return q15_elementwise(ctx, kQ15Copy, d_src, src_stride, nullptr, 0, d_dst, channels, blockSize);
+}
+
 template <typename T, typename K>
 static int freqconv_common(msdr_ctx *ctx, T *d_i, T *d_q, const T *osc_i, const T *osc_q, uint32_t osc_len, int dir, int pass,
                            uint32_t channels, uint32_t blockSize, K kernel, const char *name)
@@ -1891,7 +1950,7 @@ extern "C" int msdr_rfft_q15_init_check(uint32_t fftLenReal, uint32_t ifftFlagR,
         return fail(MSDR_STATUS_LENGTH_ERROR, "only the 128-point forward transform with bit reversal (initSpectrum, UI.cpp:523) is built");
     return 0;
 }
-extern "C" int msdr_rfft128_q15(msdr_ctx *ctx, const q15_t *d_src, uint64_t src_stride, q15_t *d_fft_out, uint8_t *d_columns, uint32_t nfft)
+static int rfft128_common(msdr_ctx *ctx, q15_t *d_src, uint64_t src_stride, q15_t *d_fft_out, uint8_t *d_columns, uint32_t nfft, bool work)
 {
     if (int rc = bind(ctx)) return rc;
     if (nfft == 0) return 0;
@@ -1905,11 +1964,24 @@ extern "C" int msdr_rfft128_q15(msdr_ctx *ctx, const q15_t *d_src, uint64_t src_
         msdr::design::fft128_tables(h.data());
         if (int rc = upload(ctx, h, &ctx->d_fft_tables)) return rc;
     }
-    if (!d_fft_out && !d_columns) return 0;
     const int grid = (int)std::min<long long>(((long long)nfft + kFftPerBlock - 1) / kFftPerBlock, 256LL * 32);
-    hipLaunchKernelGGL(spectrum_rfft128_kernel, dim3(grid), dim3(256), 0, ctx->stream, (const short *)d_src, (long long)src_stride,
+    if (work) {      // pSrc is an output too: the transform runs even when neither of the other outputs is wanted
+        hipLaunchKernelGGL(spectrum_rfft128_kernel<true>, dim3(grid), dim3(256), 0, ctx->stream, (short *)d_src, (long long)src_stride,
+                           (short *)d_fft_out, (unsigned char *)d_columns, (const short *)ctx->d_fft_tables, (int)nfft);
+        return launch_check("spectrum_rfft128_kernel<work>");
+    }
+    if (!d_fft_out && !d_columns) return 0;
+    hipLaunchKernelGGL(spectrum_rfft128_kernel<false>, dim3(grid), dim3(256), 0, ctx->stream, (const short *)d_src, (long long)src_stride,
                        (short *)d_fft_out, (unsigned char *)d_columns, (const short *)ctx->d_fft_tables, (int)nfft);
     return launch_check("spectrum_rfft128_kernel");
+}
+extern "C" int msdr_rfft128_q15(msdr_ctx *ctx, const q15_t *d_src, uint64_t src_stride, q15_t *d_fft_out, uint8_t *d_columns, uint32_t nfft)
+{
+    return rfft128_common(ctx, const_cast<q15_t *>(d_src), src_stride, d_fft_out, d_columns, nfft, false);
+}
+extern "C" int msdr_rfft128_q15_inplace(msdr_ctx *ctx, q15_t *d_src, uint64_t src_stride, q15_t *d_fft_out, uint8_t *d_columns, uint32_t nfft)
+{
+    return rfft128_common(ctx, d_src, src_stride, d_fft_out, d_columns, nfft, true);
 }
 
 struct msdr_spectrum {

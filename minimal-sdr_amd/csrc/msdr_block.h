@@ -3,6 +3,7 @@
 //   msdr_chain_block.hip   the block-cadence kernels (round 5)
 //   msdr_chain_stream.hip  the long-call chain kernels: chain_mfw_kernel (all flavours), chain_amtr_kernel, chain_fold_kernel, chain_kernel<Arith>, chain_q15mf_kernel
 //   msdr_fir_stage.hip     the arm_fir_f32 stage: fir_f32tq_kernel, fir_f32mf_kernel
+//   msdr_q15_elementwise.hip  arm_mult_q15 / arm_add_q15 / arm_sub_q15 / arm_copy_q15 over a block batch: q15_elementwise_kernel
 // Host-side geometry helpers (LDS sizes, table formats) live with the kernels' headers.  Every launcher returns the HIP error of its launch.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -25,4 +26,10 @@ struct TqParams;
 hipError_t launch_fir_f32tq(hipStream_t stream, int ns, bool skip1, unsigned grid, size_t lds_bytes, const TqParams &q);
 hipError_t launch_fir_f32mf(hipStream_t stream, unsigned grid, unsigned block, size_t lds_bytes, const float *x, float *y, const float *hist, const char *tab,
                             long long n, int channels, int nseg, long long seg_len, int hist_len, int halo, int nsteps, int nw);
+// ---- msdr_q15_elementwise.hip ----
+constexpr int kQ15Mult = 0, kQ15Add = 1, kQ15Sub = 2, kQ15Copy = 3;
+// dst[rows][cols] = op(a row r, b row r); source row r at a + r * a_stride (0: one shared row); b unused for kQ15Copy.  rows * cols < 2^31.
+// At most max_grid workgroups of 256 (grid-stride beyond).  *kernel (optional) = the name of the shape launched.
+hipError_t launch_q15_elementwise(hipStream_t stream, int op, int max_grid, const short *a, long long a_stride, const short *b, long long b_stride,
+                                  short *dst, long long rows, int cols, const char **kernel);
 }  // namespace msdr

@@ -114,6 +114,10 @@ def load_library(path=None):
         _lib.msdr_rfft128_tables.restype = None
         _lib.msdr_rfft_q15_init_check.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32]
         _lib.msdr_rfft128_q15.argtypes = [_p, _p, C.c_uint64, _p, _p, C.c_uint32]
+        _lib.msdr_rfft128_q15_inplace.argtypes = [_p, _p, C.c_uint64, _p, _p, C.c_uint32]
+        for n in ("msdr_mult_q15", "msdr_add_q15", "msdr_sub_q15"):
+            getattr(_lib, n).argtypes = [_p, _p, C.c_uint64, _p, C.c_uint64, _p, C.c_uint32, C.c_uint32]
+        _lib.msdr_copy_q15.argtypes = [_p, _p, C.c_uint64, _p, C.c_uint32, C.c_uint32]
         _lib.msdr_spectrum_create.argtypes = [_p, C.c_uint32, _p]
         _lib.msdr_spectrum_set_on.argtypes = [_p, C.c_int]
         _lib.msdr_spectrum_show.argtypes = [_p, _p, C.c_uint64, _p, _p, _p]
@@ -261,6 +265,25 @@ class Context:
         oi, oq = np.ascontiguousarray(osc_i, np.int16), np.ascontiguousarray(osc_q, np.int16)
         _ck(self.lib.msdr_freqconv_q15(self.h, _p(d_i.ptr), _p(d_q.ptr), _hp(oi), _hp(oq), C.c_uint32(oi.size),
                                        int(direction), int(passthrough), C.c_uint32(channels), C.c_uint32(n)))
+
+    # arm_mult_q15 / arm_add_q15 / arm_sub_q15 / arm_copy_q15 over a block batch: d_dst [channels][n] = op(a row c, b row c); a source's
+    # row stride defaults to n (a dense batch), 0 = one row of n samples shared by every channel
+    def _q15_binary(self, name, d_a, d_b, d_dst, channels, n, a_stride, b_stride):
+        _ck(getattr(self.lib, name)(self.h, _p(d_a.ptr), C.c_uint64(n if a_stride is None else a_stride), _p(d_b.ptr),
+                                    C.c_uint64(n if b_stride is None else b_stride), _p(d_dst.ptr), C.c_uint32(channels), C.c_uint32(n)))
+
+    def mult_q15(self, d_a, d_b, d_dst, channels, n, a_stride=None, b_stride=None):
+        self._q15_binary("msdr_mult_q15", d_a, d_b, d_dst, channels, n, a_stride, b_stride)
+
+    def add_q15(self, d_a, d_b, d_dst, channels, n, a_stride=None, b_stride=None):
+        self._q15_binary("msdr_add_q15", d_a, d_b, d_dst, channels, n, a_stride, b_stride)
+
+    def sub_q15(self, d_a, d_b, d_dst, channels, n, a_stride=None, b_stride=None):
+        self._q15_binary("msdr_sub_q15", d_a, d_b, d_dst, channels, n, a_stride, b_stride)
+
+    def copy_q15(self, d_src, d_dst, channels, n, src_stride=None):
+        _ck(self.lib.msdr_copy_q15(self.h, _p(d_src.ptr), C.c_uint64(n if src_stride is None else src_stride), _p(d_dst.ptr),
+                                   C.c_uint32(channels), C.c_uint32(n)))
 
     def freqconv_f32(self, d_i, d_q, osc_i, osc_q, direction, passthrough, channels, n):
         oi, oq = np.ascontiguousarray(osc_i, np.float32), np.ascontiguousarray(osc_q, np.float32)
@@ -520,6 +543,13 @@ def rfft128_q15(ctx, d_src, src_stride, nfft, d_fft_out=None, d_columns=None):
     """arm_rfft_q15(&FFT(128, 0, 1), ...) batched (UI.cpp:551) + showSpectrum's column heights (UI.cpp:557-572)."""
     _ck(ctx.lib.msdr_rfft128_q15(ctx.h, d_src.ptr, C.c_uint64(src_stride), d_fft_out.ptr if d_fft_out is not None else None,
                                  d_columns.ptr if d_columns is not None else None, C.c_uint32(nfft)))
+
+
+def rfft128_q15_inplace(ctx, d_src, src_stride, nfft, d_fft_out=None, d_columns=None):
+    """rfft128_q15, and like arm_rfft_q15 (arm_rfft_q15.c:103-107) each transform's 128 samples of d_src are overwritten with the CMSIS
+    work buffer (the complex FFT's output after the bit reversal)."""
+    _ck(ctx.lib.msdr_rfft128_q15_inplace(ctx.h, d_src.ptr, C.c_uint64(src_stride), d_fft_out.ptr if d_fft_out is not None else None,
+                                         d_columns.ptr if d_columns is not None else None, C.c_uint32(nfft)))
 
 
 class Spectrum(_Instance):
