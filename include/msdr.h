@@ -222,10 +222,19 @@ int msdr_biquad_df1_f32_state_from_cmsis(uint8_t numStages, const float32_t *pCo
  * definition, filter_biquad.h:36-39).  set_coefficients keeps the filter history like the
  * reference (filter_biquad.cpp:95-97) and silently ignores stage >= 4 (:86).
  * update(): in place on d_data [channels][blockSize]; blockSize must be even (the reference
- * processes sample pairs, :54-74). */
+ * processes sample pairs, :54-74).
+ * set_coefficients_channels: the same setCoefficients(stage, coef) on channels first_channel ..
+ * first_channel + count - 1 only, each with its own five words -- a bank of receivers, each with the
+ * notch of the frequency it is tuned to (tune(), Minimal-SDR.ino:343-356).  coef is a HOST array
+ * [count][5] as given to setCoefficients; the other channels' records are not touched; count == 0 and
+ * stage >= 4 do nothing; a range past `channels` is MSDR_STATUS_ARGUMENT_ERROR.  From the first such
+ * call on update() runs the kernel that reads every channel's own coefficients and stage count
+ * (channels may then run 1 .. 4 stages side by side); set_coefficients keeps writing all channels. */
 typedef struct msdr_biquad_q15 msdr_biquad_q15;
 int msdr_biquad_q15_create(msdr_ctx *ctx, uint32_t channels, msdr_biquad_q15 **out);
 int msdr_biquad_q15_set_coefficients(msdr_biquad_q15 *S, uint32_t stage, const int32_t coef[5]);
+int msdr_biquad_q15_set_coefficients_channels(msdr_biquad_q15 *S, uint32_t first_channel, uint32_t count,
+                                              uint32_t stage, const int32_t *coef);
 int msdr_biquad_q15_update(msdr_biquad_q15 *S, q15_t *d_data, uint32_t blockSize);
 int msdr_biquad_q15_get_definition(msdr_biquad_q15 *S, uint32_t channel, int32_t definition[32]); /* filter_biquad.h:152 */
 int msdr_biquad_q15_destroy(msdr_biquad_q15 *S);
@@ -462,6 +471,11 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  * msdr_chain_set_node_coefficients (Q15): AudioFilterBiquad::setCoefficients(stage, coef) on biquad node `node` (0 = biquad1_dac,
  *   1 = biquad2_dac) of a running chain -- tune() re-programming the notch on every retune, Minimal-SDR.ino:356 ->
  *   filter_biquad.cpp:84-100; history kept (:95-97), stage >= 4 silently ignored (:86).
+ * msdr_chain_set_node_coefficients_channels (Q15): the same on channels first_channel .. first_channel + count - 1 only, coef a HOST
+ *   array [count][5] (msdr_biquad_q15_set_coefficients_channels): every receiver of the bank its own notch.  From the first such call
+ *   on the chain runs its nodes as a kernel of their own behind the demodulator kernel (two launches per 128-sample tick instead of
+ *   one); a msdr_chain_graph made before that call is refused afterwards, one made after it replays as usual.  The per-channel
+ *   coefficients survive msdr_chain_set_taps / set_mode / set_osc, msdr_chain_reset and msdr_chain_init_fir.
  * msdr_chain_set_biquad_coeffs (F32): all 5 * num_biquad_stages coefficients of the arm_biquad_cascade_df1_f32 stage, CMSIS
  *   semantics (the filter carries on from the pState arm_biquad_cascade_df1_f32 would hold; see msdr_biquad_df1_f32_set_coeffs).
  *   The number of stages is fixed at creation, as numStages is in CMSIS.
@@ -472,6 +486,8 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   tables for as long as the history holds samples of theirs (a 17th change inside ONE history length drops the oldest). */
 int msdr_chain_set_taps(msdr_chain *chain, uint32_t tapset, const void *coeffs_i, const void *coeffs_q);
 int msdr_chain_set_node_coefficients(msdr_chain *chain, uint32_t node, uint32_t stage, const int32_t coef[5]);
+int msdr_chain_set_node_coefficients_channels(msdr_chain *chain, uint32_t node, uint32_t first_channel,
+                                              uint32_t count, uint32_t stage, const int32_t *coef);
 int msdr_chain_set_biquad_coeffs(msdr_chain *chain, const float32_t *biquad_coeffs);
 int msdr_chain_set_osc(msdr_chain *chain, const void *osc_i, const void *osc_q);
 /* ANR_on per channel (host array of `channels` values, or NULL: anr_on_all for every channel); the LMS filter then runs between

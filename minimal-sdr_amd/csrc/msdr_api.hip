@@ -1467,6 +1467,8 @@ struct msdr_biquad_q15 {
     int *d_defs;      // [channels][32]
     int max_stage;    // highest stage index given to setCoefficients so far (-1: none): stages above 0 chain through the records' flag bits
     int pipe_ch;      // channels per workgroup of biquad_teensy_pipe4_kernel (64 / 32 / 16), 0: never that kernel (read at create time)
+    bool per_channel; // set by the first msdr_biquad_q15_set_coefficients_channels, for the instance's life: the records may differ from channel to
+                      // channel, so update() runs biquad_teensy_pc_kernel (every lane its own coefficients and stage count, msdr_biquad_pc.hiph)
 };
 static int tq4_pipe_ch_at_create(uint32_t channels)
 {
@@ -1483,6 +1485,20 @@ __global__ void tbq_set_coef_kernel(int *defs, int channels, int stage, int c0, 
         dest[0] = c0; dest[1] = c1; dest[2] = c2;
         dest[3] = (int)(0u - (unsigned)c3);
         dest[4] = (int)(0u - (unsigned)c4);
+        dest[7] &= 0x80000000;
+    }
+}
+
+// the same on channels first .. first + count - 1, each with its own five words: coef [count][5] (device)
+__global__ void tbq_set_coef_channels_kernel(int *defs, int first, int count, int stage, const int *coef)
+{
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
+        int *dest = defs + (long long)(first + i) * 32 + (stage << 3);
+        const int *c = coef + 5 * (long long)i;
+        if (stage > 0) dest[-1] |= 0x80000000;
+        dest[0] = c[0]; dest[1] = c[1]; dest[2] = c[2];
+        dest[3] = (int)(0u - (unsigned)c[3]);
+        dest[4] = (int)(0u - (unsigned)c[4]);
         dest[7] &= 0x80000000;
     }
 }
@@ -1510,6 +1526,26 @@ extern "C" int msdr_biquad_q15_set_coefficients(msdr_biquad_q15 *S, uint32_t sta
                        (int)stage, coef[0], coef[1], coef[2], coef[3], coef[4]);
     return launch_check("tbq_set_coef_kernel");
 }
+extern "C" int msdr_biquad_q15_set_coefficients_channels(msdr_biquad_q15 *S, uint32_t first_channel, uint32_t count, uint32_t stage, const int32_t *coef)
+{
+    if (!S) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null instance");
+    if (stage >= 4 || count == 0) return 0;                     // filter_biquad.cpp:86: silently ignored
+    if (!coef) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null coefficient array");
+    if (first_channel >= S->channels || count > S->channels - first_channel)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "channels %u .. %llu of %u", first_channel, (unsigned long long)first_channel + count - 1, S->channels);
+    if (int rc = bind(S->ctx)) return rc;
+    // the host array goes to the device in stream order; the staging buffer lives until the kernel that reads it has run
+    int32_t *d_coef = nullptr;
+    if (int rc = upload(S->ctx, std::vector<int32_t>(coef, coef + 5 * (size_t)count), &d_coef)) return rc;
+    S->max_stage = std::max(S->max_stage, (int)stage);
+    S->per_channel = true;
+    hipLaunchKernelGGL(tbq_set_coef_channels_kernel, dim3(grid_1d(count)), dim3(256), 0, S->ctx->stream, S->d_defs, (int)first_channel, (int)count,
+                       (int)stage, (const int *)d_coef);
+    int rc = launch_check("tbq_set_coef_channels_kernel");
+    if (!rc && hipStreamSynchronize(S->ctx->stream) != hipSuccess) rc = fail(MSDR_STATUS_HIP_ERROR, "tbq_set_coef_channels_kernel failed");
+    hipFree(d_coef);
+    return rc;
+}
 extern "C" int msdr_biquad_q15_update(msdr_biquad_q15 *S, q15_t *d_data, uint32_t blockSize)
 {
     if (!S) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null instance");
@@ -1517,6 +1553,11 @@ extern "C" int msdr_biquad_q15_update(msdr_biquad_q15 *S, q15_t *d_data, uint32_
     if (blockSize == 0) return 0;
     if (!d_data) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null buffer");
     if (blockSize & 1u) return fail(MSDR_STATUS_LENGTH_ERROR, "AudioFilterBiquad processes sample pairs: blockSize must be even");
+    if (S->per_channel) {                                       // records differ from channel to channel: nothing of them is wave-uniform
+        if (launch_biquad_teensy_pc(S->ctx->stream, 1, (short *)d_data, S->d_defs, nullptr, (int)S->channels, (long long)blockSize) != hipSuccess)
+            return fail(MSDR_STATUS_HIP_ERROR, "biquad_teensy_pc_kernel<1> launch failed");
+        return launch_check("biquad_teensy_pc_kernel<1>");
+    }
     if (S->max_stage == 0 && (blockSize & 127u) == 0 && (reinterpret_cast<uintptr_t>(d_data) & 15) == 0 && S->pipe_ch) {
         // one stage, slab-shaped batch: the recursion alone on one wave, the input products element-wise on the others (msdr_kernels.hiph)
         const int per_group = S->pipe_ch;
@@ -2190,6 +2231,14 @@ struct msdr_chain {
     double timed_ms;
     uint64_t timed_launches;
 };
+
+// a node of the chain has per-channel coefficients (msdr_chain_set_node_coefficients_channels): the kernels that keep a node's coefficients
+// wave-uniform -- the node phase of chain_q15mb_kernel, biquad_teensy_blk / pipe4 / pipe / biquad_teensy_kernel<2> -- step aside for
+// biquad_teensy_pc_kernel<2> behind the demodulator kernel
+static bool chain_nodes_per_channel(const msdr_chain *c)
+{
+    return (c->nodes[0] && c->nodes[0]->per_channel) || (c->nodes[1] && c->nodes[1]->per_channel);
+}
 
 static void chain_post_free(msdr_chain *c)
 {
@@ -3394,7 +3443,8 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         if (int rc = chain_block_tiles(c, (int)n_samples, [&](uint32_t ch) { const int m = c->h_mode[ch]; return (m == MSDR_MODE_LSB || m == MSDR_MODE_USB) ? 0 : 1; },
                                        [&](uint32_t ch) { return c->h_tapset[ch]; },
                                        [&](int w, int tpw) { return qb_lds_bytes(c->qm_halo, (int)n_samples, c->qm_bsteps, w, tpw); },
-                                       (c->nnodes == 2 && c->nodes[0]->max_stage == 0 && c->nodes[1]->max_stage == 0 && n_samples == 128 && !c->no_fuse) ? 3 : 0)) return rc;
+                                       (c->nnodes == 2 && c->nodes[0]->max_stage == 0 && c->nodes[1]->max_stage == 0 && n_samples == 128 && !c->no_fuse &&
+                                        !chain_nodes_per_channel(c)) ? 3 : 0)) return rc;
         nseg = 1; p.nseg = 1; p.warm = 0;
     } else
     if (use_mfw) {
@@ -3543,7 +3593,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         // demodulator and the nodes), one 128-sample block, and every launch of this call with one tile per wave on three or more waves
         // (small batches: up to 16 384 channels of one flavour on this part); MSDR_Q15_NO_FUSE=1 at create time: the node kernel behind it as before
         nodes_fused = c->nnodes == 2 && c->nodes[0]->max_stage == 0 && c->nodes[1]->max_stage == 0 && n_samples == 128 && !pll_active &&
-                      !(c->anr && (c->d_anr_on || c->anr_all > 0)) && !c->no_fuse;
+                      !(c->anr && (c->d_anr_on || c->anr_all > 0)) && !c->no_fuse && !chain_nodes_per_channel(c);
         for (int part = 0; part < 2 && nodes_fused; part++) {
             const msdr_chain::BlockPart &bp = c->bpart[part];
             if (bp.wgs && (bp.tpw != 1 || bp.nw < 3 || qb_nodes_lds_bytes(c->qm_halo, 128, c->qm_bsteps, (int)bp.nw) > 160 * 1024)) nodes_fused = false;
@@ -3630,6 +3680,10 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         // while its 16-channel workgroups find a CU each (4096 channels: 15.1 -> 13.2 us per tick; at 8192 the slab kernel is ahead again,
         // 16.6 vs 17.3, tools/r05_nodes_x.sh); MSDR_BIQUAD_BLK=0 / 1 at create time overrides
         const uint32_t blk_wgs = (c->channels + kTqbCh - 1) / kTqbCh;
+        if (chain_nodes_per_channel(c)) {      // every channel its own records: one lane = one channel with its own coefficients, any shape
+            if (launch_biquad_teensy_pc(c->ctx->stream, 2, (short *)d_audio, c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels, (long long)n_samples) != hipSuccess)
+                return fail(MSDR_STATUS_HIP_ERROR, "biquad_teensy_pc_kernel<2> launch failed");
+        } else
         if (n_samples == 128 && (reinterpret_cast<uintptr_t>(d_audio) & 15) == 0 && c->nodes[0]->max_stage == 0 && c->nodes[1]->max_stage == 0 &&
             (c->blk_force >= 1 || (c->blk_force < 0 && blk_wgs <= (uint32_t)c->ctx->num_cus)))
             hipLaunchKernelGGL(biquad_teensy_blk_kernel, dim3(blk_wgs), dim3(kTqbThreads), tqb_lds_bytes(), c->ctx->stream, (short *)d_audio,
@@ -3706,11 +3760,12 @@ struct msdr_chain_graph {
     const void *k_hist, *k_state, *k_tab, *k_tiles;
     int k_cur;
     uint64_t k_mode_gen;
+    bool k_nodes_pc;       // the biquad nodes ran per channel (a kernel of its own behind the demodulator kernel) when the launches were captured
 };
 static void chain_graph_key(const msdr_chain *c, msdr_chain_graph *g)
 {
     g->k_hist = c->d_hist[c->cur]; g->k_state = c->d_bq_state; g->k_tab = c->arith == MSDR_ARITH_F32 ? (const void *)c->d_mf_tab : (const void *)c->d_qm_tab;
-    g->k_tiles = c->d_btiles; g->k_cur = c->cur; g->k_mode_gen = c->mode_gen;
+    g->k_tiles = c->d_btiles; g->k_cur = c->cur; g->k_mode_gen = c->mode_gen; g->k_nodes_pc = chain_nodes_per_channel(c);
 }
 
 extern "C" int msdr_chain_graph_create(msdr_chain *c, uint32_t ticks, const int16_t *const *d_if, void *const *d_audio, uint64_t n_samples, msdr_chain_graph **out)
@@ -3766,6 +3821,8 @@ extern "C" int msdr_chain_graph_launch(msdr_chain_graph *g)
     chain_graph_key(c, &now);
     if (now.k_hist != g->k_hist || now.k_state != g->k_state || now.k_tab != g->k_tab || now.k_tiles != g->k_tiles || now.k_cur != g->k_cur || now.k_mode_gen != g->k_mode_gen)
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "the chain has changed since this graph was made (a live update, a reset, or an odd number of direct calls in between): make the graph again");
+    if (now.k_nodes_pc != g->k_nodes_pc)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "a biquad node got per-channel coefficients since this graph was made (its captured launches keep a node's coefficients uniform): make the graph again");
     HIP_TRY(hipGraphLaunch(g->exec, c->ctx->stream));
     c->gen += g->ticks;                                     // (an even number of calls: buffers, table position and caches stay as they are)
     return 0;
@@ -4114,6 +4171,23 @@ extern "C" int msdr_chain_set_node_coefficients(msdr_chain *c, uint32_t node, ui
     std::vector<int32_t> &h = c->store.node[node];                              // keep the stored configuration in step
     if (h.size() < 5 * (size_t)(stage + 1)) h.resize(5 * (size_t)(stage + 1), 0);
     memcpy(h.data() + 5 * stage, coef, 5 * sizeof(int32_t));
+    c->store.cfg.node_stages[node] = std::max<uint32_t>(c->store.cfg.node_stages[node], stage + 1);
+    return 0;
+}
+
+extern "C" int msdr_chain_set_node_coefficients_channels(msdr_chain *c, uint32_t node, uint32_t first_channel, uint32_t count, uint32_t stage, const int32_t *coef)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (int rc = bind(c->ctx)) return rc;
+    if (c->arith != MSDR_ARITH_Q15) return fail(MSDR_STATUS_ARGUMENT_ERROR, "AudioFilterBiquad nodes belong to Q15 chains (fp32: msdr_chain_set_biquad_coeffs)");
+    if (node >= c->nnodes || !c->nodes[node]) return fail(MSDR_STATUS_ARGUMENT_ERROR, "node %u of %u", node, c->nnodes);
+    if (stage >= 4 || count == 0) return 0;                                   // filter_biquad.cpp:86
+    if (int rc = msdr_biquad_q15_set_coefficients_channels(c->nodes[node], first_channel, count, stage, coef)) return rc;
+    // The per-channel coefficients live in the node's records alone, and the node objects outlive every rebuild (chain_rebuild hands them
+    // over), msdr_chain_reset and msdr_chain_init_fir.  The stored configuration keeps the node's stage count in step; its own (uniform)
+    // coefficients only ever initialise the records of a rebuild's throw-away node.
+    std::vector<int32_t> &h = c->store.node[node];
+    if (h.size() < 5 * (size_t)(stage + 1)) h.resize(5 * (size_t)(stage + 1), 0);
     c->store.cfg.node_stages[node] = std::max<uint32_t>(c->store.cfg.node_stages[node], stage + 1);
     return 0;
 }

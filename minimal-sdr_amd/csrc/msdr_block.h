@@ -4,6 +4,7 @@
 //   msdr_chain_stream.hip  the long-call chain kernels: chain_mfw_kernel (all flavours), chain_amtr_kernel, chain_fold_kernel, chain_kernel<Arith>, chain_q15mf_kernel
 //   msdr_fir_stage.hip     the arm_fir_f32 stage: fir_f32tq_kernel, fir_f32mf_kernel
 //   msdr_q15_elementwise.hip  arm_mult_q15 / arm_add_q15 / arm_sub_q15 / arm_copy_q15 over a block batch: q15_elementwise_kernel
+//   msdr_biquad_pc.hip     AudioFilterBiquad with per-channel coefficients: biquad_teensy_pc_kernel
 // Host-side geometry helpers (LDS sizes, table formats) live with the kernels' headers.  Every launcher returns the HIP error of its launch.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -32,4 +33,8 @@ constexpr int kQ15Mult = 0, kQ15Add = 1, kQ15Sub = 2, kQ15Copy = 3;
 // At most max_grid workgroups of 256 (grid-stride beyond).  *kernel (optional) = the name of the shape launched.
 hipError_t launch_q15_elementwise(hipStream_t stream, int op, int max_grid, const short *a, long long a_stride, const short *b, long long b_stride,
                                   short *dst, long long rows, int cols, const char **kernel);
+// ---- msdr_biquad_pc.hip ----
+// biquad_teensy_pc_kernel<nodes> (msdr_biquad_pc.hiph): nodes = 1 or 2 AudioFilterBiquad nodes in series, in place on data [channels][n] (n even),
+// every channel with the coefficients and stage count of its own record in defs0 / defs1 ([channels][32]; defs1 unused for one node)
+hipError_t launch_biquad_teensy_pc(hipStream_t stream, int nodes, short *data, int *defs0, int *defs1, int channels, long long n);
 }  // namespace msdr

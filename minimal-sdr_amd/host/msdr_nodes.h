@@ -27,40 +27,67 @@ public:
         transmit(block);
         release(block);
     }
-    void setCoefficients(uint32_t stage, const int *coefficients)
-    {
-        if (stage >= 4) return;                                // filter_biquad.cpp:86
-        pending.push_back({stage, {coefficients[0], coefficients[1], coefficients[2], coefficients[3], coefficients[4]}});
-        if (AudioGPU.context()) ensure();
-    }
-    void setCoefficients(uint32_t stage, const double *coefficients)      // filter_biquad.h:43-51
-    {
-        int coef[5];
-        for (int i = 0; i < 5; i++) coef[i] = (int)(coefficients[i] * 1073741824.0);
-        setCoefficients(stage, coef);
-    }
-    void setLowpass(uint32_t stage, float frequency, float q = 0.7071f) { design(stage, MSDR_BQ_LOWPASS, frequency, q, 1.0f); }
-    void setHighpass(uint32_t stage, float frequency, float q = 0.7071f) { design(stage, MSDR_BQ_HIGHPASS, frequency, q, 1.0f); }
-    void setBandpass(uint32_t stage, float frequency, float q = 1.0f) { design(stage, MSDR_BQ_BANDPASS, frequency, q, 1.0f); }
-    void setNotch(uint32_t stage, float frequency, float q = 1.0f) { design(stage, MSDR_BQ_NOTCH, frequency, q, 1.0f); }
-    void setLowShelf(uint32_t stage, float frequency, float gain, float slope = 1.0f) { design(stage, MSDR_BQ_LOWSHELF, frequency, gain, slope); }
-    void setHighShelf(uint32_t stage, float frequency, float gain, float slope = 1.0f) { design(stage, MSDR_BQ_HIGHSHELF, frequency, gain, slope); }
+    void setCoefficients(uint32_t stage, const int *coefficients) { set(kAll, stage, coefficients); }
+    void setCoefficients(uint32_t stage, const double *coefficients) { set(kAll, stage, coefficients); }      // filter_biquad.h:43-51
+    void setLowpass(uint32_t stage, float frequency, float q = 0.7071f) { design(kAll, stage, MSDR_BQ_LOWPASS, frequency, q, 1.0f); }
+    void setHighpass(uint32_t stage, float frequency, float q = 0.7071f) { design(kAll, stage, MSDR_BQ_HIGHPASS, frequency, q, 1.0f); }
+    void setBandpass(uint32_t stage, float frequency, float q = 1.0f) { design(kAll, stage, MSDR_BQ_BANDPASS, frequency, q, 1.0f); }
+    void setNotch(uint32_t stage, float frequency, float q = 1.0f) { design(kAll, stage, MSDR_BQ_NOTCH, frequency, q, 1.0f); }
+    void setLowShelf(uint32_t stage, float frequency, float gain, float slope = 1.0f) { design(kAll, stage, MSDR_BQ_LOWSHELF, frequency, gain, slope); }
+    void setHighShelf(uint32_t stage, float frequency, float gain, float slope = 1.0f) { design(kAll, stage, MSDR_BQ_HIGHSHELF, frequency, gain, slope); }
+    // One receiver of the bank: the node's own setters on channel ch only, so a per-receiver tune() reads
+    //     biquad2_dac.channel(rx).setNotch(0, pdb_freq_actual / 8.0 * CORR_FACT, 15.0);          (Minimal-SDR.ino:356)
+    // (A proxy, not overloads with a leading channel argument: setNotch(0, 3000, 15) would be ambiguous.)  Calls made before
+    // AudioGPU.begin queue with their channel, in order with the all-channel calls.
+    class Channel {
+    public:
+        void setCoefficients(uint32_t stage, const int *coefficients) { node.set(ch, stage, coefficients); }
+        void setCoefficients(uint32_t stage, const double *coefficients) { node.set(ch, stage, coefficients); }
+        void setLowpass(uint32_t stage, float frequency, float q = 0.7071f) { node.design(ch, stage, MSDR_BQ_LOWPASS, frequency, q, 1.0f); }
+        void setHighpass(uint32_t stage, float frequency, float q = 0.7071f) { node.design(ch, stage, MSDR_BQ_HIGHPASS, frequency, q, 1.0f); }
+        void setBandpass(uint32_t stage, float frequency, float q = 1.0f) { node.design(ch, stage, MSDR_BQ_BANDPASS, frequency, q, 1.0f); }
+        void setNotch(uint32_t stage, float frequency, float q = 1.0f) { node.design(ch, stage, MSDR_BQ_NOTCH, frequency, q, 1.0f); }
+        void setLowShelf(uint32_t stage, float frequency, float gain, float slope = 1.0f) { node.design(ch, stage, MSDR_BQ_LOWSHELF, frequency, gain, slope); }
+        void setHighShelf(uint32_t stage, float frequency, float gain, float slope = 1.0f) { node.design(ch, stage, MSDR_BQ_HIGHSHELF, frequency, gain, slope); }
+    private:
+        friend class AudioFilterBiquad;
+        Channel(AudioFilterBiquad &n, uint32_t c) : node(n), ch(c) {}
+        AudioFilterBiquad &node;
+        uint32_t ch;
+    };
+    Channel channel(uint32_t ch) { return Channel(*this, ch); }
     // definition[32] of one channel, as filter_biquad.h:152 lays it out (test/debug aid)
     int getDefinition(uint32_t channel, int32_t definition[32]) { return ensure() ? msdr_biquad_q15_get_definition(node, channel, definition) : MSDR_STATUS_NO_DEVICE; }
 
 private:
-    struct Pending { uint32_t stage; int32_t coef[5]; };
-    void design(uint32_t stage, int kind, float f, float q, float slope)
+    static const uint32_t kAll = 0xFFFFFFFFu;                  // Pending::channel of a call on the node itself
+    struct Pending { uint32_t channel, stage; int32_t coef[5]; };
+    void set(uint32_t ch, uint32_t stage, const int *coefficients)
+    {
+        if (stage >= 4) return;                                // filter_biquad.cpp:86
+        pending.push_back({ch, stage, {coefficients[0], coefficients[1], coefficients[2], coefficients[3], coefficients[4]}});
+        if (AudioGPU.context()) ensure();
+    }
+    void set(uint32_t ch, uint32_t stage, const double *coefficients)
+    {
+        int coef[5];
+        for (int i = 0; i < 5; i++) coef[i] = (int)(coefficients[i] * 1073741824.0);
+        set(ch, stage, coef);
+    }
+    void design(uint32_t ch, uint32_t stage, int kind, float f, float q, float slope)
     {
         int32_t coef[5];
-        if (msdr_biquad_design(kind, f, q, slope, AUDIO_SAMPLE_RATE_EXACT, coef) == 0) setCoefficients(stage, (const int *)coef);
+        if (msdr_biquad_design(kind, f, q, slope, AUDIO_SAMPLE_RATE_EXACT, coef) == 0) set(ch, stage, (const int *)coef);
     }
     bool ensure(void)
     {
         if (!node) {
             if (!AudioGPU.context() || msdr_biquad_q15_create(AudioGPU.context(), AudioGPU.channels(), &node) != 0) { node = nullptr; return false; }
         }
-        for (const Pending &p : pending) msdr_biquad_q15_set_coefficients(node, p.stage, p.coef);
+        for (const Pending &p : pending) {
+            if (p.channel == kAll) msdr_biquad_q15_set_coefficients(node, p.stage, p.coef);
+            else msdr_biquad_q15_set_coefficients_channels(node, p.channel, 1, p.stage, p.coef);      // (a channel past the bank: refused there)
+        }
         pending.clear();
         return true;
     }
@@ -265,6 +292,17 @@ public:
         int32_t coef[5];
         if (int rc = msdr_biquad_design(MSDR_BQ_NOTCH, frequency, q, 1.0f, AUDIO_SAMPLE_RATE_EXACT, coef)) return rc;
         return setNodeCoefficients(node, stage, (const int *)coef);
+    }
+    // one receiver's node: tune() of receiver `channel` (msdr_chain_set_node_coefficients_channels)
+    int setNodeCoefficientsChannel(uint32_t node, uint32_t channel, uint32_t stage, const int *coef)
+    {
+        return chain ? msdr_chain_set_node_coefficients_channels(chain, node, channel, 1, stage, (const int32_t *)coef) : MSDR_STATUS_ARGUMENT_ERROR;
+    }
+    int setNodeNotchChannel(uint32_t node, uint32_t channel, uint32_t stage, float frequency, float q = 1.0f)
+    {
+        int32_t coef[5];
+        if (int rc = msdr_biquad_design(MSDR_BQ_NOTCH, frequency, q, 1.0f, AUDIO_SAMPLE_RATE_EXACT, coef)) return rc;
+        return setNodeCoefficientsChannel(node, channel, stage, (const int *)coef);
     }
     int setOsc(const void *osc_i, const void *osc_q) { return chain ? msdr_chain_set_osc(chain, osc_i, osc_q) : MSDR_STATUS_ARGUMENT_ERROR; }
     virtual void update(void)

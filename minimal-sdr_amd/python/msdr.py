@@ -82,6 +82,12 @@ def load_library(path=None):
         _lib.msdr_chain_set_taps.argtypes = [_p, C.c_uint32, _p, _p]
         _lib.msdr_chain_set_osc.argtypes = [_p, _p, _p]
         _lib.msdr_chain_set_node_coefficients.argtypes = [_p, C.c_uint32, C.c_uint32, _p]
+        # (looked up by name: a library built before these two calls existed -- MSDR_LIB pointing at an earlier build for an A/B timing --
+        #  still loads, and a call of theirs on it raises AttributeError)
+        for n, sig in (("msdr_chain_set_node_coefficients_channels", [_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _p]),
+                       ("msdr_biquad_q15_set_coefficients_channels", [_p, C.c_uint32, C.c_uint32, C.c_uint32, _p])):
+            if hasattr(_lib, n):
+                getattr(_lib, n).argtypes = sig
         _lib.msdr_chain_set_biquad_coeffs.argtypes = [_p, _p]
         _lib.msdr_malloc.argtypes = [_p, C.c_size_t, _p]
         _lib.msdr_free.argtypes = [_p, _p]
@@ -431,6 +437,13 @@ class BiquadDf1F32(_Instance):
         return out
 
 
+def _coefs_per_channel(what, coefs):
+    c = np.ascontiguousarray(coefs, np.int32)
+    if c.ndim != 2 or c.shape[1] != 5:
+        raise ValueError("%s: one row of 5 words (b0, b1, b2, a1, a2) per channel, shape %s given" % (what, (c.shape,)))
+    return c
+
+
 class BiquadQ15(_Instance):
     """AudioFilterBiquad: setCoefficients(stage, coef[5]) / update(), batched over channels."""
     _destroy = "msdr_biquad_q15_destroy"
@@ -444,6 +457,11 @@ class BiquadQ15(_Instance):
     def set_coefficients(self, stage, coef):
         c = np.ascontiguousarray(coef, np.int32)
         _ck(self.ctx.lib.msdr_biquad_q15_set_coefficients(self.h, C.c_uint32(stage), _hp(c)))
+
+    def set_coefficients_channels(self, first_channel, stage, coefs):
+        """setCoefficients(stage, coefs[i]) on channel first_channel + i only: coefs int32 [count, 5]."""
+        c = _coefs_per_channel("set_coefficients_channels", coefs)
+        _ck(self.ctx.lib.msdr_biquad_q15_set_coefficients_channels(self.h, C.c_uint32(first_channel), C.c_uint32(c.shape[0]), C.c_uint32(stage), _hp(c)))
 
     def update(self, d_data, n):
         _ck(self.ctx.lib.msdr_biquad_q15_update(self.h, d_data.ptr, n))
@@ -707,6 +725,12 @@ class Chain(_Instance):
         if c.size != 5:
             raise ValueError("set_node_coefficients: one stage = 5 words (b0, b1, b2, a1, a2), %d given" % c.size)
         _ck(self.ctx.lib.msdr_chain_set_node_coefficients(self.h, C.c_uint32(node), C.c_uint32(stage), _hp(c)))
+
+    def set_node_coefficients_channels(self, node, first_channel, stage, coefs):
+        """setCoefficients(stage, coefs[i]) on biquad node `node` of channel first_channel + i only: coefs int32 [count, 5]."""
+        c = _coefs_per_channel("set_node_coefficients_channels", coefs)
+        _ck(self.ctx.lib.msdr_chain_set_node_coefficients_channels(self.h, C.c_uint32(node), C.c_uint32(first_channel), C.c_uint32(c.shape[0]),
+                                                                   C.c_uint32(stage), _hp(c)))
 
     def set_biquad_coeffs(self, coeffs):
         c = np.ascontiguousarray(coeffs, np.float32).reshape(-1)
