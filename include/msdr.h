@@ -161,6 +161,13 @@ int msdr_fir_q15_reset(msdr_fir_q15 *S);
  * (the instance only holds the pointer, arm_fir_init_q15.c:100-109; the bandwidth menu rewrites FIR_AM_coeffs in place with no
  * init_FIR(), UI.cpp:337-345, Minimal-SDR.ino:221-223).  Same numTaps as at creation.  Stream-ordered behind the calls queued so far. */
 int msdr_fir_q15_set_coeffs(msdr_fir_q15 *S, const q15_t *pCoeffs);
+/* The same for channels first_channel .. first_channel + count - 1 only, each with an array of its own: pCoeffs is a HOST array
+ * [count][numTaps] (CMSIS order) -- a bank of arm_fir_instance_q15 whose pCoeffs point at different arrays.  Any int16 value is a legal
+ * tap.  State and history length are kept; count == 0 does nothing; a range past `channels` is MSDR_STATUS_ARGUMENT_ERROR.  From the first
+ * such call on msdr_fir_q15_process runs the kernel whose coefficient operand is per channel (chain_q15pc_kernel, FIR-only flavour);
+ * msdr_fir_q15_set_coeffs keeps writing all channels.  Instances of more than 10 576 taps are refused (MSDR_STATUS_ARGUMENT_ERROR, nothing
+ * changed: the kernel keeps a channel's window in 64 KB of LDS).  Synchronises the stream. */
+int msdr_fir_q15_set_coeffs_channels(msdr_fir_q15 *S, uint32_t first_channel, uint32_t count, const q15_t *pCoeffs);
 int msdr_fir_q15_destroy(msdr_fir_q15 *S);
 
 /* arm_fir_init_f32 / arm_fir_f32 (prototypes arm_math.h:1182-1202; CMSIS-DSP V1.5.x). Any numTaps >= 1. */
@@ -476,6 +483,22 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   on the chain runs its nodes as a kernel of their own behind the demodulator kernel (two launches per 128-sample tick instead of
  *   one); a msdr_chain_graph made before that call is refused afterwards, one made after it replays as usual.  The per-channel
  *   coefficients survive msdr_chain_set_taps / set_mode / set_osc, msdr_chain_reset and msdr_chain_init_fir.
+ * msdr_chain_set_taps_channels (Q15): FIR coefficients that belong to the CHANNEL -- a bank of stations, each with its own filterBandwidth
+ *   (stations.h:10-16; calc_demod_filter() rewriting FIR_AM_coeffs, Minimal-SDR.ino:221-223).  coeffs_i / coeffs_q: HOST arrays
+ *   [count][num_taps] in CMSIS order for channels first_channel .. first_channel + count - 1, read during the call; coeffs_q == NULL means
+ *   the same array behind both filters (init_FIR() for AM / SYNCAM, .ino:917-924).  num_taps is the chain's.  Any int16 value is a legal
+ *   tap (32767 and -32768 included).  Semantics of msdr_chain_set_taps for the named channels only: every state kept, the channel hears
+ *   the new filter from its next sample on over the old filter's history.  count == 0 does nothing; a range past `channels`, a NULL
+ *   coeffs_i and an fp32 chain are MSDR_STATUS_ARGUMENT_ERROR.  From the first such call on, for the rest of its life, the chain runs
+ *   chain_q15pc_kernel (coefficient operand per channel; msdr_chain_get_info().kernel names it) in place of the uniform demodulator
+ *   kernels, with the PLL / LMS / biquad-node kernels behind it as before; a chain that never receives the call runs what it always ran.
+ *   Interplay: msdr_chain_set_mode(chain, ch, mode, tapset) puts channel ch back on shared tap set `tapset` (its own taps are dropped);
+ *   msdr_chain_set_taps(chain, tapset, ...) changes the channels still on that tap set and leaves channels with taps of their own alone;
+ *   the per-channel taps survive msdr_chain_init_fir, msdr_chain_reset, msdr_chain_set_osc, msdr_chain_set_anr and both node-coefficient
+ *   setters.  A msdr_chain_graph made before the first such call is refused afterwards; one made after it REPLAYS bit-exactly (block
+ *   lengths 32 .. 512, no PLL / LMS channels, no pending oscillator change) and stays valid across later msdr_chain_set_taps_channels
+ *   calls, which rewrite the table the captured launches read; like every graph it is refused after a live update that rebuilds the chain's
+ *   tables (msdr_chain_set_taps, msdr_chain_set_osc, ...) and after msdr_chain_reset.
  * msdr_chain_set_biquad_coeffs (F32): all 5 * num_biquad_stages coefficients of the arm_biquad_cascade_df1_f32 stage, CMSIS
  *   semantics (the filter carries on from the pState arm_biquad_cascade_df1_f32 would hold; see msdr_biquad_df1_f32_set_coeffs).
  *   The number of stages is fixed at creation, as numStages is in CMSIS.
@@ -485,6 +508,8 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   table of their own time, as in the reference (the mixer runs in front of the FIR's state buffer): the library keeps up to 16 earlier
  *   tables for as long as the history holds samples of theirs (a 17th change inside ONE history length drops the oldest). */
 int msdr_chain_set_taps(msdr_chain *chain, uint32_t tapset, const void *coeffs_i, const void *coeffs_q);
+int msdr_chain_set_taps_channels(msdr_chain *chain, uint32_t first_channel, uint32_t count,
+                                 const q15_t *coeffs_i, const q15_t *coeffs_q);
 int msdr_chain_set_node_coefficients(msdr_chain *chain, uint32_t node, uint32_t stage, const int32_t coef[5]);
 int msdr_chain_set_node_coefficients_channels(msdr_chain *chain, uint32_t node, uint32_t first_channel,
                                               uint32_t count, uint32_t stage, const int32_t *coef);

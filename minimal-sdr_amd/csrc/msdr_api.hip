@@ -18,6 +18,7 @@
 #include "msdr_chain_amtr.hiph"
 #include "msdr_chain_mfb.hiph"
 #include "msdr_chain_q15mb.hiph"
+#include "msdr_chain_q15pc.hiph"
 #include "msdr_block.h"
 #include "msdr_design.h"
 #include "msdr_cascade_state.h"
@@ -801,6 +802,10 @@ struct msdr_fir_q15 : FirInst<int16_t, int32_t> {
     int *d_btiles = nullptr;
     size_t btiles_cap = 0;
     uint32_t bt_n = 0, bt_wgs = 0, bt_nw = 0, bt_tpw = 0;
+    // per-channel coefficients (msdr_fir_q15_set_coeffs_channels): from the first such call on chain_q15pc_kernel<., true> runs, over the same history
+    bool per_channel = false;
+    int pc_np = 0;
+    int16_t *d_pc_taps = nullptr;         // [channels][pc_np], complete for every channel
 };
 struct msdr_fir_f32 : FirInst<float, float> {
     // matrix-core path (msdr_fir_f32mf.hiph): header + split-fp16 Toeplitz fragments, or null (then fir_kernel<FirF32> runs)
@@ -974,8 +979,28 @@ static int fir_q15_block_tiles(msdr_fir_q15 *S, int n)
     S->bt_n = (uint32_t)n; S->bt_wgs = wgs; S->bt_nw = nw; S->bt_tpw = tpw;
     return 0;
 }
+static int fir_q15_process_pc(msdr_fir_q15 *S, const q15_t *d_src, q15_t *d_dst, uint32_t blockSize)
+{
+    if (int rc = bind(S->ctx)) return rc;
+    if (blockSize == 0) return 0;
+    if (!d_src || !d_dst) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null buffer");
+    if ((const void *)d_src == (const void *)d_dst)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "FIR process is not in-place (the reference uses separate buffers, Minimal-SDR.ino:574-578)");
+    PcParams q;
+    memset(&q, 0, sizeof q);
+    q.x = d_src; q.out = d_dst; q.hist_in = S->d_hist[S->cur]; q.n = (long long)blockSize; q.channels = (int)S->channels;
+    q.hist_len = (int)S->hist_len; q.np = S->pc_np; q.taps = S->d_pc_taps;
+    { KernelTimer kt(S->ctx); if (launch_chain_q15pc(S->ctx->stream, true, S->ctx->num_cus, q, nullptr) != hipSuccess) return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pc_kernel launch failed"); }
+    if (int rc = launch_check("chain_q15pc_kernel")) return rc;
+    hipLaunchKernelGGL((history_kernel<int16_t>), dim3(grid_1d((long long)S->channels * S->hist_len)), dim3(256), 0, S->ctx->stream,
+                       d_src, (const int16_t *)S->d_hist[S->cur], S->d_hist[S->cur ^ 1], (long long)blockSize, (int)S->hist_len, (int)S->channels);
+    if (int rc = launch_check("history_kernel")) return rc;
+    S->cur ^= 1;
+    return 0;
+}
 extern "C" int msdr_fir_q15_process(msdr_fir_q15 *S, const q15_t *d_src, q15_t *d_dst, uint32_t blockSize)
 {
+    if (S && S->per_channel) return fir_q15_process_pc(S, d_src, d_dst, blockSize);
     if (!S || !S->d_qm_tab) return fir_process<FirQ15>(S, d_src, d_dst, blockSize);
     if (int rc = bind(S->ctx)) return rc;
     if (blockSize == 0) return 0;
@@ -1025,7 +1050,7 @@ extern "C" int msdr_fir_q15_process(msdr_fir_q15 *S, const q15_t *d_src, q15_t *
 extern "C" int msdr_fir_q15_reset(msdr_fir_q15 *S) { return fir_reset(S); }
 extern "C" int msdr_fir_q15_destroy(msdr_fir_q15 *S)
 {
-    if (S) { hipFree(S->d_qm_tab); hipFree(S->d_qm_order); hipFree(S->d_btiles); }
+    if (S) { hipFree(S->d_qm_tab); hipFree(S->d_qm_order); hipFree(S->d_btiles); hipFree(S->d_pc_taps); }
     return fir_destroy(S);
 }
 // New coefficients under a running filter (the reference: the array behind S->pCoeffs rewritten in place, UI.cpp:337-345 +
@@ -1045,10 +1070,47 @@ static int fir_swap_coeffs(Inst *S, Create &&create)
 extern "C" int msdr_fir_q15_set_coeffs(msdr_fir_q15 *S, const q15_t *pCoeffs)
 {
     if (!S || !pCoeffs) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
+    if (S->per_channel) {
+        // the instance runs chain_q15pc_kernel for life and its uniform tables are never read again: set_coeffs keeps writing ALL channels, i.e.
+        // every row of the per-channel table; history pair and history length stay as they are (no second instance, whatever the taps' values)
+        if (int rc = bind(S->ctx)) return rc;
+        std::vector<int16_t> t((size_t)S->channels * S->pc_np, 0);
+        for (uint32_t ch = 0; ch < S->channels; ch++) memcpy(t.data() + (size_t)ch * S->pc_np + (S->pc_np - S->ntaps), pCoeffs, S->ntaps * sizeof(int16_t));
+        HIP_TRY(hipStreamSynchronize(S->ctx->stream));
+        HIP_TRY(hipMemcpy(S->d_pc_taps, t.data(), t.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+        return 0;
+    }
     msdr_fir_q15 *old = nullptr;
     auto create = [&](msdr_fir_q15 **n) { const int rc = msdr_fir_q15_create(S->ctx, (uint16_t)S->ntaps, pCoeffs, S->channels, n); old = *n; return rc; };
     if (int rc = fir_swap_coeffs(S, create)) { if (old) msdr_fir_q15_destroy(old); return rc; }
     return msdr_fir_q15_destroy(old);
+}
+// arm_fir_fast_q15 over a bank whose instances each point at a coefficient array of their own (arm_fir_init_q15.c:100-109 keeps the pointer)
+extern "C" int msdr_fir_q15_set_coeffs_channels(msdr_fir_q15 *S, uint32_t first_channel, uint32_t count, const q15_t *pCoeffs)
+{
+    if (!S) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null instance");
+    if (int rc = bind(S->ctx)) return rc;
+    if (count == 0) return 0;
+    if (!pCoeffs) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null coefficient array");
+    if (first_channel >= S->channels || count > S->channels - first_channel)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "channels %u .. %llu of %u", first_channel, (unsigned long long)first_channel + count - 1, S->channels);
+    if (pc_lds_bytes(pc_np((int)S->ntaps), 1, true, 1) > 64 * 1024)          // (one wave's two window copies and its tap row must fit the kernel's LDS)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "per-channel coefficients: the kernel holds filters of up to 10 576 taps (this instance has %u); nothing changed", S->ntaps);
+    HIP_TRY(hipStreamSynchronize(S->ctx->stream));
+    if (!S->per_channel) {          // every channel starts from the shared coefficients (d_taps: int32, front-padded to ntaps_pad)
+        const int np = pc_np((int)S->ntaps);
+        std::vector<int32_t> shared(S->ntaps_pad);
+        HIP_TRY(hipMemcpy(shared.data(), S->d_taps, shared.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        std::vector<int16_t> t((size_t)S->channels * np, 0);
+        for (uint32_t ch = 0; ch < S->channels; ch++)
+            for (uint32_t k = 0; k < S->ntaps; k++) t[(size_t)ch * np + (np - S->ntaps) + k] = (int16_t)shared[S->ntaps_pad - S->ntaps + k];
+        if (int rc = upload(S->ctx, t, &S->d_pc_taps)) return rc;
+        S->pc_np = np; S->per_channel = true;
+    }
+    std::vector<int16_t> rows((size_t)count * S->pc_np, 0);
+    for (uint32_t i = 0; i < count; i++) memcpy(rows.data() + (size_t)i * S->pc_np + (S->pc_np - S->ntaps), pCoeffs + (size_t)i * S->ntaps, S->ntaps * sizeof(int16_t));
+    HIP_TRY(hipMemcpy(S->d_pc_taps + (size_t)first_channel * S->pc_np, rows.data(), rows.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+    return 0;
 }
 
 extern "C" int msdr_fir_f32_destroy(msdr_fir_f32 *S);
@@ -2224,6 +2286,17 @@ struct msdr_chain {
     std::vector<int> h_post_ch;
     float *d_post_pll_state, *d_post_anr_state;      // [channels][4], [channels][kAnrStateFloats]: indexed by CHANNEL, they survive a retune
     int16_t *d_aux_x; float *d_aux_y, *d_post_scratch; size_t post_cap_virt, post_cap_post;      // capacities in elements
+    // per-channel FIR coefficients (msdr_chain_set_taps_channels; Q15): from the first such call on, for the chain's life, the demodulator kernel
+    // is chain_q15pc_kernel (msdr_chain_q15pc.hiph), whose coefficient operand is this table -- complete for EVERY channel: a channel that is
+    // still on a shared tap set holds a copy of that set's rows (refreshed by msdr_chain_set_taps / msdr_chain_set_mode)
+    // bumped by every rebuild of the device tables (chain_rebuild) and by msdr_chain_reset: part of a HIP graph's key.  The per-channel kernel's
+    // launches hold pointers (mode array, oscillator table) that the other key fields do not cover on a chain without matrix-core tables.
+    uint64_t rebuild_gen = 0;
+    bool pc_active = false;
+    int pc_np = 0;                        // taps per row: num_taps front-padded with zeros to a multiple of 8
+    int16_t *d_pc_taps = nullptr;         // [channels][2][pc_np]: I row, Q row
+    std::vector<int16_t> h_pc_taps;       // the host's copy
+    std::vector<char> h_pc_own;           // per channel: 1 = taps of its own, 0 = a copy of its tap set's
     msdr_chain_info info;
     // optional per-launch timing of the main kernel
     bool timing;
@@ -2238,6 +2311,29 @@ struct msdr_chain {
 static bool chain_nodes_per_channel(const msdr_chain *c)
 {
     return (c->nodes[0] && c->nodes[0]->per_channel) || (c->nodes[1] && c->nodes[1]->per_channel);
+}
+
+// ---- per-channel FIR coefficients: the host's copy of the table and its way to the device ----
+static void chain_pc_row_from(msdr_chain *c, uint32_t ch, const int16_t *ci, const int16_t *cq)
+{
+    int16_t *row = c->h_pc_taps.data() + (size_t)ch * 2 * c->pc_np;
+    const int off = c->pc_np - (int)c->ntaps;                   // zero taps in FRONT: they meet older samples
+    memset(row, 0, (size_t)2 * c->pc_np * sizeof(int16_t));
+    memcpy(row + off, ci, c->ntaps * sizeof(int16_t));
+    memcpy(row + c->pc_np + off, cq, c->ntaps * sizeof(int16_t));
+}
+static void chain_pc_row_shared(msdr_chain *c, uint32_t ch)       // the rows of the tap set the channel is on (the stored configuration)
+{
+    const int ts = c->h_tapset[ch];
+    chain_pc_row_from(c, ch, (const int16_t *)c->store.ci[ts].data(), (const int16_t *)c->store.cq[ts].data());
+}
+// rows first .. first + count - 1 to the device; the stream is drained first (a kernel in flight reads the table)
+static int chain_pc_upload(msdr_chain *c, uint32_t first, uint32_t count)
+{
+    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+    const size_t row = (size_t)2 * c->pc_np;
+    HIP_TRY(hipMemcpy(c->d_pc_taps + first * row, c->h_pc_taps.data() + first * row, count * row * sizeof(int16_t), hipMemcpyHostToDevice));
+    return 0;
 }
 
 static void chain_post_free(msdr_chain *c)
@@ -2268,7 +2364,7 @@ static void chain_free(msdr_chain *c)
     hipFree(c->d_anr_on);
     for (auto &e : c->events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (auto &o : c->osc_pending) hipFree(o.d_tab);
-    hipFree(c->d_f32_scratch); hipFree(c->d_osc_hist); hipFree(c->d_btiles);
+    hipFree(c->d_f32_scratch); hipFree(c->d_osc_hist); hipFree(c->d_btiles); hipFree(c->d_pc_taps);
     delete c;
 }
 
@@ -3329,7 +3425,8 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     if (c->force_generic) use_fold = false;
     const bool use_mf = f32 && c->mf_ok && !c->force_generic;
     const bool use_mfw = use_mf && c->mfw_nw > 0;
-    bool use_qm = !f32 && c->d_qm_tab != nullptr && !c->force_generic;
+    const bool use_pc = !f32 && c->pc_active;                    // per-channel taps: chain_q15pc_kernel in place of every uniform demodulator kernel
+    bool use_qm = !f32 && c->d_qm_tab != nullptr && !c->force_generic && !use_pc;
     p.osc_hist = nullptr;
     if (!c->osc_pending.empty()) {
         OscHistory oh;
@@ -3504,6 +3601,11 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     if (c->dry_run) {
         // msdr_chain_graph_create's preparation pass: everything a block-cadence call needs from the host is in place now; say whether the
         // launches that follow are fixed (capturable into a HIP graph) -- and make none
+        if (use_pc) {            // chain_q15pc_kernel + the kernels behind it + the history kernel: a fixed set of launches at a block-cadence length
+            if (!mb_n_ok((long long)n_samples)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "not a block-cadence call (32 .. 512 samples, a divisor of 1024): nothing to capture");
+            if (pll_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the PLL demodulator runs behind the kernel: not capturable");
+            if (p.osc_hist) return fail(MSDR_STATUS_ARGUMENT_ERROR, "a pending oscillator change (the history still holds samples of an earlier table): not capturable");
+        } else
         if (!use_mfb && !use_qb) return fail(MSDR_STATUS_ARGUMENT_ERROR, "not a block-cadence call (32 .. 512 samples, a divisor of 1024, 16-byte aligned buffers, matrix-core tables, no pending oscillator change): nothing to capture");
         if (c->seq_bq) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the cascade runs in CMSIS order behind the kernel (a kernel of its own with host-side sizing): not capturable");
         if (i16_via_scratch) return fail(MSDR_STATUS_ARGUMENT_ERROR, "int16 audio through the scratch batch: not capturable");
@@ -3522,6 +3624,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     bool nodes_fused = false;            // Q15 block cadence: the biquad nodes ran inside chain_q15mb_kernel
     unsigned block = kThreads;
     size_t lds_used = lds;
+    int pc_tile = 0;
     if (use_mfb) {
         static const char *const names[3] = {"chain_mfb_kernel<0> (channel-batched block tiles)", "chain_mfb_kernel<1> (channel-batched block tiles)",
                                              "chain_mfb_kernel<2> (channel-batched block tiles)"};
@@ -3659,6 +3762,17 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         }
         kname = c->qm_fr ? "chain_q15mf_kernel full-rate NCO streams" : "chain_q15mf_kernel"; block = (unsigned)nw * 64; nseg = qseg;
     }
+    else if (use_pc) {
+        PcParams q;
+        memset(&q, 0, sizeof q);
+        q.x = d_if; q.out = (short *)d_audio; q.hist_in = c->d_hist[c->cur]; q.n = (long long)n_samples; q.channels = (int)c->channels;
+        q.hist_len = (int)c->hist_len; q.np = c->pc_np; q.taps = c->d_pc_taps; q.chan_mode = c->d_mode; q.mixer = c->mixer; q.osc = c->d_osc;
+        q.osc_len = (int)c->osc_len; q.phase0 = (int)c->phase; q.sqrt_kind = c->sqrt_kind; q.syncam_q = p.syncam_q; q.osc_hist = p.osc_hist;
+        PcLaunch geo;
+        if (launch_chain_q15pc(c->ctx->stream, false, c->ctx->num_cus, q, &geo) != hipSuccess)
+            return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pc_kernel launch failed");
+        kname = "chain_q15pc_kernel (per-channel taps)"; grid = geo.grid; block = geo.block; lds_used = geo.lds_bytes; nseg = geo.nseg; pc_tile = geo.tile;
+    }
     else     (void)launch_chain_generic(c->ctx->stream, true, grid, lds, p);
     if (int rc = launch_check("chain_kernel")) return rc;
     if (e0) { HIP_TRY(hipEventRecord(e1, c->ctx->stream)); c->events.emplace_back(e0, e1); }
@@ -3738,8 +3852,8 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
 
     snprintf(c->info.kernel, sizeof c->info.kernel, "%s%s", kname, !c->seq_bq ? "" : c->seq_bq->sequential ? " + biquad_df1_seq_kernel" : " + biquad_df1_kernel");
     c->info.grid = grid; c->info.block = block; c->info.lds_bytes = (uint32_t)lds_used;
-    c->info.time_segments = (uint32_t)nseg; c->info.warmup = (uint32_t)p.warm; c->info.tile = (uint32_t)kTile;
-    c->info.taps_padded = c->ntaps_pad;
+    c->info.time_segments = (uint32_t)nseg; c->info.warmup = (uint32_t)p.warm; c->info.tile = (uint32_t)(use_pc ? pc_tile : kTile);
+    c->info.taps_padded = use_pc ? (uint32_t)c->pc_np : c->ntaps_pad;
     c->info.mfma_ksteps = use_mf ? (uint32_t)c->mf_bsteps : use_qm ? (uint32_t)c->qm_bsteps : 0u;
     return 0;
 }
@@ -3760,12 +3874,16 @@ struct msdr_chain_graph {
     const void *k_hist, *k_state, *k_tab, *k_tiles;
     int k_cur;
     uint64_t k_mode_gen;
+    uint64_t k_rebuild_gen; // the chain's tables as they were (a rebuild frees what the captured launches point at; a reset moves the mixer's position)
+    const void *k_mode, *k_osc;
+    bool k_taps_pc;        // the chain ran chain_q15pc_kernel (per-channel taps) when the launches were captured
     bool k_nodes_pc;       // the biquad nodes ran per channel (a kernel of its own behind the demodulator kernel) when the launches were captured
 };
 static void chain_graph_key(const msdr_chain *c, msdr_chain_graph *g)
 {
     g->k_hist = c->d_hist[c->cur]; g->k_state = c->d_bq_state; g->k_tab = c->arith == MSDR_ARITH_F32 ? (const void *)c->d_mf_tab : (const void *)c->d_qm_tab;
-    g->k_tiles = c->d_btiles; g->k_cur = c->cur; g->k_mode_gen = c->mode_gen; g->k_nodes_pc = chain_nodes_per_channel(c);
+    g->k_tiles = c->d_btiles; g->k_cur = c->cur; g->k_mode_gen = c->mode_gen; g->k_nodes_pc = chain_nodes_per_channel(c); g->k_taps_pc = c->pc_active;
+    g->k_rebuild_gen = c->rebuild_gen; g->k_mode = c->d_mode; g->k_osc = c->d_osc;
 }
 
 extern "C" int msdr_chain_graph_create(msdr_chain *c, uint32_t ticks, const int16_t *const *d_if, void *const *d_audio, uint64_t n_samples, msdr_chain_graph **out)
@@ -3819,10 +3937,13 @@ extern "C" int msdr_chain_graph_launch(msdr_chain_graph *g)
     if (int rc = bind(c->ctx)) return rc;
     msdr_chain_graph now;
     chain_graph_key(c, &now);
-    if (now.k_hist != g->k_hist || now.k_state != g->k_state || now.k_tab != g->k_tab || now.k_tiles != g->k_tiles || now.k_cur != g->k_cur || now.k_mode_gen != g->k_mode_gen)
+    if (now.k_hist != g->k_hist || now.k_state != g->k_state || now.k_tab != g->k_tab || now.k_tiles != g->k_tiles || now.k_cur != g->k_cur || now.k_mode_gen != g->k_mode_gen ||
+        now.k_rebuild_gen != g->k_rebuild_gen || now.k_mode != g->k_mode || now.k_osc != g->k_osc)
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "the chain has changed since this graph was made (a live update, a reset, or an odd number of direct calls in between): make the graph again");
     if (now.k_nodes_pc != g->k_nodes_pc)
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "a biquad node got per-channel coefficients since this graph was made (its captured launches keep a node's coefficients uniform): make the graph again");
+    if (now.k_taps_pc != g->k_taps_pc)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "channels got FIR coefficients of their own since this graph was made (its captured launches share tap sets between channels): make the graph again");
     HIP_TRY(hipGraphLaunch(g->exec, c->ctx->stream));
     c->gen += g->ticks;                                     // (an even number of calls: buffers, table position and caches stay as they are)
     return 0;
@@ -3864,7 +3985,7 @@ extern "C" int msdr_chain_reset(msdr_chain *c)
         for (auto &o : c->osc_pending) hipFree(o.d_tab);
         c->osc_pending.clear(); c->force_generic = false;
     }
-    c->phase = 0; c->gen++;
+    c->phase = 0; c->gen++; c->rebuild_gen++;
     return 0;
 }
 
@@ -3982,6 +4103,11 @@ extern "C" int msdr_chain_set_mode(msdr_chain *c, uint32_t channel, int32_t mode
     HIP_TRY(hipMemcpyAsync(c->d_mode + channel, &mode, sizeof(int), hipMemcpyHostToDevice, c->ctx->stream));
     HIP_TRY(hipMemcpyAsync(c->d_tapset + channel, &tapset, sizeof(int), hipMemcpyHostToDevice, c->ctx->stream));
     HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+    if (c->pc_active) {          // back on a shared tap set: the channel's own taps are dropped, its rows become a copy of that set's
+        c->h_pc_own[channel] = 0;
+        chain_pc_row_shared(c, channel);
+        if (int rc = chain_pc_upload(c, channel, 1)) return rc;
+    }
     return 0;
 }
 
@@ -4049,9 +4175,16 @@ static int chain_rebuild(msdr_chain *c, const ChainCfgStore &edited, void **stea
     n->timing = c->timing; n->events.swap(c->events); n->timed_ms = c->timed_ms; n->timed_launches = c->timed_launches;
     n->info = c->info;
     n->osc_pending.swap(c->osc_pending); n->force_generic = c->force_generic;
+    // per-channel taps survive every rebuild; the channels still on a shared tap set follow that set's (possibly new) coefficients
+    n->rebuild_gen = c->rebuild_gen + 1;
+    n->pc_active = c->pc_active; n->pc_np = c->pc_np; std::swap(n->d_pc_taps, c->d_pc_taps); n->h_pc_taps.swap(c->h_pc_taps); n->h_pc_own.swap(c->h_pc_own);
     std::swap(*c, *n);
     if (steal_osc) { *steal_osc = n->d_osc; n->d_osc = nullptr; }
     chain_free(n);
+    if (c->pc_active) {
+        for (uint32_t ch = 0; ch < c->channels; ch++) if (!c->h_pc_own[ch]) chain_pc_row_shared(c, ch);
+        if (int rc2 = chain_pc_upload(c, 0, c->channels)) return rc2;
+    }
     return 0;
 }
 
@@ -4146,6 +4279,35 @@ extern "C" int msdr_chain_set_taps(msdr_chain *c, uint32_t tapset, const void *c
     ed.ci[tapset].assign((const char *)coeffs_i, (const char *)coeffs_i + bytes);
     ed.cq[tapset].assign((const char *)coeffs_q, (const char *)coeffs_q + bytes);
     return chain_rebuild_keep_folded(c, ed, [&](uint32_t ch) { return (uint32_t)c->h_tapset[ch] == tapset; });
+}
+
+// calc_demod_filter() of ONE receiver of the bank (Minimal-SDR.ino:221-223): rows of the per-channel table rewritten under the running stream
+extern "C" int msdr_chain_set_taps_channels(msdr_chain *c, uint32_t first_channel, uint32_t count, const q15_t *coeffs_i, const q15_t *coeffs_q)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (int rc = bind(c->ctx)) return rc;
+    if (c->arith != MSDR_ARITH_Q15)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "per-channel FIR coefficients belong to Q15 chains (the fp32 chain shares its tap sets: msdr_chain_set_taps)");
+    if (count == 0) return 0;
+    if (!coeffs_i) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null coefficient array");
+    if (first_channel >= c->channels || count > c->channels - first_channel)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "channels %u .. %llu of %u", first_channel, (unsigned long long)first_channel + count - 1, c->channels);
+    if (!coeffs_q) coeffs_q = coeffs_i;                          // init_FIR() for AM / SYNCAM: one array behind both instances (.ino:917-924)
+    const bool first_call = !c->pc_active;
+    if (first_call) {
+        c->pc_np = pc_np((int)c->ntaps);
+        HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+        if (int rc = dzalloc(c->ctx, (size_t)c->channels * 2 * c->pc_np, &c->d_pc_taps)) return rc;
+        c->h_pc_taps.assign((size_t)c->channels * 2 * c->pc_np, 0);
+        c->h_pc_own.assign(c->channels, 0);
+        for (uint32_t ch = 0; ch < c->channels; ch++) chain_pc_row_shared(c, ch);
+        c->pc_active = true;
+    }
+    for (uint32_t i = 0; i < count; i++) {
+        chain_pc_row_from(c, first_channel + i, coeffs_i + (size_t)i * c->ntaps, coeffs_q + (size_t)i * c->ntaps);
+        c->h_pc_own[first_channel + i] = 1;
+    }
+    return first_call ? chain_pc_upload(c, 0, c->channels) : chain_pc_upload(c, first_channel, count);
 }
 
 extern "C" int msdr_chain_set_osc(msdr_chain *c, const void *osc_i, const void *osc_q)

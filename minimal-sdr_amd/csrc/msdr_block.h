@@ -5,6 +5,7 @@
 //   msdr_fir_stage.hip     the arm_fir_f32 stage: fir_f32tq_kernel, fir_f32mf_kernel
 //   msdr_q15_elementwise.hip  arm_mult_q15 / arm_add_q15 / arm_sub_q15 / arm_copy_q15 over a block batch: q15_elementwise_kernel
 //   msdr_biquad_pc.hip     AudioFilterBiquad with per-channel coefficients: biquad_teensy_pc_kernel
+//   msdr_chain_q15pc.hip   the Q15 chain / the arm_fir_fast_q15 stage with per-channel FIR coefficients: chain_q15pc_kernel
 // Host-side geometry helpers (LDS sizes, table formats) live with the kernels' headers.  Every launcher returns the HIP error of its launch.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -37,4 +38,10 @@ hipError_t launch_q15_elementwise(hipStream_t stream, int op, int max_grid, cons
 // biquad_teensy_pc_kernel<nodes> (msdr_biquad_pc.hiph): nodes = 1 or 2 AudioFilterBiquad nodes in series, in place on data [channels][n] (n even),
 // every channel with the coefficients and stage count of its own record in defs0 / defs1 ([channels][32]; defs1 unused for one node)
 hipError_t launch_biquad_teensy_pc(hipStream_t stream, int nodes, short *data, int *defs0, int *defs1, int channels, long long n);
+// ---- msdr_chain_q15pc.hip ----
+// chain_q15pc_kernel<CPW, FIR_ONLY> (msdr_chain_q15pc.hiph).  The launcher chooses the channels per wave (4 up to 128 samples per call, 2 up to
+// 256, else 1), the waves per workgroup (4, fewer for very long filters: 64 KB of LDS) and the time segmentation from p.n, p.np, p.channels and
+// the number of compute units, fills p.nseg / p.seg_len / p.nw itself and reports the geometry.
+struct PcLaunch { unsigned grid, block; size_t lds_bytes; int cpw, nseg, tile; };
+hipError_t launch_chain_q15pc(hipStream_t stream, bool fir_only, int num_cus, PcParams p, PcLaunch *geo);
 }  // namespace msdr

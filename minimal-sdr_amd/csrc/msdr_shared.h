@@ -110,4 +110,27 @@ struct ChainParams {
     const struct OscHistory *osc_hist;
 };
 
+// chain_q15pc_kernel (msdr_chain_q15pc.hiph): the Q15 chain / the arm_fir_fast_q15 stage with per-channel coefficients
+struct PcParams {
+    const int16_t *x;          // [channels][n] IF samples (FIR stage: input)
+    short *out;                // [channels][n] audio (FIR stage: output)
+    const int16_t *hist_in;    // [channels][hist_len] raw history, oldest first
+    long long n;
+    int channels;
+    int hist_len;
+    int np;                    // taps per row of the table: numTaps front-padded with zeros to a multiple of 8
+    const int16_t *taps;       // [channels][2][np] (I row, Q row; CMSIS order) -- FIR stage: [channels][np]
+    const int *chan_mode;      // [channels] (unused by the FIR stage)
+    int mixer;                 // MSDR_MIXER_*
+    const void *osc;           // [osc_len] int2 pairs {osc_q ("cos"), osc_i ("sin")}
+    int osc_len;
+    int phase0;                // (absolute index of sample 0 of this call) mod osc_len (mod 4 for FS4)
+    int sqrt_kind;
+    short *syncam_q;           // MSDR_CHAIN_SYNCAM_PLL: [channels][n] post-FIR Q of SYNCAM channels (their I goes to `out`); else null
+    const struct OscHistory *osc_hist;     // oscillator tables in force before a live change, or null
+    int nseg;                  // time segments per channel group
+    long long seg_len;         // a multiple of the tile (8 * 64 / channels per wave)
+    int nw;                    // waves per workgroup
+};
+
 }  // namespace msdr

@@ -273,12 +273,13 @@ private:
 // ------------------------------------------------------------------------------------------------
 class AudioSDRDemodulator : public AudioStream {
 public:
-    AudioSDRDemodulator(void) : AudioStream(1, inputQueueArray), chain(nullptr) {}
+    AudioSDRDemodulator(void) : AudioStream(1, inputQueueArray), chain(nullptr), num_taps(0) {}
     ~AudioSDRDemodulator() { if (chain) msdr_chain_destroy(chain); }
     int begin(const msdr_chain_config &cfg)
     {
         if (chain) { msdr_chain_destroy(chain); chain = nullptr; }
         if (cfg.arith != MSDR_ARITH_Q15 || cfg.channels != AudioGPU.channels()) return MSDR_STATUS_ARGUMENT_ERROR;
+        num_taps = cfg.num_taps;
         return msdr_chain_create(AudioGPU.context(), &cfg, &chain);
     }
     int init_FIR(void) { return chain ? msdr_chain_init_fir(chain) : MSDR_STATUS_ARGUMENT_ERROR; }     // Minimal-SDR.ino:901-930
@@ -304,6 +305,22 @@ public:
         if (int rc = msdr_biquad_design(MSDR_BQ_NOTCH, frequency, q, 1.0f, AUDIO_SAMPLE_RATE_EXACT, coef)) return rc;
         return setNodeCoefficientsChannel(node, channel, stage, (const int *)coef);
     }
+    // one receiver's FIR pair: the station's own filterBandwidth (stations.h:10-16; msdr_chain_set_taps_channels).  coeffs_q == nullptr: the
+    // same array behind both filters, as init_FIR() binds FIR_AM_coeffs for AM / SYNCAM (Minimal-SDR.ino:917-924)
+    int setTapsChannel(uint32_t channel, const int16_t *coeffs_i, const int16_t *coeffs_q = nullptr)
+    {
+        return chain ? msdr_chain_set_taps_channels(chain, channel, 1, coeffs_i, coeffs_q) : MSDR_STATUS_ARGUMENT_ERROR;
+    }
+    // calc_demod_filter() of receiver `channel` (Minimal-SDR.ino:221-223): calc_FIR_coeffs(FIR_AM_coeffs, numTaps, filter_bandwidth, 70, 0, 0.0, 24000)
+    int setBandwidthChannel(uint32_t channel, float bandwidth_hz)
+    {
+        if (!chain || !num_taps) return MSDR_STATUS_ARGUMENT_ERROR;
+        std::vector<int16_t> buf(2 * (size_t)num_taps + 8, 0);      // (room for the designer's other filter types)
+        msdr_calc_FIR_coeffs(buf.data(), (int)num_taps, bandwidth_hz, 70, 0, 0.0, 24000);
+        return setTapsChannel(channel, buf.data(), nullptr);
+    }
+    // ANR_on per receiver (host array of channels() values; nullptr: anr_on_all for every receiver), Minimal-SDR.ino:702-770
+    int setAnr(const int32_t *anr_on, int32_t anr_on_all = 0) { return chain ? msdr_chain_set_anr(chain, anr_on, anr_on_all) : MSDR_STATUS_ARGUMENT_ERROR; }
     int setOsc(const void *osc_i, const void *osc_q) { return chain ? msdr_chain_set_osc(chain, osc_i, osc_q) : MSDR_STATUS_ARGUMENT_ERROR; }
     virtual void update(void)
     {
@@ -321,4 +338,5 @@ public:
 private:
     audio_block_t *inputQueueArray[1];
     msdr_chain *chain;
+    uint32_t num_taps;
 };

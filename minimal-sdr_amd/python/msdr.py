@@ -85,7 +85,9 @@ def load_library(path=None):
         # (looked up by name: a library built before these two calls existed -- MSDR_LIB pointing at an earlier build for an A/B timing --
         #  still loads, and a call of theirs on it raises AttributeError)
         for n, sig in (("msdr_chain_set_node_coefficients_channels", [_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _p]),
-                       ("msdr_biquad_q15_set_coefficients_channels", [_p, C.c_uint32, C.c_uint32, C.c_uint32, _p])):
+                       ("msdr_biquad_q15_set_coefficients_channels", [_p, C.c_uint32, C.c_uint32, C.c_uint32, _p]),
+                       ("msdr_chain_set_taps_channels", [_p, C.c_uint32, C.c_uint32, _p, _p]),
+                       ("msdr_fir_q15_set_coeffs_channels", [_p, C.c_uint32, C.c_uint32, _p])):
             if hasattr(_lib, n):
                 getattr(_lib, n).argtypes = sig
         _lib.msdr_chain_set_biquad_coeffs.argtypes = [_p, _p]
@@ -370,6 +372,11 @@ class FirQ15(_Instance):
             raise ValueError("set_coeffs: %d taps given, the instance has %d" % (c.size, self.ntaps))
         _ck(self.ctx.lib.msdr_fir_q15_set_coeffs(self.h, _hp(c)))
 
+    def set_coeffs_channels(self, first_channel, coeffs):
+        """pCoeffs of channel first_channel + i only := coeffs[i]: coeffs int16 [count, numTaps], CMSIS order; state kept."""
+        c = _taps_per_channel("set_coeffs_channels", coeffs, self.ntaps)
+        _ck(self.ctx.lib.msdr_fir_q15_set_coeffs_channels(self.h, C.c_uint32(first_channel), C.c_uint32(c.shape[0]), _hp(c)))
+
 
 class FirF32(_Instance):
     """arm_fir_init_f32 / arm_fir_f32, batched over channels."""
@@ -441,6 +448,13 @@ def _coefs_per_channel(what, coefs):
     c = np.ascontiguousarray(coefs, np.int32)
     if c.ndim != 2 or c.shape[1] != 5:
         raise ValueError("%s: one row of 5 words (b0, b1, b2, a1, a2) per channel, shape %s given" % (what, (c.shape,)))
+    return c
+
+
+def _taps_per_channel(what, coeffs, ntaps):
+    c = np.ascontiguousarray(coeffs, np.int16)
+    if c.ndim != 2 or c.shape[1] != ntaps:
+        raise ValueError("%s: one row of %d taps per channel (numTaps is fixed at creation, as in CMSIS), shape %s given" % (what, ntaps, (c.shape,)))
     return c
 
 
@@ -712,6 +726,15 @@ class Chain(_Instance):
         if ci.size != self.ntaps or cq.size != self.ntaps:
             raise ValueError("set_taps: %d / %d taps given, the chain was created with %d (numTaps is fixed at creation, as in CMSIS)" % (ci.size, cq.size, self.ntaps))
         _ck(self.ctx.lib.msdr_chain_set_taps(self.h, C.c_uint32(tapset), _hp(ci), _hp(cq)))
+
+    def set_taps_channels(self, first_channel, coeffs_i, coeffs_q=None):
+        """Q15: channel first_channel + i gets FIR coefficients of its own, coeffs_i[i] / coeffs_q[i] (int16 [count, numTaps], CMSIS order);
+        coeffs_q = None: the same array behind both filters (init_FIR() for AM / SYNCAM).  Every state kept."""
+        ci = _taps_per_channel("set_taps_channels", coeffs_i, self.ntaps)
+        cq = None if coeffs_q is None else _taps_per_channel("set_taps_channels", coeffs_q, self.ntaps)
+        if cq is not None and cq.shape != ci.shape:
+            raise ValueError("set_taps_channels: coeffs_i %s and coeffs_q %s differ in shape" % ((ci.shape,), (cq.shape,)))
+        _ck(self.ctx.lib.msdr_chain_set_taps_channels(self.h, C.c_uint32(first_channel), C.c_uint32(ci.shape[0]), _hp(ci), _hp(cq)))
 
     def set_osc(self, osc_i, osc_q):
         tdt = np.float32 if self.arith == ARITH_F32 else np.int16
