@@ -2228,6 +2228,7 @@ struct msdr_chain {
     float *d_bq_state_alt;
     float *d_mw_iir;                  // folded-IIR constants (MwIirConsts) or null
     bool mfw_ssb_fold, mfw_am_fold;   // cascade as matrix products for SSB tables / envelope tables
+    int mfw_am_rowlocal;              // envelope tables, two sections: 0 = 4 x 4 row scan, 1 / 2 = section 0 / 1 row-local, the other one scans in 2 x 2
     uint32_t units_wgs_ssb;           // unit table: workgroups of SSB-table units come first, envelope-table units after them
     long long part_nseg[2], part_seg_len[2];      // the two launches choose their own time segmentation (each must fill the GPU on its own)
     long long units_tiles;
@@ -2450,7 +2451,7 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
     c->no_fuse = getenv("MSDR_Q15_NO_FUSE") != nullptr;
     c->blk_force = getenv("MSDR_BIQUAD_BLK") ? atoi(getenv("MSDR_BIQUAD_BLK")) : -1;
     c->flags = cfg->flags; c->mfw_nw = 0; c->mfw_waves_per_cu = 0; c->d_bq_state_alt = nullptr; c->d_mw_iir = nullptr; c->d_units = nullptr; c->units_cap = 0;
-    c->mode_gen = 1; c->units_mode_gen = 0; c->units_nseg = 0; c->units_wgs = 0; c->units_wgs_ssb = 0; c->mfw_ssb_fold = false; c->mfw_am_fold = false; c->units_tiles = -1;
+    c->mode_gen = 1; c->units_mode_gen = 0; c->units_nseg = 0; c->units_wgs = 0; c->units_wgs_ssb = 0; c->mfw_ssb_fold = false; c->mfw_am_fold = false; c->mfw_am_rowlocal = 0; c->units_tiles = -1;
     c->part_nseg[0] = c->part_nseg[1] = 1; c->part_seg_len[0] = c->part_seg_len[1] = 0;
     c->d_at_tab = nullptr; c->at_ns = 0; c->at_stride = 0; c->at_nw = 0;
     c->d_qm_tab = nullptr; c->d_qm_order = nullptr; c->qm_stride = 0; c->qm_halo = 0; c->qm_bsteps = 0; c->qm_order_gen = 0; c->qm_fr = false;
@@ -2681,6 +2682,7 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
         const int S_ = (int)c->nstages, NS = 2 * S_;
         bool iirfold = (S_ == 1 || S_ == 2);
         bool amfold = false;
+        int am_rowlocal = 0;                 // envelope flavour, two sections: 0 = 4 x 4 row scan, 1 / 2 = section 0 / 1 is row-local (see below)
         double gap[32] = {0}, sec_a1[2] = {0, 0}, sec_a2[2] = {0, 0}, gl1[2] = {0, 0}, Rmax = 0.0;
         std::vector<float> iirc;
         auto run_cascade = [&](double *sig, const double *vin, double *yout, int len) {      // all-pole sections in series, state in/out
@@ -2776,6 +2778,21 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
                     Rd[m][4 - k] = a; Lmax = std::max(Lmax, std::fabs(a));          // element j = 4 - k: the row's inputs 28..31 in order
                 }
             amfold = iirfold && Lmax * std::ldexp(1.0, kMwIirEnvExp) < 60000.0;
+            // ---- row-local sections (envelope flavour, two sections).  The row transition is block lower-triangular, Mt = [[M0, 0], [C, M1]]
+            // with M_s = (section s's own 2 x 2 transition)^32.  Where M_s is nothing in fp32, section s enters every row with the previous
+            // row's zero-state end value and only the other section needs a scan (dimension 2).  What the kernel drops is M_s sigma_s per row:
+            // with mu_s = max |M_s[i][j]| and the section's state bound gl1[s] (per unit of input bound, the L1 norm of the partial cascade
+            // 0..s) at most 2 mu_s gl1[s]; it reaches the output through the response R, two components, |R| <= Rmax: 4 Rmax mu_s gl1[s].
+            // The output's own bound is gl1[S-1] in the same units and an fp32 output 96 dB below that bound (the floor of the 16-bit source)
+            // resolves 2^-24 2^-16 gl1[S-1].  Section s is row-local when
+            //        4 Rmax mu_s gl1[s]  <=  2^-40 gl1[S-1]
+            // (c3: low-pass Q 0.54, pole radius 0.21: mu_0 ~ 1e-22; the fs/8 notch, Q 15: mu_1 ~ 0.3).  Both damped: section 0 is taken, section 1
+            // keeps its 2 x 2 scan.  Decided here in double precision at create and at every rebuild (msdr_chain_set_biquad_coeffs).
+            if (S_ == 2 && amfold) {
+                double mu[2] = {0.0, 0.0};
+                for (int q = 0; q < 2; q++) for (int i = 0; i < 2; i++) for (int j = 0; j < 2; j++) mu[q] = std::max(mu[q], std::fabs(Mt[2 * q + i][2 * q + j]));
+                for (int q = 1; q >= 0; q--) if (4.0 * Rmax * mu[q] * gl1[q] <= std::ldexp(1.0, -40) * gl1[1]) am_rowlocal = q + 1;
+            }
             _Float16 *lf = reinterpret_cast<_Float16 *>(iirc.data() + kMwIirLfrag), *df = reinterpret_cast<_Float16 *>(iirc.data() + kMwIirDfrag);
             for (int st2 = 0; st2 < 2; st2++)
                 for (int l = 0; l < 64; l++)
@@ -3018,6 +3035,7 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
                 if (best > 0) rc = dzalloc(ctx, (size_t)c->channels * kBqStateFloats, &c->d_bq_state_alt);
                 if (!rc && iirfold && !iirc.empty()) rc = upload(ctx, iirc, &c->d_mw_iir);
                 c->mfw_ssb_fold = iirfold && !compact && c->d_mw_iir; c->mfw_am_fold = amfold && c->d_mw_iir;
+                c->mfw_am_rowlocal = c->mfw_am_fold ? am_rowlocal : 0;
                 if (best <= 0) c->mf_ok = false;               // not even one wave's window fits next to the fragments: the VALU kernels run
                 // (full-rate layout: a lone wave per CU waits out every LDS round trip of a 60-step burst on its own -- two waves were 1.4 x the
                 //  vector-ALU kernel at 384 taps, profiles/r05/nco_long_taps.txt; one is not taken)
@@ -3621,6 +3639,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         HIP_TRY(hipEventRecord(e0, c->ctx->stream));
     }
     const char *kname = f32 ? "chain_kernel<ArithF32>" : "chain_kernel<ArithQ15>";
+    uint32_t env_scan = 0;               // msdr_chain_info.env_scan: how the folded envelope flavour of chain_mfw_kernel scanned its row states
     bool nodes_fused = false;            // Q15 block cadence: the biquad nodes ran inside chain_q15mb_kernel
     unsigned block = kThreads;
     size_t lds_used = lds;
@@ -3652,6 +3671,8 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
             q.mf_units = c->d_units + (size_t)(part == 0 ? 0 : c->units_wgs_ssb) * c->mfw_nw * 2;
             q.nseg = (int)c->part_nseg[part]; q.seg_len = c->part_seg_len[part]; q.warm = (int)(c->part_nseg[part] > 1 ? warm_tiles * kTile : 0);
             const bool fold = part == 0 ? c->mfw_ssb_fold : c->mfw_am_fold;
+            const int rowlocal = (part == 1 && fold && !c->mf_fr && !c->d_at_tab) ? c->mfw_am_rowlocal : 0;
+            if (part == 1 && fold && !c->d_at_tab) env_scan = 1u + (uint32_t)rowlocal;
             if (part == 1 && c->d_at_tab) {
                 // envelope units on the taps-in-registers kernel: the same unit table read with this kernel's own workgroup size
                 ChainParams a = q;
@@ -3663,7 +3684,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
                 if (int rc2 = launch_check("chain_amtr_kernel")) return rc2;
                 continue;
             }
-            (void)launch_chain_mfw(c->ctx->stream, (int)c->nstages, part == 1, fold, c->mf_fr, g, block, lds, q);
+            (void)launch_chain_mfw(c->ctx->stream, (int)c->nstages, part == 1, fold, c->mf_fr, rowlocal, g, block, lds, q);
             if (int rc = launch_check("chain_mfw_kernel")) return rc;
         }
         static const char *const names[5] = {"chain_mfw_kernel<0>", "chain_mfw_kernel<1>", "chain_mfw_kernel<2>", "chain_mfw_kernel<3>", "chain_mfw_kernel<4>"};
@@ -3852,6 +3873,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
 
     snprintf(c->info.kernel, sizeof c->info.kernel, "%s%s", kname, !c->seq_bq ? "" : c->seq_bq->sequential ? " + biquad_df1_seq_kernel" : " + biquad_df1_kernel");
     c->info.grid = grid; c->info.block = block; c->info.lds_bytes = (uint32_t)lds_used;
+    c->info.env_scan = env_scan;
     c->info.time_segments = (uint32_t)nseg; c->info.warmup = (uint32_t)p.warm; c->info.tile = (uint32_t)(use_pc ? pc_tile : kTile);
     c->info.taps_padded = use_pc ? (uint32_t)c->pc_np : c->ntaps_pad;
     c->info.mfma_ksteps = use_mf ? (uint32_t)c->mf_bsteps : use_qm ? (uint32_t)c->qm_bsteps : 0u;

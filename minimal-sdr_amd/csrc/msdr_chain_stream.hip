@@ -12,8 +12,14 @@
 
 namespace msdr {
 
-hipError_t launch_chain_mfw(hipStream_t stream, int stages, bool am, bool fold, bool fr, unsigned grid, unsigned block, size_t lds, const ChainParams &q)
+hipError_t launch_chain_mfw(hipStream_t stream, int stages, bool am, bool fold, bool fr, int rowlocal, unsigned grid, unsigned block, size_t lds, const ChainParams &q)
 {
+    if (rowlocal) {          // envelope tables, two sections as matrix products, section rowlocal - 1 out of the row scan
+        if (stages != 2 || !am || !fold || fr || rowlocal > 2) return hipErrorInvalidValue;
+        if (rowlocal == 1) hipLaunchKernelGGL((chain_mfw_rowlocal_kernel<1>), dim3(grid), dim3(block), lds, stream, q);
+        else hipLaunchKernelGGL((chain_mfw_rowlocal_kernel<2>), dim3(grid), dim3(block), lds, stream, q);
+        return hipGetLastError();
+    }
     // SSB-table units and envelope-table units are separate launches of separate kernels (register allocation per flavour); the cascade as
     // matrix products (fold) exists for one and two sections
 #define MSDR_MFW_LAUNCH(SS, AMF, FO) do { if (fr) hipLaunchKernelGGL((chain_mfw_kernel<SS, AMF, FO, true>), dim3(grid), dim3(block), lds, stream, q); \

@@ -50,7 +50,7 @@ class ChainConfig(C.Structure):
 class ChainInfo(C.Structure):
     _fields_ = [("kernel", C.c_char * 64), ("grid", C.c_uint32), ("block", C.c_uint32), ("lds_bytes", C.c_uint32),
                 ("time_segments", C.c_uint32), ("warmup", C.c_uint32), ("tile", C.c_uint32),
-                ("taps_padded", C.c_uint32), ("mfma_ksteps", C.c_uint32)]
+                ("taps_padded", C.c_uint32), ("mfma_ksteps", C.c_uint32), ("env_scan", C.c_uint32)]
 
 
 _lib = None
@@ -766,7 +766,7 @@ class Chain(_Instance):
         _ck(self.ctx.lib.msdr_chain_get_info(self.h, C.byref(i)))
         return {"kernel": i.kernel.decode(), "grid": i.grid, "block": i.block, "lds_bytes": i.lds_bytes,
                 "time_segments": i.time_segments, "warmup": i.warmup, "tile": i.tile, "taps_padded": i.taps_padded,
-                "mfma_ksteps": i.mfma_ksteps}
+                "mfma_ksteps": i.mfma_ksteps, "env_scan": i.env_scan}
 
     def enable_timing(self, on=True):
         _ck(self.ctx.lib.msdr_chain_enable_timing(self.h, int(on)))
