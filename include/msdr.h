@@ -534,7 +534,23 @@ typedef struct {
                                       * were scanned in the last call.  0 = that flavour did not run; 1 = every section (2 x 2 or 4 x 4 matrices);
                                       * 2 / 3 = section 0 / 1 is row-local (its transition over a 32-sample row is nothing in fp32: it takes no
                                       * part in the scan), the other section scans alone with 2 x 2 matrices */
+    uint32_t flavour;                /* F32 chains: MSDR_FLAVOUR_* bits of the host decisions that selected device code for the last call, set where
+                                      * each launch is made (0 for Q15 chains).  `kernel` names a kernel family; this says which of its paths ran */
 } msdr_chain_info;
+#define MSDR_FLAVOUR_SSB_UNITS    0x0001u   /* a launch over LSB / USB / CW units (one accumulator, cascade numerator in the taps) */
+#define MSDR_FLAVOUR_ENV_UNITS    0x0002u   /* a launch over envelope units (two accumulators) */
+#define MSDR_FLAVOUR_SSB_FOLD     0x0004u   /* the SSB units' cascade ran as matrix products (folded into the tap tables) */
+#define MSDR_FLAVOUR_ENV_FOLD     0x0008u   /* the envelope units' cascade ran as matrix products (env_scan says how its row states were scanned) */
+#define MSDR_FLAVOUR_FULL_RATE    0x0010u   /* full-rate layout: a 128-periodic oscillator table, the mixer products staged as two streams */
+#define MSDR_FLAVOUR_COMPACT      0x0020u   /* full-rate layout with compact (shifted-copy) tap fragments */
+#define MSDR_FLAVOUR_SHARED_IQ    0x0040u   /* full-rate envelope units whose two accumulators read one set of fragments (coeffs_i == coeffs_q in ANY tap set of the chain) */
+#define MSDR_FLAVOUR_AMTR         0x0080u   /* the envelope units ran on the taps-in-registers kernel (chain_amtr_kernel) */
+#define MSDR_FLAVOUR_BLOCK        0x0100u   /* block cadence: chain_mfb_kernel, channel-batched tiles */
+#define MSDR_FLAVOUR_VALU_FOLD    0x0200u   /* chain_fold_kernel<P>; P in bits 12..14 */
+#define MSDR_FLAVOUR_SEQ_CASCADE  0x0400u   /* the cascade ran behind the main kernel in CMSIS order */
+#define MSDR_FLAVOUR_SEGMENTED    0x0800u   /* a launch split the call into more than one time segment */
+#define MSDR_FLAVOUR_FOLD_PERIOD_SHIFT 12
+#define MSDR_FLAVOUR_FOLD_PERIOD(f) (((f) >> MSDR_FLAVOUR_FOLD_PERIOD_SHIFT) & 7u)
 int msdr_chain_get_info(msdr_chain *chain, msdr_chain_info *info);
 /* Measurement aid (bench.py): when enabled every msdr_chain_process() brackets its MAIN kernel with
  * HIP events on the context's stream; get_kernel_time synchronises and returns the accumulated

@@ -2224,6 +2224,7 @@ struct msdr_chain {
     uint32_t flags;
     int mfw_nw, mfw_waves_per_cu;
     char *d_at_tab; int at_ns, at_stride, at_nw;          // envelope channels with the taps in registers (msdr_chain_amtr.hiph), or null
+    bool mf_compact, mf_share_iq;                         // full-rate layout: compact tap fragments / one fragment set for both envelope accumulators (msdr_chain_info.flavour)
     bool mf_fr;                                           // full-rate layout (msdr_chain_mfw.hiph): any 128-periodic oscillator table, mixer products staged as two streams
     float *d_bq_state_alt;
     float *d_mw_iir;                  // folded-IIR constants (MwIirConsts) or null
@@ -2570,7 +2571,7 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
         if (!rc) rc = dzalloc(ctx, (size_t)c->channels * kBqStateFloats, &c->d_bq_state);
     }
     // ---- tap folding (F32): oscillator period, folded tables, per-channel folded-set index ----------
-    c->fold_P = 0; c->fold_fs4_exact = false; c->mf_P = 0; c->mf_fr = false;
+    c->fold_P = 0; c->fold_fs4_exact = false; c->mf_P = 0; c->mf_fr = false; c->mf_compact = false; c->mf_share_iq = false;
     if (!rc && f32 && !(cfg->flags & MSDR_CHAIN_NO_TAP_FOLDING)) {
         std::vector<double> oc, os;                       // one period of cos / sin
         if (cfg->mixer == MSDR_MIXER_FS4) { oc = {1, 0, -1, 0}; os = {0, 1, 0, -1}; }
@@ -2758,6 +2759,9 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
                     const double val = ((l >> 5) == 1 && j < NS) ? Rr[l & 31][j] * std::ldexp(1.0, kMwIirSigExp) : 0.0;
                     const _Float16 vh = (_Float16)val;
                     rh[l * 8 + j] = vh; rl[l * 8 + j] = (_Float16)(val - (double)vh);
+#if defined(MSDR_MUTATE) && MSDR_MUTATE == 5       /* `make mutants`, never the product: the lo halves of the cascade's response fragments dropped (rl, and lf / df below) */
+                    rl[l * 8 + j] = (_Float16)0.0f;
+#endif
                 }
             iirc[kMwIirCoef + 0] = (S_ == 2) ? (float)sec_a1[1] : 0.0f;       // the last section's feedback: w_(S-1)[n] = y[n] - a1 y[n-1] - a2 y[n-2]
             iirc[kMwIirCoef + 1] = (S_ == 2) ? (float)sec_a2[1] : 0.0f;
@@ -2791,7 +2795,12 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
             if (S_ == 2 && amfold) {
                 double mu[2] = {0.0, 0.0};
                 for (int q = 0; q < 2; q++) for (int i = 0; i < 2; i++) for (int j = 0; j < 2; j++) mu[q] = std::max(mu[q], std::fabs(Mt[2 * q + i][2 * q + j]));
-                for (int q = 1; q >= 0; q--) if (4.0 * Rmax * mu[q] * gl1[q] <= std::ldexp(1.0, -40) * gl1[1]) am_rowlocal = q + 1;
+#if defined(MSDR_MUTATE) && MSDR_MUTATE == 4       /* `make mutants`, never the product: the row-local threshold loosened from 2^-40 to 2^-16 */
+                const int rowlocal_exp = -16;
+#else
+                const int rowlocal_exp = -40;
+#endif
+                for (int q = 1; q >= 0; q--) if (4.0 * Rmax * mu[q] * gl1[q] <= std::ldexp(1.0, rowlocal_exp) * gl1[1]) am_rowlocal = q + 1;
             }
             _Float16 *lf = reinterpret_cast<_Float16 *>(iirc.data() + kMwIirLfrag), *df = reinterpret_cast<_Float16 *>(iirc.data() + kMwIirDfrag);
             for (int st2 = 0; st2 < 2; st2++)
@@ -2801,12 +2810,18 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
                         const double val = (m >= kk) ? hfull[m - kk] * std::ldexp(1.0, kMwIirEnvExp) : 0.0;
                         const _Float16 vh = (_Float16)val;
                         lf[st2 * 1024 + l * 8 + j] = vh; lf[st2 * 1024 + 512 + l * 8 + j] = (_Float16)(val - (double)vh);
+#if defined(MSDR_MUTATE) && MSDR_MUTATE == 5
+                        lf[st2 * 1024 + 512 + l * 8 + j] = (_Float16)0.0f;
+#endif
                     }
             for (int l = 0; l < 64; l++)
                 for (int j = 0; j < 8; j++) {
                     const double val = ((l >> 5) == 1 && j < 4) ? Rd[l & 31][j] * std::ldexp(1.0, kMwIirEnvExp) : 0.0;
                     const _Float16 vh = (_Float16)val;
                     df[l * 8 + j] = vh; df[512 + l * 8 + j] = (_Float16)(val - (double)vh);
+#if defined(MSDR_MUTATE) && MSDR_MUTATE == 5
+                    df[512 + l * 8 + j] = (_Float16)0.0f;
+#endif
                 }
         }
         // A retune (msdr_chain_set_mode) hands the cascade's state and numerator history of the OLD mode / tap set to the kernel of
@@ -2927,6 +2942,7 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
                     // full rate, envelope table, one low-pass for both streams: M[1] over the Q positions IS M[0] over the I positions -- one set of
                     // fragments serves both accumulators (half the LDS: 512 taps fit where two sets do not)
                     const bool share = fr && v == 2 && memcmp(hi, hq, (size_t)N * sizeof(float)) == 0;
+                    if (share) c->mf_share_iq = true;
                     for (int o = 0; o < (v == 2 ? 2 : 1); o++)
                         for (int src = 0; src < 2; src++) {
                             int jlo = J, jhi = -1;                                   // chunks with any non-zero entry: one contiguous run
@@ -3011,7 +3027,7 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
                 rc = upload(ctx, bt, &c->d_bq_mf32);
             }
             if (!rc) {
-                c->mf_ok = true; c->mf_halo = H; c->mf_bsteps = bsteps; c->mf_stride = stride;
+                c->mf_ok = true; c->mf_halo = H; c->mf_bsteps = bsteps; c->mf_stride = stride; c->mf_compact = compact;
                 // wave-stream variant: waves per workgroup that put the most waves on a CU (<= 16: the kernel's <= 128 VGPRs allow
                 // 4 per SIMD) under the 160 KB of LDS -- counted in whole waves per SIMD.  A SIMD's tile rate is the same from two waves
                 // on (profiles/r03/c3_trims.txt), so a workgroup is as slow as its fullest SIMD: 13 waves (4 + 3 + 3 + 3) ran 4 % behind
@@ -3044,6 +3060,7 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
         }
     }
     if (c->mf_fr && !c->mf_ok) { c->mf_fr = false; c->mf_P = 0; }
+    if (!c->mf_ok) { c->mf_compact = false; c->mf_share_iq = false; }
     // ---- envelope channels with the taps in registers (msdr_chain_amtr.hiph): the exact Fs/4 mixer, both FIRs of every tap set with the
     // same taps (the reference's AM case, Minimal-SDR.ino:917-924), up to 257 taps; rides on the wave-stream kernel's unit table ----
     if (!rc && f32 && c->mf_ok && c->mfw_nw > 0 && !c->mf_fr && cfg->mixer == MSDR_MIXER_FS4 && !(cfg->flags & MSDR_CHAIN_NO_MFMA) &&
@@ -3639,6 +3656,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         HIP_TRY(hipEventRecord(e0, c->ctx->stream));
     }
     const char *kname = f32 ? "chain_kernel<ArithF32>" : "chain_kernel<ArithQ15>";
+    uint32_t flavour = 0;                // msdr_chain_info.flavour: MSDR_FLAVOUR_* of the launches below, set where each one is made
     uint32_t env_scan = 0;               // msdr_chain_info.env_scan: how the folded envelope flavour of chain_mfw_kernel scanned its row states
     bool nodes_fused = false;            // Q15 block cadence: the biquad nodes ran inside chain_q15mb_kernel
     unsigned block = kThreads;
@@ -3657,6 +3675,8 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
             if (launch_chain_mfb(c->ctx->stream, (int)c->nstages, part == 1, bp.wgs, bp.nw * 64, lds_used, q) != hipSuccess)
                 return fail(MSDR_STATUS_HIP_ERROR, "chain_mfb_kernel launch failed");
             grid += bp.wgs; block = bp.nw * 64;
+            flavour |= MSDR_FLAVOUR_BLOCK | (part == 0 ? MSDR_FLAVOUR_SSB_UNITS : MSDR_FLAVOUR_ENV_UNITS);
+            if (c->nstages > 0) flavour |= (part == 0 ? MSDR_FLAVOUR_SSB_FOLD : MSDR_FLAVOUR_ENV_FOLD);      // (the block kernel runs a cascade folded or not at all)
         }
         kname = names[c->nstages];
         if (c->nstages > 0) std::swap(c->d_bq_state, c->d_bq_state_alt);      // the kernel read bq_state and wrote bq_state_out
@@ -3673,6 +3693,8 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
             const bool fold = part == 0 ? c->mfw_ssb_fold : c->mfw_am_fold;
             const int rowlocal = (part == 1 && fold && !c->mf_fr && !c->d_at_tab) ? c->mfw_am_rowlocal : 0;
             if (part == 1 && fold && !c->d_at_tab) env_scan = 1u + (uint32_t)rowlocal;
+            flavour |= part == 0 ? MSDR_FLAVOUR_SSB_UNITS : MSDR_FLAVOUR_ENV_UNITS;
+            if (c->part_nseg[part] > 1) flavour |= MSDR_FLAVOUR_SEGMENTED;
             if (part == 1 && c->d_at_tab) {
                 // envelope units on the taps-in-registers kernel: the same unit table read with this kernel's own workgroup size
                 ChainParams a = q;
@@ -3682,10 +3704,13 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
                 const size_t alds = at_lds_bytes(c->at_ns, c->at_nw);
                 (void)launch_chain_amtr(c->ctx->stream, c->at_ns, (int)c->nstages, ag, (unsigned)c->at_nw * 64, alds, a);
                 if (int rc2 = launch_check("chain_amtr_kernel")) return rc2;
+                flavour |= MSDR_FLAVOUR_AMTR;
                 continue;
             }
             (void)launch_chain_mfw(c->ctx->stream, (int)c->nstages, part == 1, fold, c->mf_fr, rowlocal, g, block, lds, q);
             if (int rc = launch_check("chain_mfw_kernel")) return rc;
+            if (fold) flavour |= part == 0 ? MSDR_FLAVOUR_SSB_FOLD : MSDR_FLAVOUR_ENV_FOLD;
+            if (c->mf_fr) flavour |= MSDR_FLAVOUR_FULL_RATE | (c->mf_compact ? MSDR_FLAVOUR_COMPACT : 0u) | ((part == 1 && c->mf_share_iq) ? MSDR_FLAVOUR_SHARED_IQ : 0u);
         }
         static const char *const names[5] = {"chain_mfw_kernel<0>", "chain_mfw_kernel<1>", "chain_mfw_kernel<2>", "chain_mfw_kernel<3>", "chain_mfw_kernel<4>"};
         static const char *const names_fr[5] = {"chain_mfw_kernel<0> full-rate NCO streams", "chain_mfw_kernel<1> full-rate NCO streams", "chain_mfw_kernel<2> full-rate NCO streams",
@@ -3708,9 +3733,10 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     }
     else if (use_fold) {
         (void)launch_chain_fold(c->ctx->stream, c->fold_P, grid, lds, p);
+        flavour |= MSDR_FLAVOUR_VALU_FOLD | ((uint32_t)c->fold_P << MSDR_FLAVOUR_FOLD_PERIOD_SHIFT) | (nseg > 1 ? MSDR_FLAVOUR_SEGMENTED : 0u);
         kname = c->fold_P == 4 ? "chain_fold_kernel<4>" : c->fold_P == 2 ? "chain_fold_kernel<2>" : "chain_fold_kernel<1>";
     }
-    else if (f32) (void)launch_chain_generic(c->ctx->stream, false, grid, lds, p);
+    else if (f32) { (void)launch_chain_generic(c->ctx->stream, false, grid, lds, p); if (nseg > 1) flavour |= MSDR_FLAVOUR_SEGMENTED; }
     else if (use_qb) {
         grid = 0;
         // the two biquad nodes as the kernel's second phase: the reference's configuration (one stage per node, nothing between the
@@ -3799,7 +3825,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     if (e0) { HIP_TRY(hipEventRecord(e1, c->ctx->stream)); c->events.emplace_back(e0, e1); }
 
     if (c->seq_bq)             // F32, ill-conditioned cascade: arm_biquad_cascade_df1_f32 in CMSIS order, in place on the audio
-        if (int rc = msdr_biquad_df1_f32_process(c->seq_bq, (const float *)fout, (float *)fout, (uint32_t)n_samples)) return rc;
+        { if (int rc = msdr_biquad_df1_f32_process(c->seq_bq, (const float *)fout, (float *)fout, (uint32_t)n_samples)) return rc; flavour |= MSDR_FLAVOUR_SEQ_CASCADE; }
 
     if (pll_active)            // SYNCAM channels: I (in d_audio) and Q (scratch) -> PLL demodulator -> audio, before the biquad nodes
         if (int rc = msdr_syncam_q15(c->pll, c->d_mode, (const q15_t *)d_audio, c->d_pll_q, (q15_t *)d_audio, (uint32_t)n_samples)) return rc;
@@ -3873,7 +3899,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
 
     snprintf(c->info.kernel, sizeof c->info.kernel, "%s%s", kname, !c->seq_bq ? "" : c->seq_bq->sequential ? " + biquad_df1_seq_kernel" : " + biquad_df1_kernel");
     c->info.grid = grid; c->info.block = block; c->info.lds_bytes = (uint32_t)lds_used;
-    c->info.env_scan = env_scan;
+    c->info.env_scan = env_scan; c->info.flavour = f32 ? flavour : 0u;
     c->info.time_segments = (uint32_t)nseg; c->info.warmup = (uint32_t)p.warm; c->info.tile = (uint32_t)(use_pc ? pc_tile : kTile);
     c->info.taps_padded = use_pc ? (uint32_t)c->pc_np : c->ntaps_pad;
     c->info.mfma_ksteps = use_mf ? (uint32_t)c->mf_bsteps : use_qm ? (uint32_t)c->qm_bsteps : 0u;

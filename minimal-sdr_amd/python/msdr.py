@@ -23,6 +23,11 @@ CHAIN_NO_MFMA = 8
 CHAIN_SYNCAM_PLL = 32
 CHAIN_FOLD_ANY_PERIOD = 64
 CHAIN_OUT_I16 = 128
+# msdr_chain_info.flavour (include/msdr.h: MSDR_FLAVOUR_*)
+FLAVOUR_SSB_UNITS, FLAVOUR_ENV_UNITS, FLAVOUR_SSB_FOLD, FLAVOUR_ENV_FOLD = 0x1, 0x2, 0x4, 0x8
+FLAVOUR_FULL_RATE, FLAVOUR_COMPACT, FLAVOUR_SHARED_IQ, FLAVOUR_AMTR = 0x10, 0x20, 0x40, 0x80
+FLAVOUR_BLOCK, FLAVOUR_VALU_FOLD, FLAVOUR_SEQ_CASCADE, FLAVOUR_SEGMENTED = 0x100, 0x200, 0x400, 0x800
+FLAVOUR_FOLD_PERIOD_SHIFT = 12
 FE_DCBLOCK, FE_AMP, FE_AGC, FE_ALL = 1, 2, 4, 7
 
 STATUS_ARGUMENT_ERROR, STATUS_LENGTH_ERROR, STATUS_NO_DEVICE = -1, -2, -100
@@ -50,7 +55,7 @@ class ChainConfig(C.Structure):
 class ChainInfo(C.Structure):
     _fields_ = [("kernel", C.c_char * 64), ("grid", C.c_uint32), ("block", C.c_uint32), ("lds_bytes", C.c_uint32),
                 ("time_segments", C.c_uint32), ("warmup", C.c_uint32), ("tile", C.c_uint32),
-                ("taps_padded", C.c_uint32), ("mfma_ksteps", C.c_uint32), ("env_scan", C.c_uint32)]
+                ("taps_padded", C.c_uint32), ("mfma_ksteps", C.c_uint32), ("env_scan", C.c_uint32), ("flavour", C.c_uint32)]
 
 
 _lib = None
@@ -766,7 +771,7 @@ class Chain(_Instance):
         _ck(self.ctx.lib.msdr_chain_get_info(self.h, C.byref(i)))
         return {"kernel": i.kernel.decode(), "grid": i.grid, "block": i.block, "lds_bytes": i.lds_bytes,
                 "time_segments": i.time_segments, "warmup": i.warmup, "tile": i.tile, "taps_padded": i.taps_padded,
-                "mfma_ksteps": i.mfma_ksteps, "env_scan": i.env_scan}
+                "mfma_ksteps": i.mfma_ksteps, "env_scan": i.env_scan, "flavour": i.flavour}
 
     def enable_timing(self, on=True):
         _ck(self.ctx.lib.msdr_chain_enable_timing(self.h, int(on)))

@@ -47,6 +47,22 @@ def test_no_oracle_or_reference_linked_into_product():
                 assert "liboracle" not in text and "msdr_oracle" not in text and "orclib" not in text, f
 
 
+def test_chain_info_struct_matches_the_header():
+    """msdr_chain_info grew by `flavour`: the ctypes mirror has the header's fields in the header's order, and every MSDR_FLAVOUR_* value."""
+    hdr = open(os.path.join(ROOT, "include", "msdr.h")).read()
+    st = hdr[hdr.rindex("typedef struct", 0, hdr.index("} msdr_chain_info;")):hdr.index("} msdr_chain_info;")]
+    st = re.sub(r"/\*.*?\*/", "", st, flags=re.S)
+    fields = []
+    for decl in re.findall(r"(?:char|uint32_t)\s+([^;]+);", st):
+        fields += [re.sub(r"\[.*\]", "", f).strip() for f in decl.split(",")]
+    assert fields == [f[0] for f in msdr.ChainInfo._fields_], fields
+    assert fields[-2:] == ["env_scan", "flavour"]
+    assert C.sizeof(msdr.ChainInfo) == 64 + 4 * (len(fields) - 1)
+    for name, val in re.findall(r"#define MSDR_(FLAVOUR_[A-Z_]+)\s+(0x[0-9a-fA-F]+|\d+)u?\b", hdr):
+        assert getattr(msdr, name) == int(val, 0), name
+    assert len(re.findall(r"#define MSDR_FLAVOUR_[A-Z_]+\s", hdr)) == 13
+
+
 class ArmFirQ15(C.Structure):          # include/msdr_cmsis.h = arm_math.h:1027-1032
     _fields_ = [("numTaps", C.c_uint16), ("pState", C.c_void_p), ("pCoeffs", C.c_void_p)]
 
