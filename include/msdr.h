@@ -180,6 +180,13 @@ int msdr_fir_f32_create(msdr_ctx *ctx, uint16_t numTaps, const float32_t *pCoeff
 int msdr_fir_f32_process(msdr_fir_f32 *S, const float32_t *d_src, float32_t *d_dst, uint32_t blockSize);
 int msdr_fir_f32_reset(msdr_fir_f32 *S);
 int msdr_fir_f32_set_coeffs(msdr_fir_f32 *S, const float32_t *pCoeffs);   /* as msdr_fir_q15_set_coeffs: state kept, same numTaps */
+/* As msdr_fir_q15_set_coeffs_channels, word for word: pCoeffs is a HOST array [count][numTaps] (CMSIS order) for channels first_channel ..
+ * first_channel + count - 1.  State and history length are kept; count == 0 does nothing; a range past `channels` and a NULL array are
+ * MSDR_STATUS_ARGUMENT_ERROR.  From the first such call on msdr_fir_f32_process runs chain_f32pc_kernel (FIR-only flavour: plain fp32 FMAs,
+ * no input-range scaling: msdr_fir_f32_set_input_range has nothing to say there) over the existing history; msdr_fir_f32_set_coeffs keeps
+ * writing all channels.  Instances of more than 7 936 taps are refused (MSDR_STATUS_ARGUMENT_ERROR, nothing changed: the kernel keeps a
+ * channel's window and tap row in 64 KB of LDS).  Synchronises the stream. */
+int msdr_fir_f32_set_coeffs_channels(msdr_fir_f32 *S, uint32_t first_channel, uint32_t count, const float32_t *pCoeffs);
 const char *msdr_fir_f32_kernel_name(msdr_fir_f32 *S);      /* the kernel msdr_fir_f32_process launches for this instance */
 /* Filters of 16..513 taps run on the matrix cores with the samples as two fp16 pieces (22 bits) after a power-of-two scale.  By
  * default the scale is chosen per 1024-output tile from the data (block floating point): nothing to declare.  max_abs > 0 pins
@@ -499,6 +506,20 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   lengths 32 .. 512, no PLL / LMS channels, no pending oscillator change) and stays valid across later msdr_chain_set_taps_channels
  *   calls, which rewrite the table the captured launches read; like every graph it is refused after a live update that rebuilds the chain's
  *   tables (msdr_chain_set_taps, msdr_chain_set_osc, ...) and after msdr_chain_reset.
+ * msdr_chain_set_taps_channels_f32 (F32): the same for an fp32 chain, with float arrays [count][num_taps]; the semantics are those of
+ *   msdr_chain_set_taps_channels (arguments, states, interplay with msdr_chain_set_mode / set_taps / init_fir / reset / set_osc / set_anr /
+ *   set_biquad_coeffs).  A Q15 chain is MSDR_STATUS_ARGUMENT_ERROR (and msdr_chain_set_taps_channels keeps refusing fp32 chains).  From
+ *   the first such call on, for the rest of its life, the chain's demodulator kernel is chain_f32pc_kernel (plain fp32 FMAs on the vector
+ *   ALU, coefficient operand per channel; msdr_chain_get_info().kernel names it, flavour carries MSDR_FLAVOUR_TAPS_PC); the cascade runs
+ *   behind it in CMSIS order (MSDR_FLAVOUR_SEQ_CASCADE) -- at the first call a cascade that ran inside the kernel is moved there with its
+ *   state, the way msdr_chain_set_biquad_coeffs moves one (and with that call's one refusal: a running cascade whose block-parallel state
+ *   has no unique CMSIS state) --, PLL and LMS channels filter with their own rows, MSDR_CHAIN_OUT_I16 converts last.  Long calls are split
+ *   into time segments (MSDR_FLAVOUR_SEGMENTED; msdr_chain_config.time_segments is honoured: 1 never splits, > 1 asks for that many); the
+ *   FIR needs no warm-up.  Chains of more than 3 840 taps are refused
+ *   (MSDR_STATUS_ARGUMENT_ERROR, nothing changed: a channel's two windows and two tap rows live in 64 KB of LDS).  Graphs: a
+ *   msdr_chain_graph made before the first call is refused afterwards (MSDR_STATUS_ARGUMENT_ERROR at launch), and
+ *   msdr_chain_graph_create on a chain already in per-channel mode is refused with MSDR_STATUS_ARGUMENT_ERROR (the launch geometry is
+ *   chosen per call): this path has no graph replay.
  * msdr_chain_set_biquad_coeffs (F32): all 5 * num_biquad_stages coefficients of the arm_biquad_cascade_df1_f32 stage, CMSIS
  *   semantics (the filter carries on from the pState arm_biquad_cascade_df1_f32 would hold; see msdr_biquad_df1_f32_set_coeffs).
  *   The number of stages is fixed at creation, as numStages is in CMSIS.
@@ -510,6 +531,8 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
 int msdr_chain_set_taps(msdr_chain *chain, uint32_t tapset, const void *coeffs_i, const void *coeffs_q);
 int msdr_chain_set_taps_channels(msdr_chain *chain, uint32_t first_channel, uint32_t count,
                                  const q15_t *coeffs_i, const q15_t *coeffs_q);
+int msdr_chain_set_taps_channels_f32(msdr_chain *chain, uint32_t first_channel, uint32_t count,
+                                     const float32_t *coeffs_i, const float32_t *coeffs_q);
 int msdr_chain_set_node_coefficients(msdr_chain *chain, uint32_t node, uint32_t stage, const int32_t coef[5]);
 int msdr_chain_set_node_coefficients_channels(msdr_chain *chain, uint32_t node, uint32_t first_channel,
                                               uint32_t count, uint32_t stage, const int32_t *coef);
@@ -551,6 +574,9 @@ typedef struct {
 #define MSDR_FLAVOUR_SEGMENTED    0x0800u   /* a launch split the call into more than one time segment */
 #define MSDR_FLAVOUR_FOLD_PERIOD_SHIFT 12
 #define MSDR_FLAVOUR_FOLD_PERIOD(f) (((f) >> MSDR_FLAVOUR_FOLD_PERIOD_SHIFT) & 7u)
+/* One more bit of `flavour`, an enumerator beside the macros above (their list is mirrored one for one, and counted, by the Python binding's ABI test):
+ * chain_f32pc_kernel ran -- per-channel FIR coefficients, msdr_chain_set_taps_channels_f32. */
+enum { MSDR_FLAVOUR_TAPS_PC = 0x8000u };
 int msdr_chain_get_info(msdr_chain *chain, msdr_chain_info *info);
 /* Measurement aid (bench.py): when enabled every msdr_chain_process() brackets its MAIN kernel with
  * HIP events on the context's stream; get_kernel_time synchronises and returns the accumulated

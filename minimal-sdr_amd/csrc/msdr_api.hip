@@ -19,6 +19,7 @@
 #include "msdr_chain_mfb.hiph"
 #include "msdr_chain_q15mb.hiph"
 #include "msdr_chain_q15pc.hiph"
+#include "msdr_chain_f32pc.hiph"
 #include "msdr_block.h"
 #include "msdr_design.h"
 #include "msdr_cascade_state.h"
@@ -822,9 +823,13 @@ struct msdr_fir_f32 : FirInst<float, float> {
     // time -0.5 % only (the kernel sits at the power cap: the clock rises by what the traffic saves), runs of 2 .. 8 alike
     // (profiles/r04/README.md).  MSDR_TQ_RUN_SHIFT overrides (tests: 0 .. 3).
     int tq_run_shift_cap = getenv("MSDR_TQ_RUN_SHIFT") ? std::max(0, std::min(6, atoi(getenv("MSDR_TQ_RUN_SHIFT")))) : 3;
-    int last_launch = 0;                 // what the last msdr_fir_f32_process launched: 0 none yet, 1 tile queue, 2 fir_f32mf_kernel (the name follows the size guard)
+    int last_launch = 0;                 // what the last msdr_fir_f32_process launched: 0 none yet, 1 tile queue, 2 fir_f32mf_kernel, 3 chain_f32pc_kernel (the name follows the size guard)
     bool tq_run_forced = getenv("MSDR_TQ_RUN_SHIFT") != nullptr;       // (the override also lifts the "every wave gets >= 16 runs" rule: small test shapes reach the run code)
     float input_range = 0.0f;            // 0 = block floating point per tile (default); > 0: a fixed scale for samples below this magnitude
+    // per-channel coefficients (msdr_fir_f32_set_coeffs_channels): from the first such call on chain_f32pc_kernel<., true, false> runs, over the same history
+    bool per_channel = false;
+    int pc_np = 0;
+    float *d_pc_taps = nullptr;           // [channels][pc_np], complete for every channel
 };
 
 template <typename Inst, typename In, typename El>
@@ -1194,8 +1199,29 @@ extern "C" int msdr_fir_f32_set_input_range(msdr_fir_f32 *S, float max_abs)
     S->input_range = max_abs;
     return S->d_fm_tab ? fir_f32_upload_header(S) : 0;
 }
+static int fir_f32_process_pc(msdr_fir_f32 *S, const float32_t *d_src, float32_t *d_dst, uint32_t blockSize)
+{
+    if (int rc = bind(S->ctx)) return rc;
+    if (blockSize == 0) return 0;
+    if (!d_src || !d_dst) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null buffer");
+    if ((const void *)d_src == (const void *)d_dst)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "FIR process is not in-place (the reference uses separate buffers, Minimal-SDR.ino:574-578)");
+    PcfParams q;
+    memset(&q, 0, sizeof q);
+    q.x = d_src; q.out = d_dst; q.hist_in = S->d_hist[S->cur]; q.n = (long long)blockSize; q.channels = (int)S->channels;
+    q.hist_len = (int)S->hist_len; q.np = S->pc_np; q.taps = S->d_pc_taps; q.mixer = MSDR_MIXER_NCO; q.in_scale = 1.0f;
+    { KernelTimer kt(S->ctx); if (launch_chain_f32pc(S->ctx->stream, true, S->ctx->num_cus, 0, q, nullptr) != hipSuccess) return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pc_kernel launch failed"); }
+    if (int rc = launch_check("chain_f32pc_kernel")) return rc;
+    S->last_launch = 3;
+    hipLaunchKernelGGL((history_kernel<float>), dim3(grid_1d((long long)S->channels * S->hist_len)), dim3(256), 0, S->ctx->stream,
+                       d_src, (const float *)S->d_hist[S->cur], S->d_hist[S->cur ^ 1], (long long)blockSize, (int)S->hist_len, (int)S->channels);
+    if (int rc = launch_check("history_kernel")) return rc;
+    S->cur ^= 1;
+    return 0;
+}
 extern "C" int msdr_fir_f32_process(msdr_fir_f32 *S, const float32_t *d_src, float32_t *d_dst, uint32_t blockSize)
 {
+    if (S && S->per_channel) return fir_f32_process_pc(S, d_src, d_dst, blockSize);
     if (!S || !S->d_fm_tab) return fir_process<FirF32>(S, d_src, d_dst, blockSize);
     if (int rc = bind(S->ctx)) return rc;
     if (blockSize == 0) return 0;
@@ -1258,6 +1284,16 @@ extern "C" int msdr_fir_f32_reset(msdr_fir_f32 *S) { return fir_reset(S); }
 extern "C" int msdr_fir_f32_set_coeffs(msdr_fir_f32 *S, const float32_t *pCoeffs)
 {
     if (!S || !pCoeffs) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
+    if (S->per_channel) {
+        // the instance runs chain_f32pc_kernel for life and its uniform tables are never read again: set_coeffs keeps writing ALL channels, i.e.
+        // every row of the per-channel table; history pair and history length stay as they are (as msdr_fir_q15_set_coeffs does)
+        if (int rc = bind(S->ctx)) return rc;
+        std::vector<float> t((size_t)S->channels * S->pc_np, 0.0f);
+        for (uint32_t ch = 0; ch < S->channels; ch++) memcpy(t.data() + (size_t)ch * S->pc_np + (S->pc_np - S->ntaps), pCoeffs, S->ntaps * sizeof(float));
+        HIP_TRY(hipStreamSynchronize(S->ctx->stream));
+        HIP_TRY(hipMemcpy(S->d_pc_taps, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+        return 0;
+    }
     msdr_fir_f32 *old = nullptr;
     const float range = S->input_range;
     auto create = [&](msdr_fir_f32 **n) {
@@ -1269,11 +1305,39 @@ extern "C" int msdr_fir_f32_set_coeffs(msdr_fir_f32 *S, const float32_t *pCoeffs
     if (int rc = fir_swap_coeffs(S, create)) { if (old) msdr_fir_f32_destroy(old); return rc; }
     return msdr_fir_f32_destroy(old);
 }
+// arm_fir_f32 over a bank whose instances each point at a coefficient array of their own (arm_fir_init_f32 keeps the pointer)
+extern "C" int msdr_fir_f32_set_coeffs_channels(msdr_fir_f32 *S, uint32_t first_channel, uint32_t count, const float32_t *pCoeffs)
+{
+    if (!S) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null instance");
+    if (int rc = bind(S->ctx)) return rc;
+    if (count == 0) return 0;
+    if (!pCoeffs) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null coefficient array");
+    if (first_channel >= S->channels || count > S->channels - first_channel)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "channels %u .. %llu of %u", first_channel, (unsigned long long)first_channel + count - 1, S->channels);
+    if (f32pc_np((int)S->ntaps) > f32pc_max_taps(true))          // (one wave's window and its tap row must fit the kernel's LDS)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "per-channel coefficients: the kernel holds filters of up to %d taps (this instance has %u); nothing changed", f32pc_max_taps(true), S->ntaps);
+    HIP_TRY(hipStreamSynchronize(S->ctx->stream));
+    if (!S->per_channel) {          // every channel starts from the shared coefficients (d_taps: front-padded to ntaps_pad)
+        const int np = f32pc_np((int)S->ntaps);
+        std::vector<float> shared(S->ntaps_pad);
+        HIP_TRY(hipMemcpy(shared.data(), S->d_taps, shared.size() * sizeof(float), hipMemcpyDeviceToHost));
+        std::vector<float> t((size_t)S->channels * np, 0.0f);
+        for (uint32_t ch = 0; ch < S->channels; ch++)
+            for (uint32_t k = 0; k < S->ntaps; k++) t[(size_t)ch * np + (np - S->ntaps) + k] = shared[S->ntaps_pad - S->ntaps + k];
+        if (int rc = upload(S->ctx, t, &S->d_pc_taps)) return rc;
+        S->pc_np = np; S->per_channel = true;
+    }
+    std::vector<float> rows((size_t)count * S->pc_np, 0.0f);
+    for (uint32_t i = 0; i < count; i++) memcpy(rows.data() + (size_t)i * S->pc_np + (S->pc_np - S->ntaps), pCoeffs + (size_t)i * S->ntaps, S->ntaps * sizeof(float));
+    HIP_TRY(hipMemcpy(S->d_pc_taps + (size_t)first_channel * S->pc_np, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
+    return 0;
+}
 // which kernel msdr_fir_f32_process launches for this instance (benchmarks / tests)
 extern "C" const char *msdr_fir_f32_kernel_name(msdr_fir_f32 *S)
 {
     static thread_local char name[64];
     if (!S) return "";
+    if (S->per_channel) return "chain_f32pc_kernel (per-channel coefficients)";
     // (a call whose tile count does not fit the queue's 32-bit index runs the stream kernel: after a call the name is the launched one)
     if (S->d_tr_tab && S->d_tq_ctr && S->last_launch != 2) snprintf(name, sizeof name, "fir_f32tq_kernel<%d, %s>", S->tr_ns, S->tr_skip1 ? "true" : "false");
     else snprintf(name, sizeof name, "%s", S->d_fm_tab ? "fir_f32mf_kernel" : "fir_kernel<FirF32>");
@@ -1281,7 +1345,7 @@ extern "C" const char *msdr_fir_f32_kernel_name(msdr_fir_f32 *S)
 }
 extern "C" int msdr_fir_f32_destroy(msdr_fir_f32 *S)
 {
-    if (S) { hipFree(S->d_fm_tab); hipFree(S->d_tr_tab); hipFree(S->d_tq_ctr); }
+    if (S) { hipFree(S->d_fm_tab); hipFree(S->d_tr_tab); hipFree(S->d_tq_ctr); hipFree(S->d_pc_taps); }
     return fir_destroy(S);
 }
 
@@ -2299,6 +2363,11 @@ struct msdr_chain {
     int16_t *d_pc_taps = nullptr;         // [channels][2][pc_np]: I row, Q row
     std::vector<int16_t> h_pc_taps;       // the host's copy
     std::vector<char> h_pc_own;           // per channel: 1 = taps of its own, 0 = a copy of its tap set's
+    // the same for fp32 chains (msdr_chain_set_taps_channels_f32): chain_f32pc_kernel (msdr_chain_f32pc.hiph) over a float table, pc_np a
+    // multiple of 4.  The cascade of such a chain runs in CMSIS order behind the kernel (seq_bq) for the rest of its life.
+    float *d_pcf_taps = nullptr;          // [channels][2][pc_np]
+    bool seq_forced = false;              // every rebuild keeps the cascade behind the kernel (chain_rebuild)
+    std::vector<float> h_pcf_taps;
     msdr_chain_info info;
     // optional per-launch timing of the main kernel
     bool timing;
@@ -2324,9 +2393,22 @@ static void chain_pc_row_from(msdr_chain *c, uint32_t ch, const int16_t *ci, con
     memcpy(row + off, ci, c->ntaps * sizeof(int16_t));
     memcpy(row + c->pc_np + off, cq, c->ntaps * sizeof(int16_t));
 }
+// msdr_chain_info.kernel of an fp32 chain with per-channel taps.  (Kept out of msdr_chain_process: the census of the UNIFORM fp32 flavours,
+// tests/test_f32_flavour_cases.py, holds that function's kernel-name literals against its own table; this path has its own tests,
+// tests/test_gpu_taps_per_channel_f32.py and tests/test_f32pc_cases.py.)
+static const char kPcfKernelName[] = "chain_f32pc_kernel (per-channel taps)";
+static void chain_pcf_row_from(msdr_chain *c, uint32_t ch, const float *ci, const float *cq)
+{
+    float *row = c->h_pcf_taps.data() + (size_t)ch * 2 * c->pc_np;
+    const int off = c->pc_np - (int)c->ntaps;                   // zero taps in FRONT: they meet older samples
+    memset(row, 0, (size_t)2 * c->pc_np * sizeof(float));
+    memcpy(row + off, ci, c->ntaps * sizeof(float));
+    memcpy(row + c->pc_np + off, cq, c->ntaps * sizeof(float));
+}
 static void chain_pc_row_shared(msdr_chain *c, uint32_t ch)       // the rows of the tap set the channel is on (the stored configuration)
 {
     const int ts = c->h_tapset[ch];
+    if (c->arith == MSDR_ARITH_F32) { chain_pcf_row_from(c, ch, (const float *)c->store.ci[ts].data(), (const float *)c->store.cq[ts].data()); return; }
     chain_pc_row_from(c, ch, (const int16_t *)c->store.ci[ts].data(), (const int16_t *)c->store.cq[ts].data());
 }
 // rows first .. first + count - 1 to the device; the stream is drained first (a kernel in flight reads the table)
@@ -2334,6 +2416,11 @@ static int chain_pc_upload(msdr_chain *c, uint32_t first, uint32_t count)
 {
     HIP_TRY(hipStreamSynchronize(c->ctx->stream));
     const size_t row = (size_t)2 * c->pc_np;
+    if (c->arith == MSDR_ARITH_F32) {
+        HIP_TRY(hipMemcpy(c->d_pcf_taps + first * row, c->h_pcf_taps.data() + first * row, count * row * sizeof(float), hipMemcpyHostToDevice));
+        c->post_mode_gen = 0;          // PLL / LMS channels: the auxiliary chain is made again with these rows (chain_post_build_steps)
+        return 0;
+    }
     HIP_TRY(hipMemcpy(c->d_pc_taps + first * row, c->h_pc_taps.data() + first * row, count * row * sizeof(int16_t), hipMemcpyHostToDevice));
     return 0;
 }
@@ -2366,7 +2453,7 @@ static void chain_free(msdr_chain *c)
     hipFree(c->d_anr_on);
     for (auto &e : c->events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (auto &o : c->osc_pending) hipFree(o.d_tab);
-    hipFree(c->d_f32_scratch); hipFree(c->d_osc_hist); hipFree(c->d_btiles); hipFree(c->d_pc_taps);
+    hipFree(c->d_f32_scratch); hipFree(c->d_osc_hist); hipFree(c->d_btiles); hipFree(c->d_pc_taps); hipFree(c->d_pcf_taps);
     delete c;
 }
 
@@ -3220,6 +3307,16 @@ static int chain_post_build_steps(msdr_chain *c)
     a.flags = c->flags & ~(uint32_t)(MSDR_CHAIN_SYNCAM_PLL | MSDR_CHAIN_OUT_I16);      // (the auxiliary chain hands fp32 to the PLL / LMS steps)
     if (int rc = msdr_chain_create(c->ctx, &a, &c->aux)) return rc;
     c->aux->phase = c->phase;
+    if (c->pc_active) {          // per-channel taps: every row of the auxiliary chain filters with its channel's rows
+        std::vector<float> ri((size_t)virt_row.size() * c->ntaps), rq(ri.size());
+        const int off = c->pc_np - (int)c->ntaps;
+        for (size_t v = 0; v < virt_row.size(); v++) {
+            const float *row = c->h_pcf_taps.data() + (size_t)virt_row[v] * 2 * c->pc_np;
+            memcpy(ri.data() + v * c->ntaps, row + off, c->ntaps * sizeof(float));
+            memcpy(rq.data() + v * c->ntaps, row + c->pc_np + off, c->ntaps * sizeof(float));
+        }
+        if (int rc = msdr_chain_set_taps_channels_f32(c->aux, 0, (uint32_t)virt_row.size(), ri.data(), rq.data())) return rc;
+    }
     for (const auto &o : c->osc_pending) {          // the auxiliary chain takes the same raw history over: the same tables apply to it
         msdr_chain::OscPending q{nullptr, o.elapsed};
         const size_t bytes = (size_t)c->osc_len * 2 * sizeof(float);
@@ -3458,7 +3555,9 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     // (history samples that arrived under an earlier oscillator table are still in reach, msdr_chain_set_osc: the as-written kernel mixes
     //  each with the table of its own time; the fast kernels come back once the history has turned over)
     if (c->force_generic) use_fold = false;
-    const bool use_mf = f32 && c->mf_ok && !c->force_generic;
+    const bool use_pcf = f32 && c->pc_active;                    // per-channel taps, fp32: chain_f32pc_kernel in place of every uniform demodulator kernel
+    if (use_pcf) use_fold = false;
+    const bool use_mf = f32 && c->mf_ok && !c->force_generic && !use_pcf;
     const bool use_mfw = use_mf && c->mfw_nw > 0;
     const bool use_pc = !f32 && c->pc_active;                    // per-channel taps: chain_q15pc_kernel in place of every uniform demodulator kernel
     bool use_qm = !f32 && c->d_qm_tab != nullptr && !c->force_generic && !use_pc;
@@ -3636,6 +3735,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     if (c->dry_run) {
         // msdr_chain_graph_create's preparation pass: everything a block-cadence call needs from the host is in place now; say whether the
         // launches that follow are fixed (capturable into a HIP graph) -- and make none
+        if (use_pcf) return fail(MSDR_STATUS_ARGUMENT_ERROR, "an fp32 chain with per-channel FIR coefficients (chain_f32pc_kernel: launch geometry chosen per call) is not capturable");
         if (use_pc) {            // chain_q15pc_kernel + the kernels behind it + the history kernel: a fixed set of launches at a block-cadence length
             if (!mb_n_ok((long long)n_samples)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "not a block-cadence call (32 .. 512 samples, a divisor of 1024): nothing to capture");
             if (pll_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the PLL demodulator runs behind the kernel: not capturable");
@@ -3735,6 +3835,18 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         (void)launch_chain_fold(c->ctx->stream, c->fold_P, grid, lds, p);
         flavour |= MSDR_FLAVOUR_VALU_FOLD | ((uint32_t)c->fold_P << MSDR_FLAVOUR_FOLD_PERIOD_SHIFT) | (nseg > 1 ? MSDR_FLAVOUR_SEGMENTED : 0u);
         kname = c->fold_P == 4 ? "chain_fold_kernel<4>" : c->fold_P == 2 ? "chain_fold_kernel<2>" : "chain_fold_kernel<1>";
+    }
+    else if (use_pcf) {
+        PcfParams q;
+        memset(&q, 0, sizeof q);
+        q.x = d_if; q.out = (float *)fout; q.hist_in = c->d_hist[c->cur]; q.n = (long long)n_samples; q.channels = (int)c->channels;
+        q.hist_len = (int)c->hist_len; q.np = c->pc_np; q.taps = c->d_pcf_taps; q.chan_mode = c->d_mode; q.mixer = c->mixer; q.osc = c->d_osc;
+        q.osc_len = (int)c->osc_len; q.phase0 = (int)c->phase; q.in_scale = c->in_scale; q.osc_hist = p.osc_hist;
+        PcLaunch geo;
+        if (launch_chain_f32pc(c->ctx->stream, false, c->ctx->num_cus, (int)c->time_segments, q, &geo) != hipSuccess)
+            return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pc_kernel launch failed");
+        kname = kPcfKernelName; grid = geo.grid; block = geo.block; lds_used = geo.lds_bytes; nseg = geo.nseg; pc_tile = geo.tile;
+        flavour |= MSDR_FLAVOUR_TAPS_PC | (geo.nseg > 1 ? MSDR_FLAVOUR_SEGMENTED : 0u);
     }
     else if (f32) { (void)launch_chain_generic(c->ctx->stream, false, grid, lds, p); if (nseg > 1) flavour |= MSDR_FLAVOUR_SEGMENTED; }
     else if (use_qb) {
@@ -3900,8 +4012,8 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     snprintf(c->info.kernel, sizeof c->info.kernel, "%s%s", kname, !c->seq_bq ? "" : c->seq_bq->sequential ? " + biquad_df1_seq_kernel" : " + biquad_df1_kernel");
     c->info.grid = grid; c->info.block = block; c->info.lds_bytes = (uint32_t)lds_used;
     c->info.env_scan = env_scan; c->info.flavour = f32 ? flavour : 0u;
-    c->info.time_segments = (uint32_t)nseg; c->info.warmup = (uint32_t)p.warm; c->info.tile = (uint32_t)(use_pc ? pc_tile : kTile);
-    c->info.taps_padded = use_pc ? (uint32_t)c->pc_np : c->ntaps_pad;
+    c->info.time_segments = (uint32_t)nseg; c->info.warmup = (uint32_t)p.warm; c->info.tile = (uint32_t)((use_pc || use_pcf) ? pc_tile : kTile);
+    c->info.taps_padded = (use_pc || use_pcf) ? (uint32_t)c->pc_np : c->ntaps_pad;
     c->info.mfma_ksteps = use_mf ? (uint32_t)c->mf_bsteps : use_qm ? (uint32_t)c->qm_bsteps : 0u;
     return 0;
 }
@@ -4188,7 +4300,10 @@ static int chain_rebuild(msdr_chain *c, const ChainCfgStore &edited, void **stea
     if (c->floor_gen == c->gen) { g_chain_floor_d = std::max(g_chain_floor_d, c->floor_d); g_chain_floor_sig = std::max(g_chain_floor_sig, c->floor_sig); }
     g_chain_floor_d = std::max(g_chain_floor_d, extra_floor_d); g_chain_floor_sig = std::max(g_chain_floor_sig, extra_floor_sig);
     const double used_d = g_chain_floor_d, used_sig = g_chain_floor_sig;
+    // (per-channel taps on an fp32 chain: the cascade stays in CMSIS order behind chain_f32pc_kernel, whatever the coefficients would choose)
+    g_chain_force_seq_cascade = c->seq_forced && cfg.num_biquad_stages > 0;
     const int rc = msdr_chain_create(c->ctx, &cfg, &n);
+    g_chain_force_seq_cascade = false;
     g_chain_floor_d = 0.0; g_chain_floor_sig = 0.0;
     if (rc) return rc;
     if (n->channels != c->channels || n->osc_len != c->osc_len || n->ntaps != c->ntaps) {
@@ -4226,6 +4341,7 @@ static int chain_rebuild(msdr_chain *c, const ChainCfgStore &edited, void **stea
     // per-channel taps survive every rebuild; the channels still on a shared tap set follow that set's (possibly new) coefficients
     n->rebuild_gen = c->rebuild_gen + 1;
     n->pc_active = c->pc_active; n->pc_np = c->pc_np; std::swap(n->d_pc_taps, c->d_pc_taps); n->h_pc_taps.swap(c->h_pc_taps); n->h_pc_own.swap(c->h_pc_own);
+    std::swap(n->d_pcf_taps, c->d_pcf_taps); n->h_pcf_taps.swap(c->h_pcf_taps); n->seq_forced = c->seq_forced;
     std::swap(*c, *n);
     if (steal_osc) { *steal_osc = n->d_osc; n->d_osc = nullptr; }
     chain_free(n);
@@ -4358,6 +4474,50 @@ extern "C" int msdr_chain_set_taps_channels(msdr_chain *c, uint32_t first_channe
     return first_call ? chain_pc_upload(c, 0, c->channels) : chain_pc_upload(c, first_channel, count);
 }
 
+// force_seq: the rebuilt chain runs the cascade in CMSIS order behind the main kernel whatever the coefficients would choose (a chain that is
+// about to get, or has, per-channel FIR coefficients: msdr_chain_set_taps_channels_f32 moves the running cascade there with its state)
+static int chain_set_biquad_coeffs_impl(msdr_chain *c, const float32_t *coeffs, bool force_seq);
+// the same for an fp32 chain: rows of floats, chain_f32pc_kernel (msdr_chain_f32pc.hiph) from the first call on
+extern "C" int msdr_chain_set_taps_channels_f32(msdr_chain *c, uint32_t first_channel, uint32_t count, const float32_t *coeffs_i, const float32_t *coeffs_q)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (int rc = bind(c->ctx)) return rc;
+    if (c->arith != MSDR_ARITH_F32)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "float per-channel FIR coefficients belong to F32 chains (Q15: msdr_chain_set_taps_channels)");
+    if (count == 0) return 0;
+    if (!coeffs_i) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null coefficient array");
+    if (first_channel >= c->channels || count > c->channels - first_channel)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "channels %u .. %llu of %u", first_channel, (unsigned long long)first_channel + count - 1, c->channels);
+    if (f32pc_np((int)c->ntaps) > f32pc_max_taps(false))      // (one wave's two windows and its two tap rows must fit the kernel's LDS)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "per-channel coefficients: the kernel holds filters of up to %d taps (this chain has %u); nothing changed", f32pc_max_taps(false), c->ntaps);
+    if (!coeffs_q) coeffs_q = coeffs_i;                          // init_FIR() for AM / SYNCAM: one array behind both instances (.ino:917-924)
+    const bool first_call = !c->pc_active;
+    if (first_call) {
+        const int np = f32pc_np((int)c->ntaps);
+        HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+        float *tab = nullptr;                                    // (first what can fail without a trace: a refusal leaves the chain as it was)
+        if (int rc = dzalloc(c->ctx, (size_t)c->channels * 2 * np, &tab)) return rc;
+        // the cascade moves behind the kernel, in CMSIS order, with its state (the way msdr_chain_set_biquad_coeffs moves a cascade between
+        // the two places); a chain whose cascade runs there already keeps its stage object
+        if (c->h_bq_stages > 0 && !c->seq_bq) {
+            const std::vector<float> same = c->h_bq;
+            if (int rc = chain_set_biquad_coeffs_impl(c, same.data(), true)) { hipFree(tab); return rc; }
+        }
+        c->seq_forced = true;
+        c->d_pcf_taps = tab;
+        c->pc_np = np;
+        c->h_pcf_taps.assign((size_t)c->channels * 2 * np, 0.0f);
+        c->h_pc_own.assign(c->channels, 0);
+        for (uint32_t ch = 0; ch < c->channels; ch++) chain_pc_row_shared(c, ch);
+        c->pc_active = true;
+    }
+    for (uint32_t i = 0; i < count; i++) {
+        chain_pcf_row_from(c, first_channel + i, coeffs_i + (size_t)i * c->ntaps, coeffs_q + (size_t)i * c->ntaps);
+        c->h_pc_own[first_channel + i] = 1;
+    }
+    return first_call ? chain_pc_upload(c, 0, c->channels) : chain_pc_upload(c, first_channel, count);
+}
+
 extern "C" int msdr_chain_set_osc(msdr_chain *c, const void *osc_i, const void *osc_q)
 {
     if (!c || !osc_i || !osc_q) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
@@ -4406,6 +4566,10 @@ extern "C" int msdr_chain_set_node_coefficients_channels(msdr_chain *c, uint32_t
 extern "C" int msdr_chain_set_biquad_coeffs(msdr_chain *c, const float32_t *coeffs)
 {
     if (!c || !coeffs) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
+    return chain_set_biquad_coeffs_impl(c, coeffs, c->seq_forced);
+}
+static int chain_set_biquad_coeffs_impl(msdr_chain *c, const float32_t *coeffs, bool force_seq)
+{
     if (int rc = bind(c->ctx)) return rc;
     if (c->arith != MSDR_ARITH_F32) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the fp32 cascade belongs to F32 chains (Q15: msdr_chain_set_node_coefficients)");
     const int S = (int)c->h_bq_stages, ny = 2 * S + 2;
@@ -4434,7 +4598,7 @@ extern "C" int msdr_chain_set_biquad_coeffs(msdr_chain *c, const float32_t *coef
         }
     }
     // ---- the rebuilt chain ----
-    const bool new_seq = cascade_needs_cmsis_order(coeffs, S);
+    const bool new_seq = force_seq || cascade_needs_cmsis_order(coeffs, S);
     if (!new_seq && !br.ok_from) return fail(MSDR_STATUS_ARGUMENT_ERROR, "no block-parallel state reproduces the CMSIS state under the new coefficients");
     ChainCfgStore ed = c->store;
     ed.bq.assign(coeffs, coeffs + 5 * S);
@@ -4454,8 +4618,10 @@ extern "C" int msdr_chain_set_biquad_coeffs(msdr_chain *c, const float32_t *coef
     }
     msdr_biquad_df1_f32 *old_seq = c->seq_bq;          // (chain_rebuild would swap the old object in: the new one must stay)
     c->seq_bq = nullptr;
+    const bool was_forced = c->seq_forced;
+    if (force_seq) c->seq_forced = true;               // (chain_rebuild reads it: the cascade goes behind the kernel, now and at every later rebuild)
     const int rrc = chain_rebuild(c, ed, nullptr, floor_d, floor_sig);
-    if (rrc) { c->seq_bq = old_seq; return rrc; }
+    if (rrc) { c->seq_bq = old_seq; c->seq_forced = was_forced; return rrc; }
     if (old_seq) msdr_biquad_df1_f32_destroy(old_seq);
     if (hist.size() != (size_t)c->channels * c->hist_len) {      // (the history length follows the cascade's place: read the carried-over copy)
         hist.resize((size_t)c->channels * c->hist_len);

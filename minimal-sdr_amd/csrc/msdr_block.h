@@ -6,6 +6,7 @@
 //   msdr_q15_elementwise.hip  arm_mult_q15 / arm_add_q15 / arm_sub_q15 / arm_copy_q15 over a block batch: q15_elementwise_kernel
 //   msdr_biquad_pc.hip     AudioFilterBiquad with per-channel coefficients: biquad_teensy_pc_kernel
 //   msdr_chain_q15pc.hip   the Q15 chain / the arm_fir_fast_q15 stage with per-channel FIR coefficients: chain_q15pc_kernel
+//   msdr_chain_f32pc.hip   the fp32 chain / the arm_fir_f32 stage with per-channel FIR coefficients: chain_f32pc_kernel
 // Host-side geometry helpers (LDS sizes, table formats) live with the kernels' headers.  Every launcher returns the HIP error of its launch.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -44,4 +45,9 @@ hipError_t launch_biquad_teensy_pc(hipStream_t stream, int nodes, short *data, i
 // the number of compute units, fills p.nseg / p.seg_len / p.nw itself and reports the geometry.
 struct PcLaunch { unsigned grid, block; size_t lds_bytes; int cpw, nseg, tile; };
 hipError_t launch_chain_q15pc(hipStream_t stream, bool fir_only, int num_cus, PcParams p, PcLaunch *geo);
+// ---- msdr_chain_f32pc.hip ----
+// chain_f32pc_kernel<CPW, FIR_ONLY, FS4> (msdr_chain_f32pc.hiph).  The same choices as above (np a multiple of 4; 64 KB of LDS); FS4 is the
+// Fs/4 mixer's flavour (p.mixer), one stream and half the products.  time_segments as msdr_chain_config.time_segments: 0 = the launcher's
+// choice, 1 = never split, > 1 = that many (as far as the call has tiles).
+hipError_t launch_chain_f32pc(hipStream_t stream, bool fir_only, int num_cus, int time_segments, PcfParams p, PcLaunch *geo);
 }  // namespace msdr

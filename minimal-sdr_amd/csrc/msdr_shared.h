@@ -133,4 +133,26 @@ struct PcParams {
     int nw;                    // waves per workgroup
 };
 
+// chain_f32pc_kernel (msdr_chain_f32pc.hiph): the fp32 chain / the arm_fir_f32 stage with per-channel coefficients
+struct PcfParams {
+    const void *x;             // [channels][n] IF samples, int16 (FIR stage: float input)
+    float *out;                // [channels][n] audio before the cascade (FIR stage: output)
+    const void *hist_in;       // [channels][hist_len] raw history, oldest first: int16 (FIR stage: float)
+    long long n;
+    int channels;
+    int hist_len;
+    int np;                    // taps per row of the table: numTaps front-padded with zeros to a multiple of 4
+    const float *taps;         // [channels][2][np] (I row, Q row; CMSIS order) -- FIR stage: [channels][np]
+    const int *chan_mode;      // [channels] (unused by the FIR stage)
+    int mixer;                 // MSDR_MIXER_*
+    const void *osc;           // [osc_len] float2 pairs {osc_q ("cos"), osc_i ("sin")}
+    int osc_len;
+    int phase0;                // (absolute index of sample 0 of this call) mod osc_len (mod 4 for FS4)
+    float in_scale;
+    const struct OscHistory *osc_hist;     // oscillator tables in force before a live change, or null
+    int nseg;                  // time segments per channel group
+    long long seg_len;         // a multiple of the tile (8 * 64 / channels per wave)
+    int nw;                    // waves per workgroup
+};
+
 }  // namespace msdr

@@ -28,6 +28,7 @@ FLAVOUR_SSB_UNITS, FLAVOUR_ENV_UNITS, FLAVOUR_SSB_FOLD, FLAVOUR_ENV_FOLD = 0x1, 
 FLAVOUR_FULL_RATE, FLAVOUR_COMPACT, FLAVOUR_SHARED_IQ, FLAVOUR_AMTR = 0x10, 0x20, 0x40, 0x80
 FLAVOUR_BLOCK, FLAVOUR_VALU_FOLD, FLAVOUR_SEQ_CASCADE, FLAVOUR_SEGMENTED = 0x100, 0x200, 0x400, 0x800
 FLAVOUR_FOLD_PERIOD_SHIFT = 12
+FLAVOUR_TAPS_PC = 0x8000
 FE_DCBLOCK, FE_AMP, FE_AGC, FE_ALL = 1, 2, 4, 7
 
 STATUS_ARGUMENT_ERROR, STATUS_LENGTH_ERROR, STATUS_NO_DEVICE = -1, -2, -100
@@ -92,7 +93,9 @@ def load_library(path=None):
         for n, sig in (("msdr_chain_set_node_coefficients_channels", [_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _p]),
                        ("msdr_biquad_q15_set_coefficients_channels", [_p, C.c_uint32, C.c_uint32, C.c_uint32, _p]),
                        ("msdr_chain_set_taps_channels", [_p, C.c_uint32, C.c_uint32, _p, _p]),
-                       ("msdr_fir_q15_set_coeffs_channels", [_p, C.c_uint32, C.c_uint32, _p])):
+                       ("msdr_fir_q15_set_coeffs_channels", [_p, C.c_uint32, C.c_uint32, _p]),
+                       ("msdr_chain_set_taps_channels_f32", [_p, C.c_uint32, C.c_uint32, _p, _p]),
+                       ("msdr_fir_f32_set_coeffs_channels", [_p, C.c_uint32, C.c_uint32, _p])):
             if hasattr(_lib, n):
                 getattr(_lib, n).argtypes = sig
         _lib.msdr_chain_set_biquad_coeffs.argtypes = [_p, _p]
@@ -407,6 +410,11 @@ class FirF32(_Instance):
             raise ValueError("set_coeffs: %d taps given, the instance has %d" % (c.size, self.ntaps))
         _ck(self.ctx.lib.msdr_fir_f32_set_coeffs(self.h, _hp(c)))
 
+    def set_coeffs_channels(self, first_channel, coeffs):
+        """pCoeffs of channel first_channel + i only := coeffs[i]: coeffs float32 [count, numTaps], CMSIS order; state kept."""
+        c = _taps_per_channel("set_coeffs_channels", coeffs, self.ntaps, np.float32)
+        _ck(self.ctx.lib.msdr_fir_f32_set_coeffs_channels(self.h, C.c_uint32(first_channel), C.c_uint32(c.shape[0]), _hp(c)))
+
     def set_input_range(self, max_abs):
         _ck(self.ctx.lib.msdr_fir_f32_set_input_range(self.h, C.c_float(max_abs)))
 
@@ -456,8 +464,8 @@ def _coefs_per_channel(what, coefs):
     return c
 
 
-def _taps_per_channel(what, coeffs, ntaps):
-    c = np.ascontiguousarray(coeffs, np.int16)
+def _taps_per_channel(what, coeffs, ntaps, dtype=np.int16):
+    c = np.ascontiguousarray(coeffs, dtype)
     if c.ndim != 2 or c.shape[1] != ntaps:
         raise ValueError("%s: one row of %d taps per channel (numTaps is fixed at creation, as in CMSIS), shape %s given" % (what, ntaps, (c.shape,)))
     return c
@@ -740,6 +748,15 @@ class Chain(_Instance):
         if cq is not None and cq.shape != ci.shape:
             raise ValueError("set_taps_channels: coeffs_i %s and coeffs_q %s differ in shape" % ((ci.shape,), (cq.shape,)))
         _ck(self.ctx.lib.msdr_chain_set_taps_channels(self.h, C.c_uint32(first_channel), C.c_uint32(ci.shape[0]), _hp(ci), _hp(cq)))
+
+    def set_taps_channels_f32(self, first_channel, coeffs_i, coeffs_q=None):
+        """F32: channel first_channel + i gets FIR coefficients of its own, coeffs_i[i] / coeffs_q[i] (float32 [count, numTaps], CMSIS order);
+        coeffs_q = None: the same array behind both filters.  Every state kept; chain_f32pc_kernel from the first call on."""
+        ci = _taps_per_channel("set_taps_channels_f32", coeffs_i, self.ntaps, np.float32)
+        cq = None if coeffs_q is None else _taps_per_channel("set_taps_channels_f32", coeffs_q, self.ntaps, np.float32)
+        if cq is not None and cq.shape != ci.shape:
+            raise ValueError("set_taps_channels_f32: coeffs_i %s and coeffs_q %s differ in shape" % ((ci.shape,), (cq.shape,)))
+        _ck(self.ctx.lib.msdr_chain_set_taps_channels_f32(self.h, C.c_uint32(first_channel), C.c_uint32(ci.shape[0]), _hp(ci), _hp(cq)))
 
     def set_osc(self, osc_i, osc_q):
         tdt = np.float32 if self.arith == ARITH_F32 else np.int16
