@@ -216,6 +216,17 @@ int msdr_biquad_df1_f32_reset(msdr_biquad_df1_f32 *S);
  * cascade's conditioning asks for it (msdr_biquad_df1_f32_cascade_info).  Synchronises the stream.  ARGUMENT_ERROR if the old
  * cascade's state cannot be expressed as a CMSIS state (a later stage's numerator shares a root with an earlier stage's denominator). */
 int msdr_biquad_df1_f32_set_coeffs(msdr_biquad_df1_f32 *S, const float32_t *pCoeffs);
+/* The same for channels first_channel .. first_channel + count - 1 only, each with an array of its own: pCoeffs is a HOST array
+ * [count][5 * numStages] -- a bank of arm_biquad_casd_df1_inst_f32 whose pCoeffs point at different arrays (every receiver its own notch).
+ * Per-channel coefficients run in CMSIS order only (biquad_df1_seq_pc_kernel: one lane per channel, every lane its own coefficients), where
+ * the state is pState itself and does not depend on the coefficients: the call writes the named rows and leaves every state alone.  At the
+ * FIRST call an instance that runs block-parallel is moved to the CMSIS order with its state (the one refusal of
+ * msdr_biquad_df1_f32_set_coeffs applies: ARGUMENT_ERROR, nothing changed), and every channel starts from the shared coefficients; the
+ * instance stays per-channel for the rest of its life, and msdr_biquad_df1_f32_set_coeffs then writes ALL rows in place (state kept, no
+ * change of kernel).  Long blocks of few channels are still split into time segments: the warm-up follows the LARGEST pole radius over all
+ * rows, and a row with a pole on the unit circle (radius >= 0.99999) or with no pole at all keeps the call in one piece.  count == 0 does
+ * nothing; a range past `channels`, a NULL array and numStages == 0 are MSDR_STATUS_ARGUMENT_ERROR, nothing changed.  Synchronises the stream. */
+int msdr_biquad_df1_f32_set_coeffs_channels(msdr_biquad_df1_f32 *S, uint32_t first_channel, uint32_t count, const float32_t *pCoeffs);
 /* The state as CMSIS keeps it: pState[4 * numStages] of one channel (synchronises the stream). */
 int msdr_biquad_df1_f32_get_cmsis_state(msdr_biquad_df1_f32 *S, uint32_t channel, float32_t *pState);
 int msdr_biquad_df1_f32_destroy(msdr_biquad_df1_f32 *S);
@@ -523,6 +534,21 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  * msdr_chain_set_biquad_coeffs (F32): all 5 * num_biquad_stages coefficients of the arm_biquad_cascade_df1_f32 stage, CMSIS
  *   semantics (the filter carries on from the pState arm_biquad_cascade_df1_f32 would hold; see msdr_biquad_df1_f32_set_coeffs).
  *   The number of stages is fixed at creation, as numStages is in CMSIS.
+ * msdr_chain_set_biquad_coeffs_channels (F32): the same on channels first_channel .. first_channel + count - 1 only, biquad_coeffs a HOST
+ *   array [count][5 * num_biquad_stages] (msdr_biquad_df1_f32_set_coeffs_channels): every receiver of the bank its own notch, as tune()
+ *   re-programs biquad2_dac (Minimal-SDR.ino:356).  Per-channel coefficients run in CMSIS order behind the demodulator kernel
+ *   (biquad_df1_seq_pc_kernel; msdr_chain_get_info().kernel ends in its name, flavour carries MSDR_FLAVOUR_SEQ_CASCADE and
+ *   MSDR_FLAVOUR_CASCADE_PC): at the first call a cascade that ran inside the kernel is moved there with its state, the way
+ *   msdr_chain_set_taps_channels_f32 moves one (and with that call's one refusal), and stays there for the rest of the chain's life; the
+ *   demodulator kernel is whatever the chain runs with its cascade behind it -- the uniform matrix-core kernels, or chain_f32pc_kernel on a
+ *   chain that also has per-channel taps (the two calls combine in either order).  From then on a call writes rows and nothing else: every
+ *   state is kept, the channel hears its new filter from its next sample on.  The rows survive msdr_chain_set_taps / set_taps_channels_f32 /
+ *   set_mode / set_osc / init_fir and msdr_chain_reset (which clears the state only); msdr_chain_set_biquad_coeffs afterwards writes EVERY
+ *   channel's row and the chain stays in per-channel mode.  count == 0 does nothing; a Q15 chain, a chain without a cascade, a range past
+ *   `channels`, a NULL array and a coefficient that is not finite are MSDR_STATUS_ARGUMENT_ERROR, nothing changed.  PLL and LMS channels run
+ *   a post cascade of their own with the chain's shared coefficients and are out of this call's scope: it is refused (ARGUMENT_ERROR, nothing
+ *   changed) on a chain created with MSDR_CHAIN_SYNCAM_PLL and on a chain with any LMS channel on, and on a chain in per-channel-cascade mode
+ *   msdr_chain_set_anr with any channel on is refused.  msdr_chain_graph_create is refused as for every cascade behind the kernel.
  * msdr_chain_set_osc: new contents for the NCO tables (same osc_len) -- AudioEffectFreqConv reads the global Osc_I_buffer_i /
  *   Osc_Q_buffer_i on every update() (freq_conv.h:33-34, freq_conv.cpp:70-103), so a sketch that rewrites them retunes the mixer
  *   without touching anything else; the position in the table carries on.  The samples already in the FIR history were mixed with the
@@ -537,6 +563,8 @@ int msdr_chain_set_node_coefficients(msdr_chain *chain, uint32_t node, uint32_t 
 int msdr_chain_set_node_coefficients_channels(msdr_chain *chain, uint32_t node, uint32_t first_channel,
                                               uint32_t count, uint32_t stage, const int32_t *coef);
 int msdr_chain_set_biquad_coeffs(msdr_chain *chain, const float32_t *biquad_coeffs);
+int msdr_chain_set_biquad_coeffs_channels(msdr_chain *chain, uint32_t first_channel, uint32_t count,
+                                          const float32_t *biquad_coeffs);
 int msdr_chain_set_osc(msdr_chain *chain, const void *osc_i, const void *osc_q);
 /* ANR_on per channel (host array of `channels` values, or NULL: anr_on_all for every channel); the LMS filter then runs between
  * the demodulator and the biquad nodes / cascade (Minimal-SDR.ino:702-770).  Its state is created on first use and cleared by
@@ -577,6 +605,9 @@ typedef struct {
 /* One more bit of `flavour`, an enumerator beside the macros above (their list is mirrored one for one, and counted, by the Python binding's ABI test):
  * chain_f32pc_kernel ran -- per-channel FIR coefficients, msdr_chain_set_taps_channels_f32. */
 enum { MSDR_FLAVOUR_TAPS_PC = 0x8000u };
+/* And another: the cascade behind the main kernel ran with per-channel coefficients -- biquad_df1_seq_pc_kernel, msdr_chain_set_biquad_coeffs_channels
+ * (always beside MSDR_FLAVOUR_SEQ_CASCADE). */
+enum { MSDR_FLAVOUR_CASCADE_PC = 0x10000u };
 int msdr_chain_get_info(msdr_chain *chain, msdr_chain_info *info);
 /* Measurement aid (bench.py): when enabled every msdr_chain_process() brackets its MAIN kernel with
  * HIP events on the context's stream; get_kernel_time synchronises and returns the accumulated

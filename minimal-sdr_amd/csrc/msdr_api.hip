@@ -1365,6 +1365,12 @@ struct msdr_biquad_df1_f32 {
     float *d_seq_scratch; // sequential, few channels x long block: the segments' warm-up samples (biquad_seqseg_gather_kernel)
     size_t seq_scratch_floats;
     std::vector<float> h_coeffs;      // 5 x stages, as given (msdr_biquad_df1_f32_set_coeffs converts the state between the two cascades)
+    bool per_channel;     // set by the first msdr_biquad_df1_f32_set_coeffs_channels, for the instance's life (always with `sequential`): the rows of
+                          // d_pc_coeffs may differ from channel to channel, so process() runs biquad_df1_seq_pc_kernel (msdr_biquad_df1_pc.hiph)
+    float *d_pc_coeffs;   // [channels][kSbqTabFloats]: every channel's 5 x stages coefficients, zero padded
+    std::vector<float> h_pc_coeffs;   // its host copy
+    std::vector<double> h_pc_radius;  // every row's largest pole radius (time segments: the warm-up follows the largest of them)
+    double pc_radius_max, pc_radius_min;
 };
 
 extern "C" int msdr_biquad_df1_f32_cascade_info(uint8_t numStages, const float32_t *pCoeffs, double *kappa, double *fp32_noise, int *cmsis_order)
@@ -1392,8 +1398,9 @@ extern "C" int msdr_biquad_df1_f32_create(msdr_ctx *ctx, uint8_t numStages, cons
     S->ctx = ctx; S->channels = channels; S->stages = numStages; S->d_tabs = nullptr; S->d_state = nullptr; S->d_state_alt = nullptr;
     S->pole_radius = numStages ? max_pole_radius(pCoeffs, (int)numStages) : 0.0;
     S->d_coeffs = nullptr; S->d_seq_scratch = nullptr; S->seq_scratch_floats = 0;
+    S->per_channel = false; S->d_pc_coeffs = nullptr; S->pc_radius_max = S->pc_radius_min = 0.0;
     S->sequential = numStages > 0 && (g_biquad_force_sequential || cascade_needs_cmsis_order(pCoeffs, (int)numStages));
-    S->seq_segments = true;
+    S->seq_segments = getenv("MSDR_BIQUAD_SEQ_NO_SEGMENTS") == nullptr;
     if (numStages) S->h_coeffs.assign(pCoeffs, pCoeffs + 5 * numStages);
     if (S->sequential) {
         std::vector<float> cf(pCoeffs, pCoeffs + 5 * numStages);
@@ -1422,8 +1429,12 @@ extern "C" int msdr_biquad_df1_f32_process(msdr_biquad_df1_f32 *S, const float32
         // few channels and a long block: one lane per (channel, time segment), each segment warmed up over the samples in front of
         // it (copied aside first, so in place stays allowed); the warm-up length follows from the slowest pole (1e-10 of the state)
         long long nseg = 1, seg_len = blockSize, warm = 0;
-        if (S->channels < 8192 && S->pole_radius > 0.0 && S->pole_radius < 0.99999 && S->seq_segments) {
-            warm = ((long long)std::ceil(std::log(1e-10) / std::log(S->pole_radius)) + 64 * S->stages + 3) & ~3LL;
+        // (per-channel coefficients: the warm-up follows the LARGEST radius over all rows; one row with a pole on the unit circle, or with
+        //  none, and the call is not split)
+        const double radius = S->per_channel ? S->pc_radius_max : S->pole_radius;
+        const bool radius_ok = S->per_channel ? (S->pc_radius_min > 0.0 && S->pc_radius_max < 0.99999) : (S->pole_radius > 0.0 && S->pole_radius < 0.99999);
+        if (S->channels < 8192 && radius_ok && S->seq_segments) {
+            warm = ((long long)std::ceil(std::log(1e-10) / std::log(radius)) + 64 * S->stages + 3) & ~3LL;
             const long long min_len = std::max<long long>(8 * warm, 1024);
             const long long want = (65536 + S->channels - 1) / S->channels;
             nseg = std::max<long long>(1, std::min(want, (long long)blockSize / min_len));
@@ -1441,14 +1452,31 @@ extern "C" int msdr_biquad_df1_f32_process(msdr_biquad_df1_f32 *S, const float32
             hipLaunchKernelGGL(biquad_seqseg_gather_kernel, dim3((unsigned)std::min<size_t>((need + 255) / 256, 65536)), dim3(256), 0, S->ctx->stream,
                                d_src, S->d_seq_scratch, (long long)blockSize, (int)S->channels, (int)nseg, seg_len, (int)warm);
             if (int rc = launch_check("biquad_seqseg_gather_kernel")) return rc;
-            hipLaunchKernelGGL(biquad_df1_seqseg_kernel, dim3((unsigned)(((long long)S->channels * nseg + 63) / 64)), dim3(64), 0, S->ctx->stream,
-                               d_src, d_dst, (long long)blockSize, (int)S->channels, (int)S->stages, (const float *)S->d_coeffs,
-                               (const float *)S->d_state, S->d_state_alt, (int)nseg, seg_len, (int)warm, (const float *)S->d_seq_scratch);
+            if (S->per_channel) {
+                { KernelTimer kt(S->ctx);
+                  if (launch_biquad_df1_seq_pc(S->ctx->stream, (int)S->stages, d_src, d_dst, (long long)blockSize, (int)S->channels, (const float *)S->d_pc_coeffs,
+                                               (const float *)S->d_state, S->d_state_alt, (int)nseg, seg_len, (int)warm, (const float *)S->d_seq_scratch) != hipSuccess)
+                      return fail(MSDR_STATUS_HIP_ERROR, "biquad_df1_seq_pc_kernel launch failed"); }
+                std::swap(S->d_state, S->d_state_alt);
+                return launch_check("biquad_df1_seq_pc_kernel");
+            }
+            { KernelTimer kt(S->ctx);
+              hipLaunchKernelGGL(biquad_df1_seqseg_kernel, dim3((unsigned)(((long long)S->channels * nseg + 63) / 64)), dim3(64), 0, S->ctx->stream,
+                                 d_src, d_dst, (long long)blockSize, (int)S->channels, (int)S->stages, (const float *)S->d_coeffs,
+                                 (const float *)S->d_state, S->d_state_alt, (int)nseg, seg_len, (int)warm, (const float *)S->d_seq_scratch); }
             std::swap(S->d_state, S->d_state_alt);
             return launch_check("biquad_df1_seqseg_kernel");
         }
-        hipLaunchKernelGGL(biquad_df1_seq_kernel, dim3((S->channels + 63) / 64), dim3(64), 0, S->ctx->stream, d_src, d_dst, (long long)blockSize,
-                           (int)S->channels, (int)S->stages, (const float *)S->d_coeffs, S->d_state);
+        if (S->per_channel) {
+            { KernelTimer kt(S->ctx);
+              if (launch_biquad_df1_seq_pc(S->ctx->stream, (int)S->stages, d_src, d_dst, (long long)blockSize, (int)S->channels, (const float *)S->d_pc_coeffs,
+                                           (const float *)S->d_state, S->d_state, 1, (long long)blockSize, 0, nullptr) != hipSuccess)
+                  return fail(MSDR_STATUS_HIP_ERROR, "biquad_df1_seq_pc_kernel launch failed"); }
+            return launch_check("biquad_df1_seq_pc_kernel");
+        }
+        { KernelTimer kt(S->ctx);
+          hipLaunchKernelGGL(biquad_df1_seq_kernel, dim3((S->channels + 63) / 64), dim3(64), 0, S->ctx->stream, d_src, d_dst, (long long)blockSize,
+                             (int)S->channels, (int)S->stages, (const float *)S->d_coeffs, S->d_state); }
         return launch_check("biquad_df1_seq_kernel");
     }
     // time segments for long blocks of few channels (never in place: a segment's warm-up reads its predecessor's input)
@@ -1483,7 +1511,7 @@ extern "C" int msdr_biquad_df1_f32_destroy(msdr_biquad_df1_f32 *S)
     if (!S) return 0;
     if (int rc = bind(S->ctx)) return rc;
     (void)hipStreamSynchronize(S->ctx->stream);
-    hipFree(S->d_tabs); hipFree(S->d_state); hipFree(S->d_state_alt); hipFree(S->d_coeffs); hipFree(S->d_seq_scratch);
+    hipFree(S->d_tabs); hipFree(S->d_state); hipFree(S->d_state_alt); hipFree(S->d_coeffs); hipFree(S->d_seq_scratch); hipFree(S->d_pc_coeffs);
     delete S;
     return 0;
 }
@@ -1569,6 +1597,18 @@ extern "C" int msdr_biquad_df1_f32_set_coeffs(msdr_biquad_df1_f32 *S, const floa
     if (!S || (S->stages && !pCoeffs)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
     if (int rc = bind(S->ctx)) return rc;
     if (S->stages == 0) return 0;
+    if (S->per_channel) {
+        // the instance runs biquad_df1_seq_pc_kernel for life: set_coeffs keeps writing ALL channels, i.e. every row of the table; the state is
+        // pState itself and stays as it is (as msdr_fir_f32_set_coeffs does on a per-channel FIR)
+        HIP_TRY(hipStreamSynchronize(S->ctx->stream));
+        for (uint32_t ch = 0; ch < S->channels; ch++) memcpy(S->h_pc_coeffs.data() + (size_t)ch * kSbqTabFloats, pCoeffs, 5 * S->stages * sizeof(float));
+        HIP_TRY(hipMemcpy(S->d_pc_coeffs, S->h_pc_coeffs.data(), S->h_pc_coeffs.size() * sizeof(float), hipMemcpyHostToDevice));
+        S->h_coeffs.assign(pCoeffs, pCoeffs + 5 * S->stages);
+        S->pole_radius = max_pole_radius(pCoeffs, (int)S->stages);
+        S->h_pc_radius.assign(S->channels, S->pole_radius);
+        S->pc_radius_max = S->pc_radius_min = S->pole_radius;
+        return 0;
+    }
     cstate::Bridge br;
     br.build(S->h_coeffs.data(), pCoeffs, (int)S->stages);
     if (!S->sequential && !br.ok_to)
@@ -1582,6 +1622,53 @@ extern "C" int msdr_biquad_df1_f32_set_coeffs(msdr_biquad_df1_f32 *S, const floa
     if (int rc = biquad_df1_write_cmsis(n, br, Y, D)) { msdr_biquad_df1_f32_destroy(n); return rc; }
     std::swap(*S, *n);
     return msdr_biquad_df1_f32_destroy(n);
+}
+// arm_biquad_cascade_df1_f32 over a bank whose instances each point at a coefficient array of their own (arm_biquad_cascade_df1_init_f32 keeps
+// the pointer): CMSIS order only, where the state is pState and does not depend on the coefficients -- a row write and nothing else
+extern "C" int msdr_biquad_df1_f32_set_coeffs_channels(msdr_biquad_df1_f32 *S, uint32_t first_channel, uint32_t count, const float32_t *pCoeffs)
+{
+    if (!S) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null instance");
+    if (int rc = bind(S->ctx)) return rc;
+    if (count == 0) return 0;
+    if (!pCoeffs) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null coefficient array");
+    if (S->stages == 0) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this instance was created with numStages 0: no coefficients to set");
+    if (first_channel >= S->channels || count > S->channels - first_channel)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "channels %u .. %llu of %u", first_channel, (unsigned long long)first_channel + count - 1, S->channels);
+    HIP_TRY(hipStreamSynchronize(S->ctx->stream));
+    if (!S->per_channel) {
+        if (!S->sequential) {          // a block-parallel instance moves to the CMSIS order with its state, the way msdr_biquad_df1_f32_set_coeffs moves one
+            cstate::Bridge br;
+            br.build(S->h_coeffs.data(), S->h_coeffs.data(), (int)S->stages);
+            if (!br.ok_to)
+                return fail(MSDR_STATUS_ARGUMENT_ERROR, "the running cascade's block-parallel state has no unique CMSIS state (a numerator shares a root with an earlier denominator); nothing changed");
+            std::vector<double> Y, D;
+            if (int rc = biquad_df1_read_cmsis(S, br, Y, D)) return rc;
+            msdr_biquad_df1_f32 *n = nullptr;
+            g_biquad_force_sequential = true;
+            const int rcc = msdr_biquad_df1_f32_create(S->ctx, (uint8_t)S->stages, S->h_coeffs.data(), S->channels, &n);
+            g_biquad_force_sequential = false;
+            if (rcc) return rcc;
+            n->seq_segments = S->seq_segments;
+            if (int rc = biquad_df1_write_cmsis(n, br, Y, D)) { msdr_biquad_df1_f32_destroy(n); return rc; }
+            std::swap(*S, *n);
+            if (int rc = msdr_biquad_df1_f32_destroy(n)) return rc;
+        }
+        std::vector<float> t((size_t)S->channels * kSbqTabFloats, 0.0f);      // every channel starts from the shared coefficients
+        for (uint32_t ch = 0; ch < S->channels; ch++) memcpy(t.data() + (size_t)ch * kSbqTabFloats, S->h_coeffs.data(), 5 * S->stages * sizeof(float));
+        if (int rc = upload(S->ctx, t, &S->d_pc_coeffs)) return rc;
+        S->h_pc_coeffs.swap(t);
+        S->h_pc_radius.assign(S->channels, S->pole_radius);
+        S->per_channel = true;
+    }
+    for (uint32_t i = 0; i < count; i++) {
+        memcpy(S->h_pc_coeffs.data() + (size_t)(first_channel + i) * kSbqTabFloats, pCoeffs + (size_t)i * 5 * S->stages, 5 * S->stages * sizeof(float));
+        S->h_pc_radius[first_channel + i] = max_pole_radius(pCoeffs + (size_t)i * 5 * S->stages, (int)S->stages);
+    }
+    S->pc_radius_max = *std::max_element(S->h_pc_radius.begin(), S->h_pc_radius.end());
+    S->pc_radius_min = *std::min_element(S->h_pc_radius.begin(), S->h_pc_radius.end());
+    HIP_TRY(hipMemcpy(S->d_pc_coeffs + (size_t)first_channel * kSbqTabFloats, S->h_pc_coeffs.data() + (size_t)first_channel * kSbqTabFloats,
+                      (size_t)count * kSbqTabFloats * sizeof(float), hipMemcpyHostToDevice));
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3937,7 +4024,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     if (e0) { HIP_TRY(hipEventRecord(e1, c->ctx->stream)); c->events.emplace_back(e0, e1); }
 
     if (c->seq_bq)             // F32, ill-conditioned cascade: arm_biquad_cascade_df1_f32 in CMSIS order, in place on the audio
-        { if (int rc = msdr_biquad_df1_f32_process(c->seq_bq, (const float *)fout, (float *)fout, (uint32_t)n_samples)) return rc; flavour |= MSDR_FLAVOUR_SEQ_CASCADE; }
+        { if (int rc = msdr_biquad_df1_f32_process(c->seq_bq, (const float *)fout, (float *)fout, (uint32_t)n_samples)) return rc; flavour |= MSDR_FLAVOUR_SEQ_CASCADE | (c->seq_bq->per_channel ? (uint32_t)MSDR_FLAVOUR_CASCADE_PC : 0u); }
 
     if (pll_active)            // SYNCAM channels: I (in d_audio) and Q (scratch) -> PLL demodulator -> audio, before the biquad nodes
         if (int rc = msdr_syncam_q15(c->pll, c->d_mode, (const q15_t *)d_audio, c->d_pll_q, (q15_t *)d_audio, (uint32_t)n_samples)) return rc;
@@ -4009,7 +4096,9 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
             if (int rc = chain_leave_generic(c)) return rc;
     }
 
-    snprintf(c->info.kernel, sizeof c->info.kernel, "%s%s", kname, !c->seq_bq ? "" : c->seq_bq->sequential ? " + biquad_df1_seq_kernel" : " + biquad_df1_kernel");
+    // (the cascade's kernel is always named in full: a main kernel's name that leaves no room for it in info.kernel is cut short instead)
+    const char *bq_name = !c->seq_bq ? "" : c->seq_bq->per_channel ? " + biquad_df1_seq_pc_kernel" : c->seq_bq->sequential ? " + biquad_df1_seq_kernel" : " + biquad_df1_kernel";
+    snprintf(c->info.kernel, sizeof c->info.kernel, "%.*s%s", (int)(sizeof c->info.kernel - 1 - strlen(bq_name)), kname, bq_name);
     c->info.grid = grid; c->info.block = block; c->info.lds_bytes = (uint32_t)lds_used;
     c->info.env_scan = env_scan; c->info.flavour = f32 ? flavour : 0u;
     c->info.time_segments = (uint32_t)nseg; c->info.warmup = (uint32_t)p.warm; c->info.tile = (uint32_t)((use_pc || use_pcf) ? pc_tile : kTile);
@@ -4575,6 +4664,12 @@ static int chain_set_biquad_coeffs_impl(msdr_chain *c, const float32_t *coeffs, 
     const int S = (int)c->h_bq_stages, ny = 2 * S + 2;
     if (S == 0) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain was created without a biquad cascade (numStages is fixed at creation, as in CMSIS)");
     for (int k = 0; k < 5 * S; k++) if (!std::isfinite(coeffs[k])) return fail(MSDR_STATUS_ARGUMENT_ERROR, "coefficient %d is not finite", k);
+    if (c->seq_bq && c->seq_bq->per_channel) {
+        // per-channel cascade coefficients: the chain stays in that mode, every channel's row is written, the state (pState itself) stays
+        if (int rc = msdr_biquad_df1_f32_set_coeffs(c->seq_bq, coeffs)) return rc;
+        c->store.bq.assign(coeffs, coeffs + 5 * S); c->h_bq.assign(coeffs, coeffs + 5 * S);      // (what a rebuild's throw-away stage object is made from)
+        return 0;
+    }
     cstate::Bridge br;
     br.build(c->h_bq.data(), coeffs, S);
     HIP_TRY(hipStreamSynchronize(c->ctx->stream));
@@ -4649,6 +4744,34 @@ static int chain_set_biquad_coeffs_impl(msdr_chain *c, const float32_t *coeffs, 
     return 0;
 }
 
+// tune() re-programming the notch of ONE receiver of the bank: rows of the cascade's per-channel coefficient table rewritten under the running
+// stream.  CMSIS order only (behind the demodulator kernel), where the state is pState and a coefficient change is a row write.
+extern "C" int msdr_chain_set_biquad_coeffs_channels(msdr_chain *c, uint32_t first_channel, uint32_t count, const float32_t *coeffs)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (int rc = bind(c->ctx)) return rc;
+    if (c->arith != MSDR_ARITH_F32)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "the fp32 cascade belongs to F32 chains (Q15: msdr_chain_set_node_coefficients_channels)");
+    const int S = (int)c->h_bq_stages;
+    if (S == 0) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain was created without a biquad cascade (numStages is fixed at creation, as in CMSIS)");
+    if (c->f32_pll) return fail(MSDR_STATUS_ARGUMENT_ERROR, "per-channel cascade coefficients: not on a chain created with MSDR_CHAIN_SYNCAM_PLL (its PLL channels run a post cascade of their own); nothing changed");
+    for (int v : c->h_anr) if (v > 0) return fail(MSDR_STATUS_ARGUMENT_ERROR, "per-channel cascade coefficients: not while an LMS channel is on (such channels run a post cascade of their own); nothing changed");
+    if (count == 0) return 0;
+    if (!coeffs) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null coefficient array");
+    if (first_channel >= c->channels || count > c->channels - first_channel)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "channels %u .. %llu of %u", first_channel, (unsigned long long)first_channel + count - 1, c->channels);
+    for (size_t k = 0; k < (size_t)count * 5 * S; k++) if (!std::isfinite(coeffs[k])) return fail(MSDR_STATUS_ARGUMENT_ERROR, "coefficient %zu is not finite", k);
+    if (!c->seq_bq) {
+        // the cascade moves behind the kernel, in CMSIS order, with its state (as msdr_chain_set_taps_channels_f32 moves it, with that call's refusal)
+        const std::vector<float> same = c->h_bq;
+        if (int rc = chain_set_biquad_coeffs_impl(c, same.data(), true)) return rc;
+        if (!c->seq_bq) return fail(MSDR_STATUS_ARGUMENT_ERROR, "internal: the cascade did not move behind the kernel");
+    }
+    if (int rc = msdr_biquad_df1_f32_set_coeffs_channels(c->seq_bq, first_channel, count, coeffs)) return rc;
+    c->seq_forced = true;                                        // every rebuild keeps the cascade behind the kernel (chain_rebuild hands the stage object over)
+    return 0;
+}
+
 extern "C" int msdr_chain_set_anr(msdr_chain *c, const int32_t *anr_on, int32_t anr_on_all)
 {
     if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
@@ -4656,6 +4779,11 @@ extern "C" int msdr_chain_set_anr(msdr_chain *c, const int32_t *anr_on, int32_t 
     if (c->arith != MSDR_ARITH_Q15) {
         // fp32 chain: the float flavour of the filter, between demodulator and cascade (chain_post_run)
         if (c->seq_bq && !c->h_bq_stages) return fail(MSDR_STATUS_ARGUMENT_ERROR, "internal: cascade coefficients not kept");
+        if (c->seq_bq && c->seq_bq->per_channel) {               // (LMS channels run a post cascade with the chain's uniform coefficients)
+            bool any = anr_on ? false : anr_on_all > 0;
+            if (anr_on) for (uint32_t ch = 0; ch < c->channels; ch++) any = any || anr_on[ch] > 0;
+            if (any) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has per-channel cascade coefficients: no LMS channels (they run a post cascade of their own); nothing changed");
+        }
         c->h_anr.assign(c->channels, anr_on ? 0 : (int)anr_on_all);
         if (anr_on) for (uint32_t ch = 0; ch < c->channels; ch++) c->h_anr[ch] = (int)anr_on[ch];
         for (int &v : c->h_anr) if (v < 0) v = 0;

@@ -7,6 +7,7 @@
 //   msdr_biquad_pc.hip     AudioFilterBiquad with per-channel coefficients: biquad_teensy_pc_kernel
 //   msdr_chain_q15pc.hip   the Q15 chain / the arm_fir_fast_q15 stage with per-channel FIR coefficients: chain_q15pc_kernel
 //   msdr_chain_f32pc.hip   the fp32 chain / the arm_fir_f32 stage with per-channel FIR coefficients: chain_f32pc_kernel
+//   msdr_biquad_df1_pc.hip arm_biquad_cascade_df1_f32 in CMSIS order with per-channel coefficients: biquad_df1_seq_pc_kernel
 // Host-side geometry helpers (LDS sizes, table formats) live with the kernels' headers.  Every launcher returns the HIP error of its launch.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -50,4 +51,12 @@ hipError_t launch_chain_q15pc(hipStream_t stream, bool fir_only, int num_cus, Pc
 // Fs/4 mixer's flavour (p.mixer), one stream and half the products.  time_segments as msdr_chain_config.time_segments: 0 = the launcher's
 // choice, 1 = never split, > 1 = that many (as far as the call has tiles).
 hipError_t launch_chain_f32pc(hipStream_t stream, bool fir_only, int num_cus, int time_segments, PcfParams p, PcLaunch *geo);
+// ---- msdr_biquad_df1_pc.hip ----
+// biquad_df1_seq_pc_kernel<S, SEG> (msdr_biquad_df1_pc.hiph): stages = S = 1 .. 4 sections in CMSIS order on data [channels][n] (y may be x), every
+// channel with the 5 S coefficients of its own row of tab ([channels][20] floats).  nseg = 1: state_in may be state_out, seg_len / warm / scratch
+// unused.  nseg > 1 (SEG): segments of seg_len samples (a multiple of 4), each warmed up over the `warm` samples biquad_seqseg_gather_kernel
+// copied to scratch ([channels][nseg][warm]) beforehand; state_out is another buffer than state_in.
+constexpr int kSbqTabFloats = 5 * kMaxStages;      // one channel's row of the coefficient table (80 bytes: rows stay 16-byte aligned)
+hipError_t launch_biquad_df1_seq_pc(hipStream_t stream, int stages, const float *x, float *y, long long n, int channels, const float *tab,
+                                    const float *state_in, float *state_out, int nseg, long long seg_len, int warm, const float *scratch);
 }  // namespace msdr

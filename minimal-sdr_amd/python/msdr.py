@@ -29,6 +29,7 @@ FLAVOUR_FULL_RATE, FLAVOUR_COMPACT, FLAVOUR_SHARED_IQ, FLAVOUR_AMTR = 0x10, 0x20
 FLAVOUR_BLOCK, FLAVOUR_VALU_FOLD, FLAVOUR_SEQ_CASCADE, FLAVOUR_SEGMENTED = 0x100, 0x200, 0x400, 0x800
 FLAVOUR_FOLD_PERIOD_SHIFT = 12
 FLAVOUR_TAPS_PC = 0x8000
+FLAVOUR_CASCADE_PC = 0x10000
 FE_DCBLOCK, FE_AMP, FE_AGC, FE_ALL = 1, 2, 4, 7
 
 STATUS_ARGUMENT_ERROR, STATUS_LENGTH_ERROR, STATUS_NO_DEVICE = -1, -2, -100
@@ -95,7 +96,9 @@ def load_library(path=None):
                        ("msdr_chain_set_taps_channels", [_p, C.c_uint32, C.c_uint32, _p, _p]),
                        ("msdr_fir_q15_set_coeffs_channels", [_p, C.c_uint32, C.c_uint32, _p]),
                        ("msdr_chain_set_taps_channels_f32", [_p, C.c_uint32, C.c_uint32, _p, _p]),
-                       ("msdr_fir_f32_set_coeffs_channels", [_p, C.c_uint32, C.c_uint32, _p])):
+                       ("msdr_fir_f32_set_coeffs_channels", [_p, C.c_uint32, C.c_uint32, _p]),
+                       ("msdr_chain_set_biquad_coeffs_channels", [_p, C.c_uint32, C.c_uint32, _p]),
+                       ("msdr_biquad_df1_f32_set_coeffs_channels", [_p, C.c_uint32, C.c_uint32, _p])):
             if hasattr(_lib, n):
                 getattr(_lib, n).argtypes = sig
         _lib.msdr_chain_set_biquad_coeffs.argtypes = [_p, _p]
@@ -451,6 +454,11 @@ class BiquadDf1F32(_Instance):
             raise ValueError("set_coeffs: %d values given, the cascade has %d stages x 5" % (c.size, self.stages))
         _ck(self.ctx.lib.msdr_biquad_df1_f32_set_coeffs(self.h, _hp(c)))
 
+    def set_coeffs_channels(self, first_channel, coeffs):
+        """pCoeffs of channel first_channel + i only := coeffs[i]: coeffs float32 [count, stages, 5] or [count, 5 * stages]; state kept (CMSIS order)."""
+        c = _cascade_per_channel("set_coeffs_channels", coeffs, self.stages)
+        _ck(self.ctx.lib.msdr_biquad_df1_f32_set_coeffs_channels(self.h, C.c_uint32(first_channel), C.c_uint32(c.shape[0]), _hp(c)))
+
     def cmsis_state(self, channel, stages):
         out = np.zeros(4 * stages, np.float32)
         _ck(self.ctx.lib.msdr_biquad_df1_f32_get_cmsis_state(self.h, C.c_uint32(channel), _hp(out)))
@@ -462,6 +470,13 @@ def _coefs_per_channel(what, coefs):
     if c.ndim != 2 or c.shape[1] != 5:
         raise ValueError("%s: one row of 5 words (b0, b1, b2, a1, a2) per channel, shape %s given" % (what, (c.shape,)))
     return c
+
+
+def _cascade_per_channel(what, coeffs, stages):
+    c = np.ascontiguousarray(coeffs, np.float32)
+    if stages < 1 or not ((c.ndim == 3 and c.shape[1:] == (stages, 5)) or (c.ndim == 2 and c.shape[1] == 5 * stages)):
+        raise ValueError("%s: one row of %d stages x 5 coefficients per channel (numStages is fixed at creation, as in CMSIS), shape %s given" % (what, stages, (c.shape,)))
+    return c.reshape(c.shape[0], 5 * stages)
 
 
 def _taps_per_channel(what, coeffs, ntaps, dtype=np.int16):
@@ -782,6 +797,12 @@ class Chain(_Instance):
         if self.stages and c.size != 5 * self.stages:
             raise ValueError("set_biquad_coeffs: %d values given, the chain's cascade has %d stages x 5" % (c.size, self.stages))
         _ck(self.ctx.lib.msdr_chain_set_biquad_coeffs(self.h, _hp(c)))
+
+    def set_biquad_coeffs_channels(self, first_channel, coeffs):
+        """F32: channel first_channel + i gets cascade coefficients of its own, coeffs[i] (float32 [count, stages, 5] or [count, 5 * stages]);
+        every state kept; the cascade runs in CMSIS order behind the demodulator kernel (biquad_df1_seq_pc_kernel) from the first call on."""
+        c = _cascade_per_channel("set_biquad_coeffs_channels", coeffs, self.stages)
+        _ck(self.ctx.lib.msdr_chain_set_biquad_coeffs_channels(self.h, C.c_uint32(first_channel), C.c_uint32(c.shape[0]), _hp(c)))
 
     def info(self):
         i = ChainInfo()
