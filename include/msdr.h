@@ -553,7 +553,36 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   Osc_Q_buffer_i on every update() (freq_conv.h:33-34, freq_conv.cpp:70-103), so a sketch that rewrites them retunes the mixer
  *   without touching anything else; the position in the table carries on.  The samples already in the FIR history were mixed with the
  *   table of their own time, as in the reference (the mixer runs in front of the FIR's state buffer): the library keeps up to 16 earlier
- *   tables for as long as the history holds samples of theirs (a 17th change inside ONE history length drops the oldest). */
+ *   tables for as long as the history holds samples of theirs (a 17th change inside ONE history length drops the oldest).
+ * msdr_chain_set_osc_channels: oscillator tables that belong to the CHANNEL -- tune() of receiver rx moves that receiver's local oscillator
+ *   and nothing else (Minimal-SDR.ino:328-368); a bank of AudioEffectFreqConv nodes is a bank of Osc_I_buffer_i / Osc_Q_buffer_i pairs
+ *   (freq_conv.h:33-34).  osc_i / osc_q: HOST arrays [count][osc_len], q15_t or float32_t by the chain's arithmetic as in
+ *   msdr_chain_set_osc, for channels first_channel .. first_channel + count - 1, read during the call; osc_len is the chain's.  Semantics of
+ *   msdr_chain_set_osc for the named channels only: the table position carries on (it is common to all channels), every filter state is
+ *   kept, the samples already in a channel's FIR history stay mixed with the tables of their own time.  count == 0 does nothing; a NULL
+ *   chain, a NULL array (either one), a range past `channels`, a chain with the Fs/4 mixer and, on an fp32 chain, a table entry that is not
+ *   finite are MSDR_STATUS_ARGUMENT_ERROR, nothing changed.  From the first such call on, for the rest of its life, the chain's demodulator
+ *   kernel is chain_q15pco_kernel (Q15; PLL, LMS and node kernels behind it as before) or chain_f32pco_kernel (F32; the cascade moves behind
+ *   the kernel in CMSIS order with its state, exactly as the first msdr_chain_set_taps_channels_f32 call moves it and with that call's one
+ *   refusal; MSDR_CHAIN_OUT_I16 converts last); msdr_chain_get_info().kernel names it, and on an fp32 chain flavour carries
+ *   MSDR_FLAVOUR_OSC_PC beside MSDR_FLAVOUR_TAPS_PC (and MSDR_FLAVOUR_SEQ_CASCADE where there is a cascade).  Both kernels read per-channel
+ *   tap rows: a chain without per-channel taps gets its table filled from the shared tap sets, and msdr_chain_set_taps_channels[_f32],
+ *   msdr_chain_set_biquad_coeffs_channels and this call combine in any order.  msdr_chain_set_osc afterwards writes EVERY channel's row and
+ *   the chain stays in per-channel mode.  The rows survive msdr_chain_set_taps / set_taps_channels[_f32] / set_mode / set_anr, the node and
+ *   cascade setters, msdr_chain_init_fir and msdr_chain_reset (which clears the pending generations: no sample of theirs is left).
+ *   Generations: one call is ONE generation for the whole chain, whatever `count` (and so is msdr_chain_set_osc); two calls with no
+ *   msdr_chain_process between them count once; up to 16 are kept, a 17th inside one history length drops the oldest.  A pending generation
+ *   is a device copy of the whole bank, channels x osc_len x 8 bytes, freed once the history has turned over.
+ *   Limits: a channel's windows, tap rows and oscillator row live in 64 KB of LDS.  Q15: 12 x num_taps (rounded up to 8) + 4 x osc_len
+ *   <= 61 440 -- 5 072 taps at osc_len = 128, every chain (num_taps <= 4096) up to osc_len = 3 072.  F32: 3 776 taps at osc_len = 128 (3 840
+ *   without the row; every 64 entries more cost 32 taps).  Longer chains are refused at the first call (ARGUMENT_ERROR, nothing changed).
+ *   fp32 chains whose PLL / LMS channels run through the auxiliary chain are out of scope (it is built from the shared tables): the call
+ *   is refused (ARGUMENT_ERROR, nothing changed) on an fp32 chain created with MSDR_CHAIN_SYNCAM_PLL or with any LMS channel on, and on an
+ *   fp32 chain in this mode msdr_chain_set_anr with any channel on is refused.  Q15 chains have no such limit.
+ *   Graphs, Q15: a msdr_chain_graph made before the first call is refused at launch afterwards; one made in this mode is accepted under the
+ *   conditions of per-channel taps (block lengths 32 .. 512, no PLL / LMS channels, no pending generation, the oscillator period dividing
+ *   n_samples), replays bit-exactly, and is refused after any later msdr_chain_set_osc_channels / msdr_chain_set_osc.  F32:
+ *   msdr_chain_graph_create is refused, as on every chain with the cascade behind the kernel. */
 int msdr_chain_set_taps(msdr_chain *chain, uint32_t tapset, const void *coeffs_i, const void *coeffs_q);
 int msdr_chain_set_taps_channels(msdr_chain *chain, uint32_t first_channel, uint32_t count,
                                  const q15_t *coeffs_i, const q15_t *coeffs_q);
@@ -566,6 +595,8 @@ int msdr_chain_set_biquad_coeffs(msdr_chain *chain, const float32_t *biquad_coef
 int msdr_chain_set_biquad_coeffs_channels(msdr_chain *chain, uint32_t first_channel, uint32_t count,
                                           const float32_t *biquad_coeffs);
 int msdr_chain_set_osc(msdr_chain *chain, const void *osc_i, const void *osc_q);
+int msdr_chain_set_osc_channels(msdr_chain *chain, uint32_t first_channel, uint32_t count,
+                                const void *osc_i, const void *osc_q);
 /* ANR_on per channel (host array of `channels` values, or NULL: anr_on_all for every channel); the LMS filter then runs between
  * the demodulator and the biquad nodes / cascade (Minimal-SDR.ino:702-770).  Its state is created on first use and cleared by
  * msdr_chain_reset() (not by msdr_chain_init_fir()).  Q15 chains: as the reference, on the int16 audio.  F32 chains (an
@@ -608,6 +639,9 @@ enum { MSDR_FLAVOUR_TAPS_PC = 0x8000u };
 /* And another: the cascade behind the main kernel ran with per-channel coefficients -- biquad_df1_seq_pc_kernel, msdr_chain_set_biquad_coeffs_channels
  * (always beside MSDR_FLAVOUR_SEQ_CASCADE). */
 enum { MSDR_FLAVOUR_CASCADE_PC = 0x10000u };
+/* And another: the demodulator kernel mixed every channel with its own oscillator row -- chain_f32pco_kernel, msdr_chain_set_osc_channels
+ * (always beside MSDR_FLAVOUR_TAPS_PC). */
+enum { MSDR_FLAVOUR_OSC_PC = 0x20000u };
 int msdr_chain_get_info(msdr_chain *chain, msdr_chain_info *info);
 /* Measurement aid (bench.py): when enabled every msdr_chain_process() brackets its MAIN kernel with
  * HIP events on the context's stream; get_kernel_time synchronises and returns the accumulated

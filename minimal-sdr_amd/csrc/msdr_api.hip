@@ -20,6 +20,7 @@
 #include "msdr_chain_q15mb.hiph"
 #include "msdr_chain_q15pc.hiph"
 #include "msdr_chain_f32pc.hiph"
+#include "msdr_chain_oscpc.hiph"
 #include "msdr_block.h"
 #include "msdr_design.h"
 #include "msdr_cascade_state.h"
@@ -2336,7 +2337,8 @@ struct msdr_chain {
     uint64_t floor_gen = ~0ull;
     // msdr_chain_set_osc: the tables that were in force when the samples still in the FIR history arrived, oldest first.  While any is
     // pending the chain runs chain_kernel<Arith>, which mixes every history sample with the table of its own time.
-    struct OscPending { void *d_tab; long long elapsed; };
+    // (stride: 0 = one table that all channels shared, osc_len = a copy of the whole bank of per-channel rows, see below)
+    struct OscPending { void *d_tab; long long elapsed; int stride; };
     std::vector<OscPending> osc_pending;
     bool force_generic = false;          // the as-written kernel for the time being: no mode counts as numerator-folded
     OscHistory *d_osc_hist = nullptr;    // the pending tables as the kernel reads them
@@ -2455,6 +2457,12 @@ struct msdr_chain {
     float *d_pcf_taps = nullptr;          // [channels][2][pc_np]
     bool seq_forced = false;              // every rebuild keeps the cascade behind the kernel (chain_rebuild)
     std::vector<float> h_pcf_taps;
+    // per-channel oscillator tables (msdr_chain_set_osc_channels): from the first such call on, for the chain's life, the demodulator kernel is
+    // chain_q15pco_kernel / chain_f32pco_kernel (msdr_chain_oscpc.hiph), which read per-channel tap rows as above (pc_active is set with it) and
+    // mix channel ch with row ch of this bank.  d_osc stays what the stored shared tables say; nothing reads it in this mode.
+    bool opc_active = false;
+    void *d_osc_bank = nullptr;           // [channels][osc_len] pairs {osc_q ("cos"), osc_i ("sin")}: int2 (Q15) / float2 (F32)
+    uint64_t osc_gen = 0;                 // bumped by every change of the bank: part of a HIP graph's key
     msdr_chain_info info;
     // optional per-launch timing of the main kernel
     bool timing;
@@ -2484,6 +2492,7 @@ static void chain_pc_row_from(msdr_chain *c, uint32_t ch, const int16_t *ci, con
 // tests/test_f32_flavour_cases.py, holds that function's kernel-name literals against its own table; this path has its own tests,
 // tests/test_gpu_taps_per_channel_f32.py and tests/test_f32pc_cases.py.)
 static const char kPcfKernelName[] = "chain_f32pc_kernel (per-channel taps)";
+static const char kPcfoKernelName[] = "chain_f32pco_kernel (per-channel taps and oscillator tables)";
 static void chain_pcf_row_from(msdr_chain *c, uint32_t ch, const float *ci, const float *cq)
 {
     float *row = c->h_pcf_taps.data() + (size_t)ch * 2 * c->pc_np;
@@ -2540,7 +2549,7 @@ static void chain_free(msdr_chain *c)
     hipFree(c->d_anr_on);
     for (auto &e : c->events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (auto &o : c->osc_pending) hipFree(o.d_tab);
-    hipFree(c->d_f32_scratch); hipFree(c->d_osc_hist); hipFree(c->d_btiles); hipFree(c->d_pc_taps); hipFree(c->d_pcf_taps);
+    hipFree(c->d_f32_scratch); hipFree(c->d_osc_hist); hipFree(c->d_btiles); hipFree(c->d_pc_taps); hipFree(c->d_pcf_taps); hipFree(c->d_osc_bank);
     delete c;
 }
 
@@ -3654,7 +3663,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         memset(&oh, 0, sizeof oh);
         for (const auto &o : c->osc_pending) {
             if (oh.n >= kOscHistMax) break;
-            oh.tab[oh.n] = o.d_tab; oh.sw[oh.n] = -o.elapsed; oh.n++;
+            oh.tab[oh.n] = o.d_tab; oh.sw[oh.n] = -o.elapsed; oh.stride[oh.n] = o.stride; oh.n++;
         }
         if (!c->d_osc_hist) HIP_TRY(hipMalloc((void **)&c->d_osc_hist, sizeof(OscHistory)));
         HIP_TRY(hipMemcpyAsync(c->d_osc_hist, &oh, sizeof oh, hipMemcpyHostToDevice, c->ctx->stream));
@@ -3823,7 +3832,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         // msdr_chain_graph_create's preparation pass: everything a block-cadence call needs from the host is in place now; say whether the
         // launches that follow are fixed (capturable into a HIP graph) -- and make none
         if (use_pcf) return fail(MSDR_STATUS_ARGUMENT_ERROR, "an fp32 chain with per-channel FIR coefficients (chain_f32pc_kernel: launch geometry chosen per call) is not capturable");
-        if (use_pc) {            // chain_q15pc_kernel + the kernels behind it + the history kernel: a fixed set of launches at a block-cadence length
+        if (use_pc) {            // chain_q15pc_kernel / chain_q15pco_kernel + the kernels behind it + the history kernel: a fixed set of launches at a block-cadence length
             if (!mb_n_ok((long long)n_samples)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "not a block-cadence call (32 .. 512 samples, a divisor of 1024): nothing to capture");
             if (pll_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the PLL demodulator runs behind the kernel: not capturable");
             if (p.osc_hist) return fail(MSDR_STATUS_ARGUMENT_ERROR, "a pending oscillator change (the history still holds samples of an earlier table): not capturable");
@@ -3930,9 +3939,17 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         q.hist_len = (int)c->hist_len; q.np = c->pc_np; q.taps = c->d_pcf_taps; q.chan_mode = c->d_mode; q.mixer = c->mixer; q.osc = c->d_osc;
         q.osc_len = (int)c->osc_len; q.phase0 = (int)c->phase; q.in_scale = c->in_scale; q.osc_hist = p.osc_hist;
         PcLaunch geo;
-        if (launch_chain_f32pc(c->ctx->stream, false, c->ctx->num_cus, (int)c->time_segments, q, &geo) != hipSuccess)
-            return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pc_kernel launch failed");
-        kname = kPcfKernelName; grid = geo.grid; block = geo.block; lds_used = geo.lds_bytes; nseg = geo.nseg; pc_tile = geo.tile;
+        if (c->opc_active) {          // per-channel oscillator tables: the bank in place of the shared table
+            q.osc = c->d_osc_bank;
+            if (launch_chain_f32pco(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, q, &geo) != hipSuccess)
+                return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pco_kernel launch failed");
+            kname = kPcfoKernelName; flavour |= MSDR_FLAVOUR_OSC_PC;
+        } else {
+            if (launch_chain_f32pc(c->ctx->stream, false, c->ctx->num_cus, (int)c->time_segments, q, &geo) != hipSuccess)
+                return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pc_kernel launch failed");
+            kname = kPcfKernelName;
+        }
+        grid = geo.grid; block = geo.block; lds_used = geo.lds_bytes; nseg = geo.nseg; pc_tile = geo.tile;
         flavour |= MSDR_FLAVOUR_TAPS_PC | (geo.nseg > 1 ? MSDR_FLAVOUR_SEGMENTED : 0u);
     }
     else if (f32) { (void)launch_chain_generic(c->ctx->stream, false, grid, lds, p); if (nseg > 1) flavour |= MSDR_FLAVOUR_SEGMENTED; }
@@ -4015,9 +4032,17 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         q.hist_len = (int)c->hist_len; q.np = c->pc_np; q.taps = c->d_pc_taps; q.chan_mode = c->d_mode; q.mixer = c->mixer; q.osc = c->d_osc;
         q.osc_len = (int)c->osc_len; q.phase0 = (int)c->phase; q.sqrt_kind = c->sqrt_kind; q.syncam_q = p.syncam_q; q.osc_hist = p.osc_hist;
         PcLaunch geo;
-        if (launch_chain_q15pc(c->ctx->stream, false, c->ctx->num_cus, q, &geo) != hipSuccess)
-            return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pc_kernel launch failed");
-        kname = "chain_q15pc_kernel (per-channel taps)"; grid = geo.grid; block = geo.block; lds_used = geo.lds_bytes; nseg = geo.nseg; pc_tile = geo.tile;
+        if (c->opc_active) {          // per-channel oscillator tables: the bank in place of the shared table
+            q.osc = c->d_osc_bank;
+            if (launch_chain_q15pco(c->ctx->stream, c->ctx->num_cus, q, &geo) != hipSuccess)
+                return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pco_kernel launch failed");
+            kname = "chain_q15pco_kernel (per-channel taps and oscillator tables)";
+        } else {
+            if (launch_chain_q15pc(c->ctx->stream, false, c->ctx->num_cus, q, &geo) != hipSuccess)
+                return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pc_kernel launch failed");
+            kname = "chain_q15pc_kernel (per-channel taps)";
+        }
+        grid = geo.grid; block = geo.block; lds_used = geo.lds_bytes; nseg = geo.nseg; pc_tile = geo.tile;
     }
     else     (void)launch_chain_generic(c->ctx->stream, true, grid, lds, p);
     if (int rc = launch_check("chain_kernel")) return rc;
@@ -4127,12 +4152,14 @@ struct msdr_chain_graph {
     const void *k_mode, *k_osc;
     bool k_taps_pc;        // the chain ran chain_q15pc_kernel (per-channel taps) when the launches were captured
     bool k_nodes_pc;       // the biquad nodes ran per channel (a kernel of its own behind the demodulator kernel) when the launches were captured
+    bool k_osc_pc;         // the chain ran chain_q15pco_kernel (per-channel oscillator tables) when the launches were captured
+    uint64_t k_osc_gen;    // the bank as it was: every later change makes a generation, which the captured launches know nothing of
 };
 static void chain_graph_key(const msdr_chain *c, msdr_chain_graph *g)
 {
     g->k_hist = c->d_hist[c->cur]; g->k_state = c->d_bq_state; g->k_tab = c->arith == MSDR_ARITH_F32 ? (const void *)c->d_mf_tab : (const void *)c->d_qm_tab;
     g->k_tiles = c->d_btiles; g->k_cur = c->cur; g->k_mode_gen = c->mode_gen; g->k_nodes_pc = chain_nodes_per_channel(c); g->k_taps_pc = c->pc_active;
-    g->k_rebuild_gen = c->rebuild_gen; g->k_mode = c->d_mode; g->k_osc = c->d_osc;
+    g->k_rebuild_gen = c->rebuild_gen; g->k_mode = c->d_mode; g->k_osc = c->d_osc; g->k_osc_pc = c->opc_active; g->k_osc_gen = c->osc_gen;
 }
 
 extern "C" int msdr_chain_graph_create(msdr_chain *c, uint32_t ticks, const int16_t *const *d_if, void *const *d_audio, uint64_t n_samples, msdr_chain_graph **out)
@@ -4193,6 +4220,8 @@ extern "C" int msdr_chain_graph_launch(msdr_chain_graph *g)
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "a biquad node got per-channel coefficients since this graph was made (its captured launches keep a node's coefficients uniform): make the graph again");
     if (now.k_taps_pc != g->k_taps_pc)
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "channels got FIR coefficients of their own since this graph was made (its captured launches share tap sets between channels): make the graph again");
+    if (now.k_osc_pc != g->k_osc_pc || now.k_osc_gen != g->k_osc_gen)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "channels got oscillator tables of their own, or the bank of tables changed, since this graph was made (the history holds samples of the earlier tables): make the graph again");
     HIP_TRY(hipGraphLaunch(g->exec, c->ctx->stream));
     c->gen += g->ticks;                                     // (an even number of calls: buffers, table position and caches stay as they are)
     return 0;
@@ -4431,6 +4460,8 @@ static int chain_rebuild(msdr_chain *c, const ChainCfgStore &edited, void **stea
     n->rebuild_gen = c->rebuild_gen + 1;
     n->pc_active = c->pc_active; n->pc_np = c->pc_np; std::swap(n->d_pc_taps, c->d_pc_taps); n->h_pc_taps.swap(c->h_pc_taps); n->h_pc_own.swap(c->h_pc_own);
     std::swap(n->d_pcf_taps, c->d_pcf_taps); n->h_pcf_taps.swap(c->h_pcf_taps); n->seq_forced = c->seq_forced;
+    // ... and so does the bank of per-channel oscillator tables (its pending generations went over with osc_pending above)
+    n->opc_active = c->opc_active; std::swap(n->d_osc_bank, c->d_osc_bank); n->osc_gen = c->osc_gen;
     std::swap(*c, *n);
     if (steal_osc) { *steal_osc = n->d_osc; n->d_osc = nullptr; }
     chain_free(n);
@@ -4499,7 +4530,7 @@ static int chain_rebuild_keep_folded(msdr_chain *c, const ChainCfgStore &edited,
         if (!c->osc_pending.empty() && c->osc_pending.back().elapsed == 0) hipFree(old_osc);
         else {
             if (c->osc_pending.size() >= (size_t)kOscHistMax) { hipFree(c->osc_pending.front().d_tab); c->osc_pending.erase(c->osc_pending.begin()); }
-            c->osc_pending.push_back(msdr_chain::OscPending{old_osc, 0});
+            c->osc_pending.push_back(msdr_chain::OscPending{old_osc, 0, 0});
         }
         c->force_generic = true;
     }
@@ -4534,6 +4565,41 @@ extern "C" int msdr_chain_set_taps(msdr_chain *c, uint32_t tapset, const void *c
     return chain_rebuild_keep_folded(c, ed, [&](uint32_t ch) { return (uint32_t)c->h_tapset[ch] == tapset; });
 }
 
+// force_seq: the rebuilt chain runs the cascade in CMSIS order behind the main kernel whatever the coefficients would choose (a chain that is
+// about to get, or has, per-channel FIR coefficients: msdr_chain_set_taps_channels_f32 moves the running cascade there with its state)
+static int chain_set_biquad_coeffs_impl(msdr_chain *c, const float32_t *coeffs, bool force_seq);
+// The first per-channel call of a chain's life (msdr_chain_set_taps_channels[_f32], msdr_chain_set_osc_channels): the per-channel tap table,
+// every row a copy of its tap set's; F32: the cascade moves behind the kernel.  The caller uploads the table (chain_pc_upload, all rows).
+static int chain_pc_activate(msdr_chain *c)
+{
+    if (c->pc_active) return 0;
+    const bool f32 = c->arith == MSDR_ARITH_F32;
+    const int np = f32 ? f32pc_np((int)c->ntaps) : pc_np((int)c->ntaps);
+    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+    float *ftab = nullptr;                                   // (first what can fail without a trace: a refusal leaves the chain as it was)
+    int16_t *qtab = nullptr;
+    if (int rc = f32 ? dzalloc(c->ctx, (size_t)c->channels * 2 * np, &ftab) : dzalloc(c->ctx, (size_t)c->channels * 2 * np, &qtab)) return rc;
+    if (f32) {
+        // the cascade moves behind the kernel, in CMSIS order, with its state (the way msdr_chain_set_biquad_coeffs moves a cascade between
+        // the two places); a chain whose cascade runs there already keeps its stage object
+        if (c->h_bq_stages > 0 && !c->seq_bq) {
+            const std::vector<float> same = c->h_bq;
+            if (int rc = chain_set_biquad_coeffs_impl(c, same.data(), true)) { hipFree(ftab); return rc; }
+        }
+        c->seq_forced = true;
+        c->d_pcf_taps = ftab;
+        c->h_pcf_taps.assign((size_t)c->channels * 2 * np, 0.0f);
+    } else {
+        c->d_pc_taps = qtab;
+        c->h_pc_taps.assign((size_t)c->channels * 2 * np, 0);
+    }
+    c->pc_np = np;
+    c->h_pc_own.assign(c->channels, 0);
+    for (uint32_t ch = 0; ch < c->channels; ch++) chain_pc_row_shared(c, ch);
+    c->pc_active = true;
+    return 0;
+}
+
 // calc_demod_filter() of ONE receiver of the bank (Minimal-SDR.ino:221-223): rows of the per-channel table rewritten under the running stream
 extern "C" int msdr_chain_set_taps_channels(msdr_chain *c, uint32_t first_channel, uint32_t count, const q15_t *coeffs_i, const q15_t *coeffs_q)
 {
@@ -4547,15 +4613,7 @@ extern "C" int msdr_chain_set_taps_channels(msdr_chain *c, uint32_t first_channe
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "channels %u .. %llu of %u", first_channel, (unsigned long long)first_channel + count - 1, c->channels);
     if (!coeffs_q) coeffs_q = coeffs_i;                          // init_FIR() for AM / SYNCAM: one array behind both instances (.ino:917-924)
     const bool first_call = !c->pc_active;
-    if (first_call) {
-        c->pc_np = pc_np((int)c->ntaps);
-        HIP_TRY(hipStreamSynchronize(c->ctx->stream));
-        if (int rc = dzalloc(c->ctx, (size_t)c->channels * 2 * c->pc_np, &c->d_pc_taps)) return rc;
-        c->h_pc_taps.assign((size_t)c->channels * 2 * c->pc_np, 0);
-        c->h_pc_own.assign(c->channels, 0);
-        for (uint32_t ch = 0; ch < c->channels; ch++) chain_pc_row_shared(c, ch);
-        c->pc_active = true;
-    }
+    if (int rc = chain_pc_activate(c)) return rc;
     for (uint32_t i = 0; i < count; i++) {
         chain_pc_row_from(c, first_channel + i, coeffs_i + (size_t)i * c->ntaps, coeffs_q + (size_t)i * c->ntaps);
         c->h_pc_own[first_channel + i] = 1;
@@ -4563,9 +4621,6 @@ extern "C" int msdr_chain_set_taps_channels(msdr_chain *c, uint32_t first_channe
     return first_call ? chain_pc_upload(c, 0, c->channels) : chain_pc_upload(c, first_channel, count);
 }
 
-// force_seq: the rebuilt chain runs the cascade in CMSIS order behind the main kernel whatever the coefficients would choose (a chain that is
-// about to get, or has, per-channel FIR coefficients: msdr_chain_set_taps_channels_f32 moves the running cascade there with its state)
-static int chain_set_biquad_coeffs_impl(msdr_chain *c, const float32_t *coeffs, bool force_seq);
 // the same for an fp32 chain: rows of floats, chain_f32pc_kernel (msdr_chain_f32pc.hiph) from the first call on
 extern "C" int msdr_chain_set_taps_channels_f32(msdr_chain *c, uint32_t first_channel, uint32_t count, const float32_t *coeffs_i, const float32_t *coeffs_q)
 {
@@ -4581,25 +4636,7 @@ extern "C" int msdr_chain_set_taps_channels_f32(msdr_chain *c, uint32_t first_ch
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "per-channel coefficients: the kernel holds filters of up to %d taps (this chain has %u); nothing changed", f32pc_max_taps(false), c->ntaps);
     if (!coeffs_q) coeffs_q = coeffs_i;                          // init_FIR() for AM / SYNCAM: one array behind both instances (.ino:917-924)
     const bool first_call = !c->pc_active;
-    if (first_call) {
-        const int np = f32pc_np((int)c->ntaps);
-        HIP_TRY(hipStreamSynchronize(c->ctx->stream));
-        float *tab = nullptr;                                    // (first what can fail without a trace: a refusal leaves the chain as it was)
-        if (int rc = dzalloc(c->ctx, (size_t)c->channels * 2 * np, &tab)) return rc;
-        // the cascade moves behind the kernel, in CMSIS order, with its state (the way msdr_chain_set_biquad_coeffs moves a cascade between
-        // the two places); a chain whose cascade runs there already keeps its stage object
-        if (c->h_bq_stages > 0 && !c->seq_bq) {
-            const std::vector<float> same = c->h_bq;
-            if (int rc = chain_set_biquad_coeffs_impl(c, same.data(), true)) { hipFree(tab); return rc; }
-        }
-        c->seq_forced = true;
-        c->d_pcf_taps = tab;
-        c->pc_np = np;
-        c->h_pcf_taps.assign((size_t)c->channels * 2 * np, 0.0f);
-        c->h_pc_own.assign(c->channels, 0);
-        for (uint32_t ch = 0; ch < c->channels; ch++) chain_pc_row_shared(c, ch);
-        c->pc_active = true;
-    }
+    if (int rc = chain_pc_activate(c)) return rc;
     for (uint32_t i = 0; i < count; i++) {
         chain_pcf_row_from(c, first_channel + i, coeffs_i + (size_t)i * c->ntaps, coeffs_q + (size_t)i * c->ntaps);
         c->h_pc_own[first_channel + i] = 1;
@@ -4607,11 +4644,100 @@ extern "C" int msdr_chain_set_taps_channels_f32(msdr_chain *c, uint32_t first_ch
     return first_call ? chain_pc_upload(c, 0, c->channels) : chain_pc_upload(c, first_channel, count);
 }
 
+// ---- per-channel oscillator tables ----
+// `count` rows of pairs {osc_q ("cos"), osc_i ("sin")} as the kernels read them, from tables [.][osc_len] that lie src_stride entries apart
+// (0: the same table for every row)
+static void chain_osc_pairs(const msdr_chain *c, char *dst, uint32_t count, const void *osc_i, const void *osc_q, size_t src_stride)
+{
+    const size_t L = c->osc_len;
+    for (uint32_t r = 0; r < count; r++)
+        for (size_t k = 0; k < L; k++) {
+            const size_t si = (size_t)r * src_stride + k, di = ((size_t)r * L + k) * 2;
+            if (c->arith == MSDR_ARITH_F32) { ((float *)dst)[di] = ((const float *)osc_q)[si]; ((float *)dst)[di + 1] = ((const float *)osc_i)[si]; }
+            else { ((int32_t *)dst)[di] = ((const int16_t *)osc_q)[si]; ((int32_t *)dst)[di + 1] = ((const int16_t *)osc_i)[si]; }
+        }
+}
+// Rows first .. first + count - 1 of the bank rewritten under the running stream: ONE generation for the whole chain.  The tables in force so
+// far are kept for the samples still in the FIR history: the shared table (stride 0) at the first call of the chain's life, a device copy of the
+// whole bank afterwards.  At the first call the chain goes over to per-channel taps too (chain_pc_activate) and the bank is filled from the
+// stored shared tables.  Everything that can fail happens before anything changes.
+static int chain_osc_rows(msdr_chain *c, uint32_t first, uint32_t count, const void *osc_i, const void *osc_q, size_t src_stride)
+{
+    const size_t L = c->osc_len, row_bytes = L * 8;          // int2 / float2
+    const bool first_call = !c->opc_active;
+    std::vector<char> rows((size_t)count * row_bytes);
+    chain_osc_pairs(c, rows.data(), count, osc_i, osc_q, src_stride);
+    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+    void *bank = nullptr, *snap = nullptr;
+    if (first_call && hipMalloc(&bank, (size_t)c->channels * row_bytes) != hipSuccess) { (void)hipGetLastError(); return fail(MSDR_STATUS_OUT_OF_MEMORY, "device allocation of the oscillator bank failed"); }
+    // a table that was replaced before any sample arrived under it mixed nothing: it is not a generation (chain_rebuild_keep_folded)
+    const bool new_gen = c->osc_pending.empty() || c->osc_pending.back().elapsed != 0;
+    if (new_gen) {
+        const size_t nb = first_call ? row_bytes : (size_t)c->channels * row_bytes;
+        if (hipMalloc(&snap, nb) != hipSuccess || hipMemcpy(snap, first_call ? c->d_osc : c->d_osc_bank, nb, hipMemcpyDeviceToDevice) != hipSuccess) {
+            (void)hipGetLastError(); hipFree(bank); hipFree(snap);
+            return fail(MSDR_STATUS_OUT_OF_MEMORY, "device copy of the oscillator tables in force (one pending generation: channels x osc_len x 8 bytes) failed");
+        }
+    }
+    const bool taps_first = !c->pc_active;
+    if (int rc = chain_pc_activate(c)) { hipFree(bank); hipFree(snap); return rc; }
+    if (taps_first) if (int rc = chain_pc_upload(c, 0, c->channels)) { hipFree(bank); hipFree(snap); return rc; }
+    if (first_call) {
+        std::vector<char> all((size_t)c->channels * row_bytes);
+        chain_osc_pairs(c, all.data(), c->channels, c->store.osc_i.data(), c->store.osc_q.data(), 0);
+        if (hipMemcpy(bank, all.data(), all.size(), hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); hipFree(bank); hipFree(snap); return fail(MSDR_STATUS_HIP_ERROR, "upload of the oscillator bank failed"); }
+        c->d_osc_bank = bank; c->opc_active = true;
+    }
+    HIP_TRY(hipMemcpy((char *)c->d_osc_bank + (size_t)first * row_bytes, rows.data(), rows.size(), hipMemcpyHostToDevice));
+    if (new_gen) {
+        if (c->osc_pending.size() >= (size_t)kOscHistMax) { hipFree(c->osc_pending.front().d_tab); c->osc_pending.erase(c->osc_pending.begin()); }
+        c->osc_pending.push_back(msdr_chain::OscPending{snap, 0, first_call ? 0 : (int)L});
+    }
+    c->force_generic = true;          // (generations are pending: msdr_chain_process counts them down and frees them, chain_leave_generic)
+    c->osc_gen++;
+    return 0;
+}
+
+// tune() of ONE receiver of the bank (Minimal-SDR.ino:328-368): that receiver's local oscillator and nothing else
+extern "C" int msdr_chain_set_osc_channels(msdr_chain *c, uint32_t first_channel, uint32_t count, const void *osc_i, const void *osc_q)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (int rc = bind(c->ctx)) return rc;
+    if (c->mixer != MSDR_MIXER_NCO) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has the Fs/4 mixer: no oscillator tables (Minimal-SDR.ino:546-558)");
+    if (count == 0) return 0;
+    if (!osc_i || !osc_q) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null oscillator array");
+    if (first_channel >= c->channels || count > c->channels - first_channel)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "channels %u .. %llu of %u", first_channel, (unsigned long long)first_channel + count - 1, c->channels);
+    const bool f32 = c->arith == MSDR_ARITH_F32;
+    if (f32) {
+        const size_t total = (size_t)count * c->osc_len;
+        for (size_t k = 0; k < total; k++)
+            if (!std::isfinite(((const float *)osc_i)[k]) || !std::isfinite(((const float *)osc_q)[k])) return fail(MSDR_STATUS_ARGUMENT_ERROR, "oscillator table entry %zu is not finite", k);
+        // PLL / LMS channels of an fp32 chain run through an auxiliary chain that is built from the shared tables
+        if (c->f32_pll) return fail(MSDR_STATUS_ARGUMENT_ERROR, "per-channel oscillator tables: not on an fp32 chain created with MSDR_CHAIN_SYNCAM_PLL (its PLL channels run through an auxiliary chain with the shared tables); nothing changed");
+        for (int v : c->h_anr) if (v > 0) return fail(MSDR_STATUS_ARGUMENT_ERROR, "per-channel oscillator tables: not while an LMS channel of an fp32 chain is on (such channels run through an auxiliary chain with the shared tables); nothing changed");
+    }
+    if (!c->opc_active) {          // (one wave's windows, tap rows and oscillator row must fit the kernel's LDS)
+        const int np = f32 ? f32pc_np((int)c->ntaps) : pc_np((int)c->ntaps);
+        const int cap = f32 ? f32pco_max_taps((int)c->osc_len) : pco_max_taps((int)c->osc_len);
+        if (np > cap)
+            return fail(MSDR_STATUS_ARGUMENT_ERROR, "per-channel oscillator tables: beside a row of %u entries the kernel holds filters of up to %d taps (this chain has %u); nothing changed", c->osc_len, cap, c->ntaps);
+    }
+    return chain_osc_rows(c, first_channel, count, osc_i, osc_q, c->osc_len);
+}
+
 extern "C" int msdr_chain_set_osc(msdr_chain *c, const void *osc_i, const void *osc_q)
 {
     if (!c || !osc_i || !osc_q) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
     if (int rc = bind(c->ctx)) return rc;
     if (c->mixer != MSDR_MIXER_NCO) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has the Fs/4 mixer: no oscillator tables (Minimal-SDR.ino:546-558)");
+    if (c->opc_active) {          // per-channel oscillator tables: EVERY channel's row, one generation; the stored shared tables follow
+        if (int rc = chain_osc_rows(c, 0, c->channels, osc_i, osc_q, 0)) return rc;
+        const size_t nb = c->store.osc_i.size();
+        c->store.osc_i.assign((const char *)osc_i, (const char *)osc_i + nb);
+        c->store.osc_q.assign((const char *)osc_q, (const char *)osc_q + nb);
+        return 0;
+    }
     ChainCfgStore ed = c->store;
     const size_t bytes = ed.osc_i.size();
     ed.osc_i.assign((const char *)osc_i, (const char *)osc_i + bytes);
@@ -4779,9 +4905,10 @@ extern "C" int msdr_chain_set_anr(msdr_chain *c, const int32_t *anr_on, int32_t 
     if (c->arith != MSDR_ARITH_Q15) {
         // fp32 chain: the float flavour of the filter, between demodulator and cascade (chain_post_run)
         if (c->seq_bq && !c->h_bq_stages) return fail(MSDR_STATUS_ARGUMENT_ERROR, "internal: cascade coefficients not kept");
-        if (c->seq_bq && c->seq_bq->per_channel) {               // (LMS channels run a post cascade with the chain's uniform coefficients)
+        if ((c->seq_bq && c->seq_bq->per_channel) || c->opc_active) {      // (LMS channels run a post cascade with the chain's uniform coefficients, behind an auxiliary chain with the shared oscillator tables)
             bool any = anr_on ? false : anr_on_all > 0;
             if (anr_on) for (uint32_t ch = 0; ch < c->channels; ch++) any = any || anr_on[ch] > 0;
+            if (any && c->opc_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has per-channel oscillator tables: no LMS channels (they run through an auxiliary chain with the shared tables); nothing changed");
             if (any) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has per-channel cascade coefficients: no LMS channels (they run a post cascade of their own); nothing changed");
         }
         c->h_anr.assign(c->channels, anr_on ? 0 : (int)anr_on_all);

@@ -51,6 +51,11 @@ hipError_t launch_chain_q15pc(hipStream_t stream, bool fir_only, int num_cus, Pc
 // Fs/4 mixer's flavour (p.mixer), one stream and half the products.  time_segments as msdr_chain_config.time_segments: 0 = the launcher's
 // choice, 1 = never split, > 1 = that many (as far as the call has tiles).
 hipError_t launch_chain_f32pc(hipStream_t stream, bool fir_only, int num_cus, int time_segments, PcfParams p, PcLaunch *geo);
+// ---- msdr_chain_oscpc.hip ----
+// chain_q15pco_kernel<CPW> / chain_f32pco_kernel<CPW> (msdr_chain_oscpc.hiph): the two chain kernels above with per-channel oscillator tables.
+// p.osc is the bank [channels][osc_len] of pairs, p.mixer MSDR_MIXER_NCO; geometry chosen as above, with the row's LDS counted in.
+hipError_t launch_chain_q15pco(hipStream_t stream, int num_cus, PcParams p, PcLaunch *geo);
+hipError_t launch_chain_f32pco(hipStream_t stream, int num_cus, int time_segments, PcfParams p, PcLaunch *geo);
 // ---- msdr_biquad_df1_pc.hip ----
 // biquad_df1_seq_pc_kernel<S, SEG> (msdr_biquad_df1_pc.hiph): stages = S = 1 .. 4 sections in CMSIS order on data [channels][n] (y may be x), every
 // channel with the 5 S coefficients of its own row of tab ([channels][20] floats).  nseg = 1: state_in may be state_out, seg_len / warm / scratch

@@ -53,7 +53,10 @@ constexpr int kBqStateFloats = 16;
 // time t < sw[k] (t relative to the call, so sw <= 0) was mixed with table k when it arrived (freq_conv.cpp:70-103 mixes each block with
 // the tables as they are at that update()), and chain_kernel<Arith> mixes it with that table again.
 constexpr int kOscHistMax = 16;      // oscillator tables that can still have samples in one FIR history (msdr_chain_set_osc)
-struct OscHistory { const void *tab[kOscHistMax]; long long sw[kOscHistMax]; int n; };
+// stride (at the END: the kernels above read tab / sw / n where they always were): the per-channel-oscillator kernels (msdr_chain_oscpc.hiph)
+// read channel ch's row of generation k at tab[k] + ch * stride[k] pairs -- 0 for a table that all channels shared, osc_len for a copy of
+// the whole bank (msdr_chain_set_osc_channels)
+struct OscHistory { const void *tab[kOscHistMax]; long long sw[kOscHistMax]; int n; int stride[kOscHistMax]; };
 
 constexpr int kChainOutI16 = 0x40000000;
 

@@ -322,6 +322,11 @@ public:
     // ANR_on per receiver (host array of channels() values; nullptr: anr_on_all for every receiver), Minimal-SDR.ino:702-770
     int setAnr(const int32_t *anr_on, int32_t anr_on_all = 0) { return chain ? msdr_chain_set_anr(chain, anr_on, anr_on_all) : MSDR_STATUS_ARGUMENT_ERROR; }
     int setOsc(const void *osc_i, const void *osc_q) { return chain ? msdr_chain_set_osc(chain, osc_i, osc_q) : MSDR_STATUS_ARGUMENT_ERROR; }
+    // tune() of receiver `channel` (Minimal-SDR.ino:328-368): that receiver's own Osc_I_buffer_i / Osc_Q_buffer_i (osc_len entries each), nobody else's
+    int setOscChannel(uint32_t channel, const void *osc_i, const void *osc_q)
+    {
+        return chain ? msdr_chain_set_osc_channels(chain, channel, 1, osc_i, osc_q) : MSDR_STATUS_ARGUMENT_ERROR;
+    }
     virtual void update(void)
     {
         audio_block_t *in = receiveReadOnly();

@@ -30,6 +30,7 @@ FLAVOUR_BLOCK, FLAVOUR_VALU_FOLD, FLAVOUR_SEQ_CASCADE, FLAVOUR_SEGMENTED = 0x100
 FLAVOUR_FOLD_PERIOD_SHIFT = 12
 FLAVOUR_TAPS_PC = 0x8000
 FLAVOUR_CASCADE_PC = 0x10000
+FLAVOUR_OSC_PC = 0x20000
 FE_DCBLOCK, FE_AMP, FE_AGC, FE_ALL = 1, 2, 4, 7
 
 STATUS_ARGUMENT_ERROR, STATUS_LENGTH_ERROR, STATUS_NO_DEVICE = -1, -2, -100
@@ -98,7 +99,8 @@ def load_library(path=None):
                        ("msdr_chain_set_taps_channels_f32", [_p, C.c_uint32, C.c_uint32, _p, _p]),
                        ("msdr_fir_f32_set_coeffs_channels", [_p, C.c_uint32, C.c_uint32, _p]),
                        ("msdr_chain_set_biquad_coeffs_channels", [_p, C.c_uint32, C.c_uint32, _p]),
-                       ("msdr_biquad_df1_f32_set_coeffs_channels", [_p, C.c_uint32, C.c_uint32, _p])):
+                       ("msdr_biquad_df1_f32_set_coeffs_channels", [_p, C.c_uint32, C.c_uint32, _p]),
+                       ("msdr_chain_set_osc_channels", [_p, C.c_uint32, C.c_uint32, _p, _p])):
             if hasattr(_lib, n):
                 getattr(_lib, n).argtypes = sig
         _lib.msdr_chain_set_biquad_coeffs.argtypes = [_p, _p]
@@ -486,6 +488,19 @@ def _taps_per_channel(what, coeffs, ntaps, dtype=np.int16):
     return c
 
 
+def _osc_per_channel(what, tab, osc_len, arith):
+    t = np.asarray(tab)
+    if arith == ARITH_Q15 and t.dtype.kind not in "iu":
+        raise ValueError("%s: a Q15 chain takes integer tables (q15_t), dtype %s given" % (what, t.dtype))
+    if arith == ARITH_F32 and t.dtype.kind not in "fiu":
+        raise ValueError("%s: an fp32 chain takes real tables (float32_t), dtype %s given" % (what, t.dtype))
+    if t.ndim != 2 or t.shape[1] != osc_len:
+        raise ValueError("%s: one row of %d entries per channel (osc_len is fixed at creation), shape %s given" % (what, osc_len, (t.shape,)))
+    if arith == ARITH_Q15 and t.size and (t.min() < -32768 or t.max() > 32767):
+        raise ValueError("%s: a table entry outside int16" % what)
+    return np.ascontiguousarray(t, np.float32 if arith == ARITH_F32 else np.int16)
+
+
 class BiquadQ15(_Instance):
     """AudioFilterBiquad: setCoefficients(stage, coef[5]) / update(), batched over channels."""
     _destroy = "msdr_biquad_q15_destroy"
@@ -779,6 +794,16 @@ class Chain(_Instance):
         if self.osc_len and (oi.size != self.osc_len or oq.size != self.osc_len):
             raise ValueError("set_osc: tables of %d / %d entries, the chain's have %d" % (oi.size, oq.size, self.osc_len))
         _ck(self.ctx.lib.msdr_chain_set_osc(self.h, _hp(oi), _hp(oq)))
+
+    def set_osc_channels(self, first_channel, osc_i, osc_q):
+        """channel first_channel + i gets oscillator tables of its own, osc_i[i] / osc_q[i] ([count, osc_len]; int16 on a Q15 chain, float32 on
+        an fp32 chain): tune() of ONE receiver.  The table position carries on, every state kept; chain_q15pco_kernel / chain_f32pco_kernel
+        from the first call on."""
+        oi = _osc_per_channel("set_osc_channels", osc_i, self.osc_len, self.arith)
+        oq = _osc_per_channel("set_osc_channels", osc_q, self.osc_len, self.arith)
+        if oi.shape != oq.shape:
+            raise ValueError("set_osc_channels: osc_i %s and osc_q %s differ in shape" % ((oi.shape,), (oq.shape,)))
+        _ck(self.ctx.lib.msdr_chain_set_osc_channels(self.h, C.c_uint32(first_channel), C.c_uint32(oi.shape[0]), _hp(oi), _hp(oq)))
 
     def set_node_coefficients(self, node, stage, coef):
         c = np.ascontiguousarray(coef, np.int32)
