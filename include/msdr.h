@@ -530,7 +530,24 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   (MSDR_STATUS_ARGUMENT_ERROR, nothing changed: a channel's two windows and two tap rows live in 64 KB of LDS).  Graphs: a
  *   msdr_chain_graph made before the first call is refused afterwards (MSDR_STATUS_ARGUMENT_ERROR at launch), and
  *   msdr_chain_graph_create on a chain already in per-channel mode is refused with MSDR_STATUS_ARGUMENT_ERROR (the launch geometry is
- *   chosen per call): this path has no graph replay.
+ *   chosen per call) -- unless msdr_chain_set_block_kernel is on: see there.
+ * msdr_chain_set_block_kernel (F32; default off): with `on` != 0 a block-cadence call (32 .. 512 samples, a divisor of 1024) of a chain in
+ *   per-channel mode (msdr_chain_set_taps_channels_f32 / msdr_chain_set_osc_channels, with or without a cascade, shared or per-channel
+ *   cascade rows) runs chain_f32pcb_kernel: mixer, FIR, demodulator, the CMSIS-order cascade, the MSDR_CHAIN_OUT_I16 conversion and the next
+ *   FIR history in ONE launch, the same operations in the same order as the unfused launches -- bit-identical audio and states.  The call is
+ *   a switch of the host's: stream-ordered, every state kept, before or after the chain enters per-channel mode.  A call runs the unfused
+ *   launches exactly as before while any of this holds: another block length; an oscillator generation pending (one history length after
+ *   msdr_chain_set_osc / set_osc_channels); a chain created with MSDR_CHAIN_SYNCAM_PLL or with an LMS channel on; one wave's windows, tap
+ *   rows, oscillator row and output row past 64 KB of LDS.  Both paths work on the same history, table position and cascade state, so a
+ *   chain moves between them from call to call.  msdr_chain_get_info(): kernel begins "chain_f32pcb_kernel" (and ends in the name of the
+ *   cascade that ran as its second phase), flavour = MSDR_FLAVOUR_BLOCK | MSDR_FLAVOUR_TAPS_PC, plus MSDR_FLAVOUR_OSC_PC,
+ *   MSDR_FLAVOUR_SEQ_CASCADE and MSDR_FLAVOUR_CASCADE_PC where they apply.  A Q15 chain and a NULL chain are MSDR_STATUS_ARGUMENT_ERROR.
+ *   Graphs: with the block kernel on, msdr_chain_graph_create accepts such a chain where the conditions above hold (and, as ever, `ticks`
+ *   is even and the oscillator period divides n_samples).  The graph stays valid across later msdr_chain_set_taps_channels_f32 and
+ *   msdr_chain_set_biquad_coeffs_channels calls, which rewrite rows the captured launches read (a call that allocates or moves a table --
+ *   the first per-channel cascade call -- invalidates it).  msdr_chain_graph_launch is refused (MSDR_STATUS_ARGUMENT_ERROR, nothing
+ *   enqueued) after msdr_chain_set_osc / set_osc_channels, msdr_chain_set_mode / set_taps / set_anr / set_biquad_coeffs, msdr_chain_reset,
+ *   msdr_chain_set_block_kernel(chain, 0), an odd number of direct calls, and any other live update that rebuilds tables.
  * msdr_chain_set_biquad_coeffs (F32): all 5 * num_biquad_stages coefficients of the arm_biquad_cascade_df1_f32 stage, CMSIS
  *   semantics (the filter carries on from the pState arm_biquad_cascade_df1_f32 would hold; see msdr_biquad_df1_f32_set_coeffs).
  *   The number of stages is fixed at creation, as numStages is in CMSIS.
@@ -597,6 +614,7 @@ int msdr_chain_set_biquad_coeffs_channels(msdr_chain *chain, uint32_t first_chan
 int msdr_chain_set_osc(msdr_chain *chain, const void *osc_i, const void *osc_q);
 int msdr_chain_set_osc_channels(msdr_chain *chain, uint32_t first_channel, uint32_t count,
                                 const void *osc_i, const void *osc_q);
+int msdr_chain_set_block_kernel(msdr_chain *chain, int on);   /* F32 chains; default off */
 /* ANR_on per channel (host array of `channels` values, or NULL: anr_on_all for every channel); the LMS filter then runs between
  * the demodulator and the biquad nodes / cascade (Minimal-SDR.ino:702-770).  Its state is created on first use and cleared by
  * msdr_chain_reset() (not by msdr_chain_init_fir()).  Q15 chains: as the reference, on the int16 audio.  F32 chains (an
@@ -627,7 +645,7 @@ typedef struct {
 #define MSDR_FLAVOUR_COMPACT      0x0020u   /* full-rate layout with compact (shifted-copy) tap fragments */
 #define MSDR_FLAVOUR_SHARED_IQ    0x0040u   /* full-rate envelope units whose two accumulators read one set of fragments (coeffs_i == coeffs_q in ANY tap set of the chain) */
 #define MSDR_FLAVOUR_AMTR         0x0080u   /* the envelope units ran on the taps-in-registers kernel (chain_amtr_kernel) */
-#define MSDR_FLAVOUR_BLOCK        0x0100u   /* block cadence: chain_mfb_kernel, channel-batched tiles */
+#define MSDR_FLAVOUR_BLOCK        0x0100u   /* block cadence: chain_mfb_kernel, channel-batched tiles; with MSDR_FLAVOUR_TAPS_PC: chain_f32pcb_kernel */
 #define MSDR_FLAVOUR_VALU_FOLD    0x0200u   /* chain_fold_kernel<P>; P in bits 12..14 */
 #define MSDR_FLAVOUR_SEQ_CASCADE  0x0400u   /* the cascade ran behind the main kernel in CMSIS order */
 #define MSDR_FLAVOUR_SEGMENTED    0x0800u   /* a launch split the call into more than one time segment */
@@ -643,6 +661,12 @@ enum { MSDR_FLAVOUR_CASCADE_PC = 0x10000u };
  * (always beside MSDR_FLAVOUR_TAPS_PC). */
 enum { MSDR_FLAVOUR_OSC_PC = 0x20000u };
 int msdr_chain_get_info(msdr_chain *chain, msdr_chain_info *info);
+/* Introspection for tests: what a chain carries from call to call.  get_fir_history: *hist_len = the raw int16 samples the chain keeps per
+ * channel (a property of the kernels it runs), and, where hist != NULL (capacity >= that many), channel's samples, oldest first.
+ * get_cmsis_state (F32 chains whose cascade runs behind the kernel: MSDR_FLAVOUR_SEQ_CASCADE): 4 * num_biquad_stages floats, as
+ * msdr_biquad_df1_f32_get_cmsis_state.  Both wait for the stream. */
+int msdr_chain_get_fir_history(msdr_chain *chain, uint32_t channel, int16_t *hist, uint32_t capacity, uint32_t *hist_len);
+int msdr_chain_get_cmsis_state(msdr_chain *chain, uint32_t channel, float32_t *pState);
 /* Measurement aid (bench.py): when enabled every msdr_chain_process() brackets its MAIN kernel with
  * HIP events on the context's stream; get_kernel_time synchronises and returns the accumulated
  * device time in ms and the number of launches timed (reset != 0 clears the accumulators). */

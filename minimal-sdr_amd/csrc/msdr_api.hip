@@ -2463,6 +2463,11 @@ struct msdr_chain {
     bool opc_active = false;
     void *d_osc_bank = nullptr;           // [channels][osc_len] pairs {osc_q ("cos"), osc_i ("sin")}: int2 (Q15) / float2 (F32)
     uint64_t osc_gen = 0;                 // bumped by every change of the bank: part of a HIP graph's key
+    // msdr_chain_set_block_kernel (F32): a block-cadence call of the chain in per-channel mode runs chain_f32pcb_kernel (msdr_chain_f32pcb.hiph) --
+    // demodulator, CMSIS-order cascade, int16 conversion and the next history in ONE launch -- where msdr_chain_process finds the conditions met;
+    // every other call runs the unfused launches over the same history, table position and cascade state.  Off by default.
+    bool block_pc = false;
+    uint64_t block_epoch = 0;             // bumped by every change of block_pc: part of a HIP graph's key
     msdr_chain_info info;
     // optional per-launch timing of the main kernel
     bool timing;
@@ -2493,6 +2498,8 @@ static void chain_pc_row_from(msdr_chain *c, uint32_t ch, const int16_t *ci, con
 // tests/test_gpu_taps_per_channel_f32.py and tests/test_f32pc_cases.py.)
 static const char kPcfKernelName[] = "chain_f32pc_kernel (per-channel taps)";
 static const char kPcfoKernelName[] = "chain_f32pco_kernel (per-channel taps and oscillator tables)";
+static const char kPcbKernelName[] = "chain_f32pcb_kernel (per-channel taps, one launch per block)";
+static const char kPcboKernelName[] = "chain_f32pcb_kernel (per-channel taps and oscillator tables, one launch per block)";
 static void chain_pcf_row_from(msdr_chain *c, uint32_t ch, const float *ci, const float *cq)
 {
     float *row = c->h_pcf_taps.data() + (size_t)ch * 2 * c->pc_np;
@@ -3674,6 +3681,16 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     // otherwise the fp32 audio goes to a scratch block batch and is converted last.
     void *fout = d_audio;                                        // where the fp32 passes of this call read and write the audio
     bool i16_via_scratch = false;
+    // ---- msdr_chain_set_block_kernel: the whole block-cadence call of a per-channel chain in one launch (msdr_chain_f32pcb.hiph) -- where no
+    // oscillator generation is pending, nothing runs behind the kernel but a CMSIS-order cascade, and one wave's LDS fits
+    bool use_pcb = false;
+    PcLaunch pcb_geo;
+    memset(&pcb_geo, 0, sizeof pcb_geo);
+    if (use_pcf && c->block_pc && mb_n_ok((long long)n_samples) && !p.osc_hist && !(c->f32_pll || c->aux != nullptr || chain_summary(c).any_anr) &&
+        (!c->seq_bq || c->seq_bq->stages == 0 || c->seq_bq->sequential))
+        use_pcb = chain_f32pcb_lds((int)n_samples, c->pc_np, c->mixer == kMixerFs4 ? 0 : (int)c->osc_len, &pcb_geo);
+    if (use_pcb) { /* (the kernel converts in its store phase: no scratch batch) */ }
+    else
     if (f32 && (c->flags & MSDR_CHAIN_OUT_I16)) {
         const bool post_active = c->f32_pll || c->aux != nullptr || chain_summary(c).any_anr;
         if (use_mfw && !c->seq_bq && !post_active) p.dbg |= kChainOutI16;
@@ -3831,6 +3848,11 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     if (c->dry_run) {
         // msdr_chain_graph_create's preparation pass: everything a block-cadence call needs from the host is in place now; say whether the
         // launches that follow are fixed (capturable into a HIP graph) -- and make none
+        if (use_pcb) {           // chain_f32pcb_kernel: one launch, its geometry fixed by the call's shape
+            if (n_samples % c->osc_len) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the oscillator's position changes from call to call at this block length: not capturable");
+            return 0;
+        }
+        if (use_pcf && c->block_pc) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the block kernel does not take this call (32 .. 512 samples, a divisor of 1024; no pending oscillator change; no PLL / LMS channels; 64 KB of LDS): chain_f32pc_kernel's launch geometry is chosen per call, not capturable");
         if (use_pcf) return fail(MSDR_STATUS_ARGUMENT_ERROR, "an fp32 chain with per-channel FIR coefficients (chain_f32pc_kernel: launch geometry chosen per call) is not capturable");
         if (use_pc) {            // chain_q15pc_kernel / chain_q15pco_kernel + the kernels behind it + the history kernel: a fixed set of launches at a block-cadence length
             if (!mb_n_ok((long long)n_samples)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "not a block-cadence call (32 .. 512 samples, a divisor of 1024): nothing to capture");
@@ -3931,6 +3953,25 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         (void)launch_chain_fold(c->ctx->stream, c->fold_P, grid, lds, p);
         flavour |= MSDR_FLAVOUR_VALU_FOLD | ((uint32_t)c->fold_P << MSDR_FLAVOUR_FOLD_PERIOD_SHIFT) | (nseg > 1 ? MSDR_FLAVOUR_SEGMENTED : 0u);
         kname = c->fold_P == 4 ? "chain_fold_kernel<4>" : c->fold_P == 2 ? "chain_fold_kernel<2>" : "chain_fold_kernel<1>";
+    }
+    else if (use_pcb) {
+        PcbParams q;
+        memset(&q, 0, sizeof q);
+        q.x = d_if; q.out = d_audio; q.hist_in = c->d_hist[c->cur]; q.hist_out = c->d_hist[c->cur ^ 1]; q.n = (int)n_samples; q.channels = (int)c->channels;
+        q.hist_len = (int)c->hist_len; q.np = c->pc_np; q.taps = c->d_pcf_taps; q.chan_mode = c->d_mode;
+        q.osc = c->opc_active ? c->d_osc_bank : (const void *)c->d_osc; q.osc_len = (int)c->osc_len; q.osc_stride = c->opc_active ? (int)c->osc_len : 0;
+        q.phase0 = (int)c->phase; q.in_scale = c->in_scale; q.out_i16 = (c->flags & MSDR_CHAIN_OUT_I16) ? 1 : 0;
+        if (c->seq_bq && c->seq_bq->stages > 0) {          // the cascade's own table and state: direct calls of the stage, unfused calls and these share them
+            q.stages = (int)c->seq_bq->stages; q.bq_state = c->seq_bq->d_state;
+            q.bq_tab = c->seq_bq->per_channel ? c->seq_bq->d_pc_coeffs : c->seq_bq->d_coeffs; q.bq_stride = c->seq_bq->per_channel ? kSbqTabFloats : 0;
+            flavour |= MSDR_FLAVOUR_SEQ_CASCADE | (c->seq_bq->per_channel ? (uint32_t)MSDR_FLAVOUR_CASCADE_PC : 0u);
+        }
+        PcLaunch geo;
+        if (launch_chain_f32pcb(c->ctx->stream, c->mixer == kMixerFs4, q, &geo) != hipSuccess)
+            return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pcb_kernel launch failed");
+        kname = c->opc_active ? kPcboKernelName : kPcbKernelName;
+        grid = geo.grid; block = geo.block; lds_used = geo.lds_bytes; nseg = 1; pc_tile = geo.tile;
+        flavour |= MSDR_FLAVOUR_BLOCK | MSDR_FLAVOUR_TAPS_PC | (c->opc_active ? (uint32_t)MSDR_FLAVOUR_OSC_PC : 0u);
     }
     else if (use_pcf) {
         PcfParams q;
@@ -4048,7 +4089,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     if (int rc = launch_check("chain_kernel")) return rc;
     if (e0) { HIP_TRY(hipEventRecord(e1, c->ctx->stream)); c->events.emplace_back(e0, e1); }
 
-    if (c->seq_bq)             // F32, ill-conditioned cascade: arm_biquad_cascade_df1_f32 in CMSIS order, in place on the audio
+    if (c->seq_bq && !use_pcb) // F32, ill-conditioned cascade: arm_biquad_cascade_df1_f32 in CMSIS order, in place on the audio (chain_f32pcb_kernel ran it itself)
         { if (int rc = msdr_biquad_df1_f32_process(c->seq_bq, (const float *)fout, (float *)fout, (uint32_t)n_samples)) return rc; flavour |= MSDR_FLAVOUR_SEQ_CASCADE | (c->seq_bq->per_channel ? (uint32_t)MSDR_FLAVOUR_CASCADE_PC : 0u); }
 
     if (pll_active)            // SYNCAM channels: I (in d_audio) and Q (scratch) -> PLL demodulator -> audio, before the biquad nodes
@@ -4107,7 +4148,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         if (int rc = launch_check("f32_to_q15_kernel")) return rc;
     }
 
-    if (!use_mfb && !use_qb) {            // (the block kernels write the next history themselves)
+    if (!use_mfb && !use_qb && !use_pcb) {            // (the block kernels write the next history themselves)
         hipLaunchKernelGGL((history_kernel<int16_t>), dim3(grid_1d((long long)c->channels * c->hist_len)), dim3(256), 0, c->ctx->stream,
                            d_if, (const int16_t *)c->d_hist[c->cur], c->d_hist[c->cur ^ 1], (long long)n_samples, (int)c->hist_len,
                            (int)c->channels);
@@ -4121,7 +4162,8 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
             if (int rc = chain_leave_generic(c)) return rc;
     }
 
-    // (the cascade's kernel is always named in full: a main kernel's name that leaves no room for it in info.kernel is cut short instead)
+    // (the cascade's kernel is always named in full: a main kernel's name that leaves no room for it in info.kernel is cut short instead;
+    //  behind chain_f32pcb_kernel it names the cascade that ran as that kernel's second phase)
     const char *bq_name = !c->seq_bq ? "" : c->seq_bq->per_channel ? " + biquad_df1_seq_pc_kernel" : c->seq_bq->sequential ? " + biquad_df1_seq_kernel" : " + biquad_df1_kernel";
     snprintf(c->info.kernel, sizeof c->info.kernel, "%.*s%s", (int)(sizeof c->info.kernel - 1 - strlen(bq_name)), kname, bq_name);
     c->info.grid = grid; c->info.block = block; c->info.lds_bytes = (uint32_t)lds_used;
@@ -4154,12 +4196,25 @@ struct msdr_chain_graph {
     bool k_nodes_pc;       // the biquad nodes ran per channel (a kernel of its own behind the demodulator kernel) when the launches were captured
     bool k_osc_pc;         // the chain ran chain_q15pco_kernel (per-channel oscillator tables) when the launches were captured
     uint64_t k_osc_gen;    // the bank as it was: every later change makes a generation, which the captured launches know nothing of
+    // chain_f32pcb_kernel (msdr_chain_set_block_kernel): the captured launches read the per-channel tables through these pointers -- a row
+    // rewritten in place (msdr_chain_set_taps_channels_f32, msdr_chain_set_biquad_coeffs_channels) is what the next replay filters with, a table
+    // that moved or changed its size is not -- and they are the launches of the configuration these epochs stand for
+    bool k_block_pc;
+    uint64_t k_block_epoch, k_anr_gen;
+    const void *k_pcf_taps, *k_osc_bank, *k_bq_tab, *k_bq_state;
+    size_t k_pcf_cap, k_osc_cap, k_bq_cap;
 };
 static void chain_graph_key(const msdr_chain *c, msdr_chain_graph *g)
 {
     g->k_hist = c->d_hist[c->cur]; g->k_state = c->d_bq_state; g->k_tab = c->arith == MSDR_ARITH_F32 ? (const void *)c->d_mf_tab : (const void *)c->d_qm_tab;
     g->k_tiles = c->d_btiles; g->k_cur = c->cur; g->k_mode_gen = c->mode_gen; g->k_nodes_pc = chain_nodes_per_channel(c); g->k_taps_pc = c->pc_active;
     g->k_rebuild_gen = c->rebuild_gen; g->k_mode = c->d_mode; g->k_osc = c->d_osc; g->k_osc_pc = c->opc_active; g->k_osc_gen = c->osc_gen;
+    g->k_block_pc = c->arith == MSDR_ARITH_F32 && c->pc_active && c->block_pc; g->k_block_epoch = c->block_epoch; g->k_anr_gen = c->anr_gen;
+    g->k_pcf_taps = c->d_pcf_taps; g->k_pcf_cap = c->pc_active ? (size_t)c->channels * 2 * (size_t)c->pc_np : 0;
+    g->k_osc_bank = c->d_osc_bank; g->k_osc_cap = c->opc_active ? (size_t)c->channels * c->osc_len : 0;
+    const msdr_biquad_df1_f32 *S = c->seq_bq;
+    g->k_bq_tab = !S ? nullptr : S->per_channel ? (const void *)S->d_pc_coeffs : (const void *)S->d_coeffs; g->k_bq_state = S ? S->d_state : nullptr;
+    g->k_bq_cap = !S ? 0 : S->per_channel ? (size_t)S->channels * kSbqTabFloats : (size_t)5 * S->stages;
 }
 
 extern "C" int msdr_chain_graph_create(msdr_chain *c, uint32_t ticks, const int16_t *const *d_if, void *const *d_audio, uint64_t n_samples, msdr_chain_graph **out)
@@ -4222,6 +4277,15 @@ extern "C" int msdr_chain_graph_launch(msdr_chain_graph *g)
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "channels got FIR coefficients of their own since this graph was made (its captured launches share tap sets between channels): make the graph again");
     if (now.k_osc_pc != g->k_osc_pc || now.k_osc_gen != g->k_osc_gen)
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "channels got oscillator tables of their own, or the bank of tables changed, since this graph was made (the history holds samples of the earlier tables): make the graph again");
+    if (g->k_block_pc || now.k_block_pc) {          // the graph holds chain_f32pcb_kernel launches (or the chain would make them now)
+        if (now.k_block_pc != g->k_block_pc || now.k_block_epoch != g->k_block_epoch)
+            return fail(MSDR_STATUS_ARGUMENT_ERROR, "msdr_chain_set_block_kernel changed the chain's block-cadence kernel since this graph was made: make the graph again");
+        if (now.k_anr_gen != g->k_anr_gen)
+            return fail(MSDR_STATUS_ARGUMENT_ERROR, "msdr_chain_set_anr ran since this graph was made (LMS channels run behind the kernel, which the captured launches know nothing of): make the graph again");
+        if (now.k_pcf_taps != g->k_pcf_taps || now.k_pcf_cap != g->k_pcf_cap || now.k_osc_bank != g->k_osc_bank || now.k_osc_cap != g->k_osc_cap ||
+            now.k_bq_tab != g->k_bq_tab || now.k_bq_cap != g->k_bq_cap || now.k_bq_state != g->k_bq_state)
+            return fail(MSDR_STATUS_ARGUMENT_ERROR, "a per-channel table or the cascade's state moved since this graph was made (a first per-channel call, a segmented direct call of the cascade): make the graph again");
+    }
     HIP_TRY(hipGraphLaunch(g->exec, c->ctx->stream));
     c->gen += g->ticks;                                     // (an even number of calls: buffers, table position and caches stay as they are)
     return 0;
@@ -4462,6 +4526,7 @@ static int chain_rebuild(msdr_chain *c, const ChainCfgStore &edited, void **stea
     std::swap(n->d_pcf_taps, c->d_pcf_taps); n->h_pcf_taps.swap(c->h_pcf_taps); n->seq_forced = c->seq_forced;
     // ... and so does the bank of per-channel oscillator tables (its pending generations went over with osc_pending above)
     n->opc_active = c->opc_active; std::swap(n->d_osc_bank, c->d_osc_bank); n->osc_gen = c->osc_gen;
+    n->block_pc = c->block_pc; n->block_epoch = c->block_epoch;          // (msdr_chain_set_block_kernel holds for the chain's life)
     std::swap(*c, *n);
     if (steal_osc) { *steal_osc = n->d_osc; n->d_osc = nullptr; }
     chain_free(n);
@@ -4642,6 +4707,17 @@ extern "C" int msdr_chain_set_taps_channels_f32(msdr_chain *c, uint32_t first_ch
         c->h_pc_own[first_channel + i] = 1;
     }
     return first_call ? chain_pc_upload(c, 0, c->channels) : chain_pc_upload(c, first_channel, count);
+}
+
+// One launch per block-cadence call of an fp32 chain in per-channel mode (chain_f32pcb_kernel); a switch of the host's, no device work
+extern "C" int msdr_chain_set_block_kernel(msdr_chain *c, int on)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (int rc = bind(c->ctx)) return rc;
+    if (c->arith != MSDR_ARITH_F32) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the block kernel belongs to F32 chains (a Q15 chain with per-channel taps replays as a graph as it is)");
+    const bool v = on != 0;
+    if (v != c->block_pc) { c->block_pc = v; c->block_epoch++; }
+    return 0;
 }
 
 // ---- per-channel oscillator tables ----
@@ -4942,6 +5018,25 @@ extern "C" int msdr_chain_get_info(msdr_chain *c, msdr_chain_info *info)
     if (!c || !info) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
     *info = c->info;
     return 0;
+}
+
+// introspection for tests: what a chain carries from call to call
+extern "C" int msdr_chain_get_fir_history(msdr_chain *c, uint32_t channel, int16_t *hist, uint32_t capacity, uint32_t *hist_len)
+{
+    if (!c || channel >= c->channels) return fail(MSDR_STATUS_ARGUMENT_ERROR, "bad argument");
+    if (int rc = bind(c->ctx)) return rc;
+    if (hist_len) *hist_len = c->hist_len;
+    if (!hist) return 0;
+    if (capacity < c->hist_len) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the history holds %u samples, room for %u given", c->hist_len, capacity);
+    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+    HIP_TRY(hipMemcpy(hist, c->d_hist[c->cur] + (size_t)channel * c->hist_len, (size_t)c->hist_len * sizeof(int16_t), hipMemcpyDeviceToHost));
+    return 0;
+}
+extern "C" int msdr_chain_get_cmsis_state(msdr_chain *c, uint32_t channel, float32_t *pState)
+{
+    if (!c || !pState || channel >= c->channels) return fail(MSDR_STATUS_ARGUMENT_ERROR, "bad argument");
+    if (c->arith != MSDR_ARITH_F32 || !c->seq_bq) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the chain's cascade does not run behind the kernel: no pState of its own");
+    return msdr_biquad_df1_f32_get_cmsis_state(c->seq_bq, channel, pState);
 }
 
 extern "C" int msdr_chain_enable_timing(msdr_chain *c, int on)

@@ -8,6 +8,7 @@
 //   msdr_chain_q15pc.hip   the Q15 chain / the arm_fir_fast_q15 stage with per-channel FIR coefficients: chain_q15pc_kernel
 //   msdr_chain_f32pc.hip   the fp32 chain / the arm_fir_f32 stage with per-channel FIR coefficients: chain_f32pc_kernel
 //   msdr_biquad_df1_pc.hip arm_biquad_cascade_df1_f32 in CMSIS order with per-channel coefficients: biquad_df1_seq_pc_kernel
+//   msdr_chain_f32pcb.hip  the fp32 chain with per-channel settings at block cadence, one launch per call: chain_f32pcb_kernel
 // Host-side geometry helpers (LDS sizes, table formats) live with the kernels' headers.  Every launcher returns the HIP error of its launch.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -64,4 +65,11 @@ hipError_t launch_chain_f32pco(hipStream_t stream, int num_cus, int time_segment
 constexpr int kSbqTabFloats = 5 * kMaxStages;      // one channel's row of the coefficient table (80 bytes: rows stay 16-byte aligned)
 hipError_t launch_biquad_df1_seq_pc(hipStream_t stream, int stages, const float *x, float *y, long long n, int channels, const float *tab,
                                     const float *state_in, float *state_out, int nseg, long long seg_len, int warm, const float *scratch);
+// ---- msdr_chain_f32pcb.hip ----
+// chain_f32pcb_kernel<CPW, FS4> (msdr_chain_f32pcb.hiph): mixer, FIR, demod, CMSIS-order cascade, fp32 / int16 store and the next history of one
+// block-cadence call (p.n = 32 .. 512, a multiple of 8) in one launch.  fs4: the Fs/4 mixer's flavour (p.osc unused).  The geometry follows
+// from (p.n, p.np, p.osc_len) alone (f32pcb_geometry); the launcher fills p.nw.  chain_f32pcb_lds: that geometry without a launch -- false where
+// one wave with one channel does not fit 64 KB of LDS (osc_len = 0: Fs/4).
+bool chain_f32pcb_lds(int n, int np, int osc_len, PcLaunch *geo);
+hipError_t launch_chain_f32pcb(hipStream_t stream, bool fs4, PcbParams p, PcLaunch *geo);
 }  // namespace msdr

@@ -158,4 +158,29 @@ struct PcfParams {
     int nw;                    // waves per workgroup
 };
 
+// chain_f32pcb_kernel (msdr_chain_f32pcb.hiph): a whole block-cadence call of the fp32 chain with per-channel settings in one launch
+struct PcbParams {
+    const int16_t *x;          // [channels][n] IF samples
+    void *out;                 // [channels][n] audio behind the cascade: float, or int16 (out_i16)
+    const int16_t *hist_in;    // [channels][hist_len] raw history, oldest first
+    int16_t *hist_out;         // [channels][hist_len] the history this call leaves (another buffer than hist_in)
+    int n;                     // 32 .. 512 samples, a multiple of 8
+    int channels;
+    int hist_len;
+    int np;                    // taps per row of the table: numTaps front-padded with zeros to a multiple of 4
+    const float *taps;         // [channels][2][np] (I row, Q row; CMSIS order)
+    const int *chan_mode;      // [channels]
+    const void *osc;           // float2 pairs {osc_q ("cos"), osc_i ("sin")}: channel ch reads osc_len pairs from pair ch * osc_stride on (unused: Fs/4)
+    int osc_len;
+    int osc_stride;            // 0: one table shared by all channels; osc_len: a bank [channels][osc_len]
+    int phase0;                // (absolute index of sample 0 of this call) mod osc_len (mod 4 for Fs/4)
+    float in_scale;
+    int stages;                // 0 .. kMaxStages cascade sections in CMSIS order
+    const float *bq_tab;       // channel ch reads 5 x stages coefficients from float ch * bq_stride on
+    int bq_stride;             // 0: one row shared by all channels; kSbqTabFloats: a table [channels][kSbqTabFloats]
+    float *bq_state;           // [channels][kBqStateFloats]: pState per stage, read and written in place
+    int out_i16;               // `out` is int16, converted as arm_float_to_q15
+    int nw;                    // waves per workgroup
+};
+
 }  // namespace msdr

@@ -269,7 +269,8 @@ private:
 // ------------------------------------------------------------------------------------------------
 // AudioSDRDemodulator -- the whole demodulation() step (+ optional biquad nodes) as ONE graph node and ONE
 // kernel per tick: IF block batch in, audio block batch out.  Configure with a msdr_chain_config whose
-// `channels` equals AudioGPU.channels() and whose arith is MSDR_ARITH_Q15 (int16 audio blocks).
+// `channels` equals AudioGPU.channels() and whose arith is MSDR_ARITH_Q15, or MSDR_ARITH_F32 with MSDR_CHAIN_OUT_I16 in `flags` (the
+// audio blocks are int16 either way: an fp32 chain converts as arm_float_to_q15 does).
 // ------------------------------------------------------------------------------------------------
 class AudioSDRDemodulator : public AudioStream {
 public:
@@ -278,7 +279,8 @@ public:
     int begin(const msdr_chain_config &cfg)
     {
         if (chain) { msdr_chain_destroy(chain); chain = nullptr; }
-        if (cfg.arith != MSDR_ARITH_Q15 || cfg.channels != AudioGPU.channels()) return MSDR_STATUS_ARGUMENT_ERROR;
+        const bool i16_audio = cfg.arith == MSDR_ARITH_Q15 || (cfg.arith == MSDR_ARITH_F32 && (cfg.flags & MSDR_CHAIN_OUT_I16));
+        if (!i16_audio || cfg.channels != AudioGPU.channels()) return MSDR_STATUS_ARGUMENT_ERROR;
         num_taps = cfg.num_taps;
         return msdr_chain_create(AudioGPU.context(), &cfg, &chain);
     }
@@ -311,6 +313,20 @@ public:
     {
         return chain ? msdr_chain_set_taps_channels(chain, channel, 1, coeffs_i, coeffs_q) : MSDR_STATUS_ARGUMENT_ERROR;
     }
+    // the same on an fp32 chain (msdr_chain_set_taps_channels_f32): float rows in CMSIS order
+    int setTapsChannelF32(uint32_t channel, const float *coeffs_i, const float *coeffs_q = nullptr)
+    {
+        return chain ? msdr_chain_set_taps_channels_f32(chain, channel, 1, coeffs_i, coeffs_q) : MSDR_STATUS_ARGUMENT_ERROR;
+    }
+    // one receiver's cascade on an fp32 chain: 5 x num_biquad_stages coefficients, tune()'s notch (msdr_chain_set_biquad_coeffs_channels)
+    int setBiquadCoeffsChannel(uint32_t channel, const float *coeffs)
+    {
+        return chain ? msdr_chain_set_biquad_coeffs_channels(chain, channel, 1, coeffs) : MSDR_STATUS_ARGUMENT_ERROR;
+    }
+    // fp32 chain in per-channel mode: the whole tick in one launch (msdr_chain_set_block_kernel: chain_f32pcb_kernel)
+    int setBlockKernel(bool on) { return chain ? msdr_chain_set_block_kernel(chain, on ? 1 : 0) : MSDR_STATUS_ARGUMENT_ERROR; }
+    // which kernel the last tick ran (msdr_chain_get_info)
+    int info(msdr_chain_info *out) { return chain ? msdr_chain_get_info(chain, out) : MSDR_STATUS_ARGUMENT_ERROR; }
     // calc_demod_filter() of receiver `channel` (Minimal-SDR.ino:221-223): calc_FIR_coeffs(FIR_AM_coeffs, numTaps, filter_bandwidth, 70, 0, 0.0, 24000)
     int setBandwidthChannel(uint32_t channel, float bandwidth_hz)
     {

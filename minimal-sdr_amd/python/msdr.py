@@ -100,7 +100,10 @@ def load_library(path=None):
                        ("msdr_fir_f32_set_coeffs_channels", [_p, C.c_uint32, C.c_uint32, _p]),
                        ("msdr_chain_set_biquad_coeffs_channels", [_p, C.c_uint32, C.c_uint32, _p]),
                        ("msdr_biquad_df1_f32_set_coeffs_channels", [_p, C.c_uint32, C.c_uint32, _p]),
-                       ("msdr_chain_set_osc_channels", [_p, C.c_uint32, C.c_uint32, _p, _p])):
+                       ("msdr_chain_set_osc_channels", [_p, C.c_uint32, C.c_uint32, _p, _p]),
+                       ("msdr_chain_set_block_kernel", [_p, C.c_int]),
+                       ("msdr_chain_get_fir_history", [_p, C.c_uint32, _p, C.c_uint32, _p]),
+                       ("msdr_chain_get_cmsis_state", [_p, C.c_uint32, _p])):
             if hasattr(_lib, n):
                 getattr(_lib, n).argtypes = sig
         _lib.msdr_chain_set_biquad_coeffs.argtypes = [_p, _p]
@@ -804,6 +807,25 @@ class Chain(_Instance):
         if oi.shape != oq.shape:
             raise ValueError("set_osc_channels: osc_i %s and osc_q %s differ in shape" % ((oi.shape,), (oq.shape,)))
         _ck(self.ctx.lib.msdr_chain_set_osc_channels(self.h, C.c_uint32(first_channel), C.c_uint32(oi.shape[0]), _hp(oi), _hp(oq)))
+
+    def set_block_kernel(self, on):
+        """F32: a block-cadence call of a chain in per-channel mode as ONE launch (chain_f32pcb_kernel: demodulator, CMSIS-order cascade, int16
+        conversion and the next history), bit-identical to the unfused launches, and capturable by graph().  Off by default; every state kept."""
+        _ck(self.ctx.lib.msdr_chain_set_block_kernel(self.h, C.c_int(1 if on else 0)))
+
+    def fir_history(self, channel):
+        """the raw int16 samples the chain carries for `channel`, oldest first (msdr_chain_get_fir_history)"""
+        n = C.c_uint32(0)
+        _ck(self.ctx.lib.msdr_chain_get_fir_history(self.h, C.c_uint32(channel), None, C.c_uint32(0), C.byref(n)))
+        h = np.zeros(n.value, np.int16)
+        _ck(self.ctx.lib.msdr_chain_get_fir_history(self.h, C.c_uint32(channel), _hp(h), C.c_uint32(h.size), None))
+        return h
+
+    def cmsis_state(self, channel):
+        """pState of the cascade behind the kernel for `channel`: 4 floats per stage (msdr_chain_get_cmsis_state)"""
+        st = np.zeros(4 * max(self.stages, 1), np.float32)
+        _ck(self.ctx.lib.msdr_chain_get_cmsis_state(self.h, C.c_uint32(channel), _hp(st)))
+        return st[:4 * self.stages]
 
     def set_node_coefficients(self, node, stage, coef):
         c = np.ascontiguousarray(coef, np.int32)
