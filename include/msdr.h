@@ -599,7 +599,35 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   Graphs, Q15: a msdr_chain_graph made before the first call is refused at launch afterwards; one made in this mode is accepted under the
  *   conditions of per-channel taps (block lengths 32 .. 512, no PLL / LMS channels, no pending generation, the oscillator period dividing
  *   n_samples), replays bit-exactly, and is refused after any later msdr_chain_set_osc_channels / msdr_chain_set_osc.  F32:
- *   msdr_chain_graph_create is refused, as on every chain with the cascade behind the kernel. */
+ *   msdr_chain_graph_create is refused, as on every chain with the cascade behind the kernel.
+ * msdr_chain_set_input_rows: one antenna, one ADC stream (or a handful), and a bank of receivers tuned to different stations inside it --
+ *   the case per-channel oscillator tables exist for.  input_row: a HOST array [channels], read during the call; entry c names the row of
+ *   d_if that receiver c hears.  From the next msdr_chain_process / msdr_chain_graph_create on, d_if is [n_inputs][n_samples] row-major
+ *   (d_audio stays [channels][n_samples]) and receiver c produces, bit for bit, what it would produce if d_if[c] held a copy of row
+ *   input_row[c].  Every state is kept: FIR history, node and cascade state, PLL / LMS state, the table position, pending oscillator
+ *   generations.  The FIR history stays PER CHANNEL -- it holds what that receiver heard -- so a live change of the map is an antenna switch:
+ *   the receiver carries on over its own old history, and msdr_chain_get_fir_history, msdr_chain_init_fir, msdr_chain_reset, the oscillator
+ *   generations and the move between chain_f32pcb_kernel and the unfused launches work unchanged.  n_inputs == 0 (with any input_row) returns
+ *   the chain to the identity: d_if is [channels][n_samples] again, states kept.  Stream-ordered; like its siblings it may synchronise the
+ *   stream.  A NULL chain, n_inputs > 0 with a NULL array and an entry >= n_inputs are MSDR_STATUS_ARGUMENT_ERROR, nothing changed.
+ *   From the first call on (whatever its n_inputs), for the rest of its life, the chain runs the per-channel kernel family
+ *   (chain_q15pc_kernel / chain_q15pco_kernel; chain_f32pc_kernel / chain_f32pco_kernel / chain_f32pcb_kernel), whose kernels take the map as
+ *   an operand: a chain not yet in per-channel mode enters it exactly as the first msdr_chain_set_osc_channels / set_taps_channels[_f32] call
+ *   does (the tap table filled from the shared tap sets; F32: the cascade behind the kernel in CMSIS order with its state, with that move's
+ *   one refusal and the per-channel kernel's tap limit).  The call combines in any order with msdr_chain_set_taps_channels[_f32],
+ *   set_osc_channels, set_biquad_coeffs_channels, set_node_coefficients_channels and set_block_kernel; the map survives all of those and
+ *   msdr_chain_set_taps / set_osc / set_mode / set_anr / init_fir / reset.  msdr_chain_get_info().kernel names the same kernels as before; on
+ *   fp32 chains flavour carries MSDR_FLAVOUR_SHARED_IF while a map is in force.
+ *   fp32 chains whose PLL / LMS channels run through the auxiliary chain are out of scope (it gathers its rows from d_if by channel and is
+ *   built from the shared tables): the call is refused (ARGUMENT_ERROR, nothing changed) on an fp32 chain created with
+ *   MSDR_CHAIN_SYNCAM_PLL or with any LMS channel on, and while a map is in force msdr_chain_set_anr with any channel on is refused on an
+ *   fp32 chain.  Q15 chains have no such limit: their PLL / LMS / node kernels work on the demodulator's output.
+ *   Graphs: a msdr_chain_graph made before a msdr_chain_set_input_rows call is refused at launch after it -- after ANY later call, the return
+ *   to the identity included.  One made while a map is in force is accepted under the conditions per-channel chains have already (Q15: those
+ *   of per-channel taps / oscillator tables; F32: only with msdr_chain_set_block_kernel on), its d_if[k] are [n_inputs][n_samples], and it
+ *   replays bit-exactly.
+ *   Out of scope: the uniform (matrix-core) kernels, the msdr_fir_* stage instances, fp32 chains with PLL / LMS channels, and sharing one
+ *   history per input row (the histories cost channels x hist_len x 2 bytes as before). */
 int msdr_chain_set_taps(msdr_chain *chain, uint32_t tapset, const void *coeffs_i, const void *coeffs_q);
 int msdr_chain_set_taps_channels(msdr_chain *chain, uint32_t first_channel, uint32_t count,
                                  const q15_t *coeffs_i, const q15_t *coeffs_q);
@@ -615,6 +643,7 @@ int msdr_chain_set_osc(msdr_chain *chain, const void *osc_i, const void *osc_q);
 int msdr_chain_set_osc_channels(msdr_chain *chain, uint32_t first_channel, uint32_t count,
                                 const void *osc_i, const void *osc_q);
 int msdr_chain_set_block_kernel(msdr_chain *chain, int on);   /* F32 chains; default off */
+int msdr_chain_set_input_rows(msdr_chain *chain, uint32_t n_inputs, const uint32_t *input_row);
 /* ANR_on per channel (host array of `channels` values, or NULL: anr_on_all for every channel); the LMS filter then runs between
  * the demodulator and the biquad nodes / cascade (Minimal-SDR.ino:702-770).  Its state is created on first use and cleared by
  * msdr_chain_reset() (not by msdr_chain_init_fir()).  Q15 chains: as the reference, on the int16 audio.  F32 chains (an
@@ -660,6 +689,9 @@ enum { MSDR_FLAVOUR_CASCADE_PC = 0x10000u };
 /* And another: the demodulator kernel mixed every channel with its own oscillator row -- chain_f32pco_kernel, msdr_chain_set_osc_channels
  * (always beside MSDR_FLAVOUR_TAPS_PC). */
 enum { MSDR_FLAVOUR_OSC_PC = 0x20000u };
+/* And another: the demodulator kernel read its IF samples through an input map -- msdr_chain_set_input_rows with n_inputs > 0, d_if
+ * [n_inputs][n_samples] (always beside MSDR_FLAVOUR_TAPS_PC). */
+enum { MSDR_FLAVOUR_SHARED_IF = 0x40000u };
 int msdr_chain_get_info(msdr_chain *chain, msdr_chain_info *info);
 /* Introspection for tests: what a chain carries from call to call.  get_fir_history: *hist_len = the raw int16 samples the chain keeps per
  * channel (a property of the kernels it runs), and, where hist != NULL (capacity >= that many), channel's samples, oldest first.

@@ -2468,6 +2468,12 @@ struct msdr_chain {
     // every other call runs the unfused launches over the same history, table position and cascade state.  Off by default.
     bool block_pc = false;
     uint64_t block_epoch = 0;             // bumped by every change of block_pc: part of a HIP graph's key
+    // msdr_chain_set_input_rows: receiver ch hears row h_in_row[ch] of a d_if that is [n_inputs][n_samples]; n_inputs == 0: the identity, d_if
+    // [channels][n_samples].  The per-channel kernels and history_rows_kernel read the device table, which later calls rewrite in place.
+    // The FIR history stays per channel, so nothing else of the chain knows about the map.
+    uint32_t n_inputs = 0;
+    int *d_in_row = nullptr;              // [channels], allocated by the first call; read by the kernels only while n_inputs > 0
+    uint64_t in_row_epoch = 0;            // bumped by every msdr_chain_set_input_rows call: part of a HIP graph's key
     msdr_chain_info info;
     // optional per-launch timing of the main kernel
     bool timing;
@@ -2556,7 +2562,7 @@ static void chain_free(msdr_chain *c)
     hipFree(c->d_anr_on);
     for (auto &e : c->events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (auto &o : c->osc_pending) hipFree(o.d_tab);
-    hipFree(c->d_f32_scratch); hipFree(c->d_osc_hist); hipFree(c->d_btiles); hipFree(c->d_pc_taps); hipFree(c->d_pcf_taps); hipFree(c->d_osc_bank);
+    hipFree(c->d_f32_scratch); hipFree(c->d_osc_hist); hipFree(c->d_btiles); hipFree(c->d_pc_taps); hipFree(c->d_pcf_taps); hipFree(c->d_osc_bank); hipFree(c->d_in_row);
     delete c;
 }
 
@@ -3961,6 +3967,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         q.hist_len = (int)c->hist_len; q.np = c->pc_np; q.taps = c->d_pcf_taps; q.chan_mode = c->d_mode;
         q.osc = c->opc_active ? c->d_osc_bank : (const void *)c->d_osc; q.osc_len = (int)c->osc_len; q.osc_stride = c->opc_active ? (int)c->osc_len : 0;
         q.phase0 = (int)c->phase; q.in_scale = c->in_scale; q.out_i16 = (c->flags & MSDR_CHAIN_OUT_I16) ? 1 : 0;
+        q.in_row = c->n_inputs ? c->d_in_row : nullptr;
         if (c->seq_bq && c->seq_bq->stages > 0) {          // the cascade's own table and state: direct calls of the stage, unfused calls and these share them
             q.stages = (int)c->seq_bq->stages; q.bq_state = c->seq_bq->d_state;
             q.bq_tab = c->seq_bq->per_channel ? c->seq_bq->d_pc_coeffs : c->seq_bq->d_coeffs; q.bq_stride = c->seq_bq->per_channel ? kSbqTabFloats : 0;
@@ -3971,7 +3978,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
             return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pcb_kernel launch failed");
         kname = c->opc_active ? kPcboKernelName : kPcbKernelName;
         grid = geo.grid; block = geo.block; lds_used = geo.lds_bytes; nseg = 1; pc_tile = geo.tile;
-        flavour |= MSDR_FLAVOUR_BLOCK | MSDR_FLAVOUR_TAPS_PC | (c->opc_active ? (uint32_t)MSDR_FLAVOUR_OSC_PC : 0u);
+        flavour |= MSDR_FLAVOUR_BLOCK | MSDR_FLAVOUR_TAPS_PC | (c->opc_active ? (uint32_t)MSDR_FLAVOUR_OSC_PC : 0u) | (c->n_inputs ? (uint32_t)MSDR_FLAVOUR_SHARED_IF : 0u);
     }
     else if (use_pcf) {
         PcfParams q;
@@ -3979,6 +3986,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         q.x = d_if; q.out = (float *)fout; q.hist_in = c->d_hist[c->cur]; q.n = (long long)n_samples; q.channels = (int)c->channels;
         q.hist_len = (int)c->hist_len; q.np = c->pc_np; q.taps = c->d_pcf_taps; q.chan_mode = c->d_mode; q.mixer = c->mixer; q.osc = c->d_osc;
         q.osc_len = (int)c->osc_len; q.phase0 = (int)c->phase; q.in_scale = c->in_scale; q.osc_hist = p.osc_hist;
+        q.in_row = c->n_inputs ? c->d_in_row : nullptr;
         PcLaunch geo;
         if (c->opc_active) {          // per-channel oscillator tables: the bank in place of the shared table
             q.osc = c->d_osc_bank;
@@ -3991,7 +3999,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
             kname = kPcfKernelName;
         }
         grid = geo.grid; block = geo.block; lds_used = geo.lds_bytes; nseg = geo.nseg; pc_tile = geo.tile;
-        flavour |= MSDR_FLAVOUR_TAPS_PC | (geo.nseg > 1 ? MSDR_FLAVOUR_SEGMENTED : 0u);
+        flavour |= MSDR_FLAVOUR_TAPS_PC | (geo.nseg > 1 ? MSDR_FLAVOUR_SEGMENTED : 0u) | (c->n_inputs ? (uint32_t)MSDR_FLAVOUR_SHARED_IF : 0u);
     }
     else if (f32) { (void)launch_chain_generic(c->ctx->stream, false, grid, lds, p); if (nseg > 1) flavour |= MSDR_FLAVOUR_SEGMENTED; }
     else if (use_qb) {
@@ -4072,6 +4080,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         q.x = d_if; q.out = (short *)d_audio; q.hist_in = c->d_hist[c->cur]; q.n = (long long)n_samples; q.channels = (int)c->channels;
         q.hist_len = (int)c->hist_len; q.np = c->pc_np; q.taps = c->d_pc_taps; q.chan_mode = c->d_mode; q.mixer = c->mixer; q.osc = c->d_osc;
         q.osc_len = (int)c->osc_len; q.phase0 = (int)c->phase; q.sqrt_kind = c->sqrt_kind; q.syncam_q = p.syncam_q; q.osc_hist = p.osc_hist;
+        q.in_row = c->n_inputs ? c->d_in_row : nullptr;
         PcLaunch geo;
         if (c->opc_active) {          // per-channel oscillator tables: the bank in place of the shared table
             q.osc = c->d_osc_bank;
@@ -4148,6 +4157,12 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         if (int rc = launch_check("f32_to_q15_kernel")) return rc;
     }
 
+    if (!use_mfb && !use_qb && !use_pcb && c->n_inputs) {          // msdr_chain_set_input_rows: each channel's history from the row it heard
+        hipLaunchKernelGGL((history_rows_kernel<int16_t>), dim3(grid_1d((long long)c->channels * c->hist_len)), dim3(256), 0, c->ctx->stream,
+                           d_if, (const int16_t *)c->d_hist[c->cur], c->d_hist[c->cur ^ 1], (long long)n_samples, (int)c->hist_len,
+                           (int)c->channels, (const int *)c->d_in_row);
+        if (int rc = launch_check("history_rows_kernel")) return rc;
+    } else
     if (!use_mfb && !use_qb && !use_pcb) {            // (the block kernels write the next history themselves)
         hipLaunchKernelGGL((history_kernel<int16_t>), dim3(grid_1d((long long)c->channels * c->hist_len)), dim3(256), 0, c->ctx->stream,
                            d_if, (const int16_t *)c->d_hist[c->cur], c->d_hist[c->cur ^ 1], (long long)n_samples, (int)c->hist_len,
@@ -4201,6 +4216,7 @@ struct msdr_chain_graph {
     // that moved or changed its size is not -- and they are the launches of the configuration these epochs stand for
     bool k_block_pc;
     uint64_t k_block_epoch, k_anr_gen;
+    uint64_t k_in_row_epoch;   // msdr_chain_set_input_rows calls so far: each changes what the captured d_if pointers are taken to be
     const void *k_pcf_taps, *k_osc_bank, *k_bq_tab, *k_bq_state;
     size_t k_pcf_cap, k_osc_cap, k_bq_cap;
 };
@@ -4210,6 +4226,7 @@ static void chain_graph_key(const msdr_chain *c, msdr_chain_graph *g)
     g->k_tiles = c->d_btiles; g->k_cur = c->cur; g->k_mode_gen = c->mode_gen; g->k_nodes_pc = chain_nodes_per_channel(c); g->k_taps_pc = c->pc_active;
     g->k_rebuild_gen = c->rebuild_gen; g->k_mode = c->d_mode; g->k_osc = c->d_osc; g->k_osc_pc = c->opc_active; g->k_osc_gen = c->osc_gen;
     g->k_block_pc = c->arith == MSDR_ARITH_F32 && c->pc_active && c->block_pc; g->k_block_epoch = c->block_epoch; g->k_anr_gen = c->anr_gen;
+    g->k_in_row_epoch = c->in_row_epoch;
     g->k_pcf_taps = c->d_pcf_taps; g->k_pcf_cap = c->pc_active ? (size_t)c->channels * 2 * (size_t)c->pc_np : 0;
     g->k_osc_bank = c->d_osc_bank; g->k_osc_cap = c->opc_active ? (size_t)c->channels * c->osc_len : 0;
     const msdr_biquad_df1_f32 *S = c->seq_bq;
@@ -4277,6 +4294,8 @@ extern "C" int msdr_chain_graph_launch(msdr_chain_graph *g)
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "channels got FIR coefficients of their own since this graph was made (its captured launches share tap sets between channels): make the graph again");
     if (now.k_osc_pc != g->k_osc_pc || now.k_osc_gen != g->k_osc_gen)
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "channels got oscillator tables of their own, or the bank of tables changed, since this graph was made (the history holds samples of the earlier tables): make the graph again");
+    if (now.k_in_row_epoch != g->k_in_row_epoch)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "msdr_chain_set_input_rows ran since this graph was made (its captured launches read d_if by the rows of that time): make the graph again");
     if (g->k_block_pc || now.k_block_pc) {          // the graph holds chain_f32pcb_kernel launches (or the chain would make them now)
         if (now.k_block_pc != g->k_block_pc || now.k_block_epoch != g->k_block_epoch)
             return fail(MSDR_STATUS_ARGUMENT_ERROR, "msdr_chain_set_block_kernel changed the chain's block-cadence kernel since this graph was made: make the graph again");
@@ -4527,6 +4546,7 @@ static int chain_rebuild(msdr_chain *c, const ChainCfgStore &edited, void **stea
     // ... and so does the bank of per-channel oscillator tables (its pending generations went over with osc_pending above)
     n->opc_active = c->opc_active; std::swap(n->d_osc_bank, c->d_osc_bank); n->osc_gen = c->osc_gen;
     n->block_pc = c->block_pc; n->block_epoch = c->block_epoch;          // (msdr_chain_set_block_kernel holds for the chain's life)
+    n->n_inputs = c->n_inputs; std::swap(n->d_in_row, c->d_in_row); n->in_row_epoch = c->in_row_epoch;       // (the input map too)
     std::swap(*c, *n);
     if (steal_osc) { *steal_osc = n->d_osc; n->d_osc = nullptr; }
     chain_free(n);
@@ -4717,6 +4737,39 @@ extern "C" int msdr_chain_set_block_kernel(msdr_chain *c, int on)
     if (c->arith != MSDR_ARITH_F32) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the block kernel belongs to F32 chains (a Q15 chain with per-channel taps replays as a graph as it is)");
     const bool v = on != 0;
     if (v != c->block_pc) { c->block_pc = v; c->block_epoch++; }
+    return 0;
+}
+
+// One antenna stream (or a few) feeds the bank: receiver ch hears row input_row[ch] of d_if.  The map is a device table the per-channel
+// kernels read; everything the chain carries stays per channel, so the call touches nothing else.  Everything that can fail happens before
+// anything changes.
+extern "C" int msdr_chain_set_input_rows(msdr_chain *c, uint32_t n_inputs, const uint32_t *input_row)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (int rc = bind(c->ctx)) return rc;
+    if (n_inputs > 0 && !input_row) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null input-row array");
+    if (n_inputs > 0x7fffffffu) return fail(MSDR_STATUS_ARGUMENT_ERROR, "n_inputs %u: too many rows", n_inputs);
+    for (uint32_t ch = 0; n_inputs > 0 && ch < c->channels; ch++)
+        if (input_row[ch] >= n_inputs) return fail(MSDR_STATUS_ARGUMENT_ERROR, "input_row[%u] = %u, but d_if has %u rows; nothing changed", ch, input_row[ch], n_inputs);
+    const bool f32 = c->arith == MSDR_ARITH_F32;
+    if (f32) {
+        // PLL / LMS channels of an fp32 chain run through an auxiliary chain that gathers its rows from d_if by channel (chain_post_run)
+        if (c->f32_pll) return fail(MSDR_STATUS_ARGUMENT_ERROR, "input rows: not on an fp32 chain created with MSDR_CHAIN_SYNCAM_PLL (its PLL channels run through an auxiliary chain that gathers d_if by channel); nothing changed");
+        for (int v : c->h_anr) if (v > 0) return fail(MSDR_STATUS_ARGUMENT_ERROR, "input rows: not while an LMS channel of an fp32 chain is on (such channels run through an auxiliary chain that gathers d_if by channel); nothing changed");
+        if (!c->pc_active && f32pc_np((int)c->ntaps) > f32pc_max_taps(false))
+            return fail(MSDR_STATUS_ARGUMENT_ERROR, "input rows: the per-channel kernel holds filters of up to %d taps (this chain has %u); nothing changed", f32pc_max_taps(false), c->ntaps);
+    }
+    HIP_TRY(hipStreamSynchronize(c->ctx->stream));          // (a kernel in flight reads the table)
+    if (!c->d_in_row) if (int rc = dzalloc(c->ctx, (size_t)c->channels, &c->d_in_row)) return rc;
+    const bool taps_first = !c->pc_active;                  // the per-channel kernel family, entered as the other per-channel setters enter it
+    if (int rc = chain_pc_activate(c)) return rc;
+    if (taps_first) if (int rc = chain_pc_upload(c, 0, c->channels)) return rc;
+    if (n_inputs > 0) {
+        std::vector<int> rows(input_row, input_row + c->channels);
+        HIP_TRY(hipMemcpy(c->d_in_row, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice));
+    }
+    c->n_inputs = n_inputs;
+    c->in_row_epoch++;
     return 0;
 }
 
@@ -4981,9 +5034,10 @@ extern "C" int msdr_chain_set_anr(msdr_chain *c, const int32_t *anr_on, int32_t 
     if (c->arith != MSDR_ARITH_Q15) {
         // fp32 chain: the float flavour of the filter, between demodulator and cascade (chain_post_run)
         if (c->seq_bq && !c->h_bq_stages) return fail(MSDR_STATUS_ARGUMENT_ERROR, "internal: cascade coefficients not kept");
-        if ((c->seq_bq && c->seq_bq->per_channel) || c->opc_active) {      // (LMS channels run a post cascade with the chain's uniform coefficients, behind an auxiliary chain with the shared oscillator tables)
+        if ((c->seq_bq && c->seq_bq->per_channel) || c->opc_active || c->n_inputs) {      // (LMS channels run a post cascade with the chain's uniform coefficients, behind an auxiliary chain with the shared oscillator tables)
             bool any = anr_on ? false : anr_on_all > 0;
             if (anr_on) for (uint32_t ch = 0; ch < c->channels; ch++) any = any || anr_on[ch] > 0;
+            if (any && c->n_inputs) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has an input map (msdr_chain_set_input_rows): no LMS channels (they run through an auxiliary chain that gathers its rows from d_if by channel); nothing changed");
             if (any && c->opc_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has per-channel oscillator tables: no LMS channels (they run through an auxiliary chain with the shared tables); nothing changed");
             if (any) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has per-channel cascade coefficients: no LMS channels (they run a post cascade of their own); nothing changed");
         }

@@ -134,6 +134,7 @@ struct PcParams {
     int nseg;                  // time segments per channel group
     long long seg_len;         // a multiple of the tile (8 * 64 / channels per wave)
     int nw;                    // waves per workgroup
+    const int *in_row;         // [channels]: channel ch hears row in_row[ch] of x (msdr_chain_set_input_rows), x being [n_inputs][n]; null: row ch
 };
 
 // chain_f32pc_kernel (msdr_chain_f32pc.hiph): the fp32 chain / the arm_fir_f32 stage with per-channel coefficients
@@ -156,6 +157,8 @@ struct PcfParams {
     int nseg;                  // time segments per channel group
     long long seg_len;         // a multiple of the tile (8 * 64 / channels per wave)
     int nw;                    // waves per workgroup
+    const int *in_row;         // [channels]: channel ch hears row in_row[ch] of x (msdr_chain_set_input_rows), x being [n_inputs][n]; null: row ch
+                               // (chains only: the FIR stage leaves it null)
 };
 
 // chain_f32pcb_kernel (msdr_chain_f32pcb.hiph): a whole block-cadence call of the fp32 chain with per-channel settings in one launch
@@ -181,6 +184,8 @@ struct PcbParams {
     float *bq_state;           // [channels][kBqStateFloats]: pState per stage, read and written in place
     int out_i16;               // `out` is int16, converted as arm_float_to_q15
     int nw;                    // waves per workgroup
+    const int *in_row;         // [channels]: channel ch hears row in_row[ch] of x (msdr_chain_set_input_rows), x being [n_inputs][n]; null: row ch.
+                               // hist_in / hist_out stay rows of the CHANNEL: what that receiver heard
 };
 
 }  // namespace msdr

@@ -343,6 +343,14 @@ public:
     {
         return chain ? msdr_chain_set_osc_channels(chain, channel, 1, osc_i, osc_q) : MSDR_STATUS_ARGUMENT_ERROR;
     }
+    // one queue_adc feeds the bank (msdr_chain_set_input_rows): receiver c hears row rows[c] of the incoming block.  The block stays
+    // [AudioGPU.channels()][AUDIO_BLOCK_SAMPLES]; with a map in force the node reads only its first n_inputs rows (so n_inputs <= channels()).
+    // n_inputs == 0: every receiver hears its own row again
+    int setInputRows(uint32_t n_inputs, const uint32_t *rows)
+    {
+        if (!chain || n_inputs > AudioGPU.channels()) return MSDR_STATUS_ARGUMENT_ERROR;
+        return msdr_chain_set_input_rows(chain, n_inputs, rows);
+    }
     virtual void update(void)
     {
         audio_block_t *in = receiveReadOnly();

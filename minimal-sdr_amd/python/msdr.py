@@ -31,6 +31,7 @@ FLAVOUR_FOLD_PERIOD_SHIFT = 12
 FLAVOUR_TAPS_PC = 0x8000
 FLAVOUR_CASCADE_PC = 0x10000
 FLAVOUR_OSC_PC = 0x20000
+FLAVOUR_SHARED_IF = 0x40000
 FE_DCBLOCK, FE_AMP, FE_AGC, FE_ALL = 1, 2, 4, 7
 
 STATUS_ARGUMENT_ERROR, STATUS_LENGTH_ERROR, STATUS_NO_DEVICE = -1, -2, -100
@@ -102,6 +103,7 @@ def load_library(path=None):
                        ("msdr_biquad_df1_f32_set_coeffs_channels", [_p, C.c_uint32, C.c_uint32, _p]),
                        ("msdr_chain_set_osc_channels", [_p, C.c_uint32, C.c_uint32, _p, _p]),
                        ("msdr_chain_set_block_kernel", [_p, C.c_int]),
+                       ("msdr_chain_set_input_rows", [_p, C.c_uint32, _p]),
                        ("msdr_chain_get_fir_history", [_p, C.c_uint32, _p, C.c_uint32, _p]),
                        ("msdr_chain_get_cmsis_state", [_p, C.c_uint32, _p])):
             if hasattr(_lib, n):
@@ -504,6 +506,23 @@ def _osc_per_channel(what, tab, osc_len, arith):
     return np.ascontiguousarray(t, np.float32 if arith == ARITH_F32 else np.int16)
 
 
+def _input_rows(what, rows, channels, n_inputs):
+    r = np.asarray(rows)
+    if r.dtype.kind not in "iu":
+        raise ValueError("%s: row indices are integers, dtype %s given" % (what, r.dtype))
+    if r.ndim != 1 or r.shape[0] != channels:
+        raise ValueError("%s: one row index per channel (%d), shape %s given" % (what, channels, (r.shape,)))
+    if r.size and r.min() < 0:
+        raise ValueError("%s: a negative row index" % what)
+    if n_inputs is None:
+        n_inputs = int(r.max()) + 1 if r.size else 0
+    if isinstance(n_inputs, bool) or not isinstance(n_inputs, (int, np.integer)) or n_inputs <= 0 or n_inputs > 0x7fffffff:
+        raise ValueError("%s: n_inputs is a positive row count, %r given" % (what, n_inputs))
+    if r.size and r.max() >= n_inputs:
+        raise ValueError("%s: row index %d, but the input has %d rows" % (what, int(r.max()), n_inputs))
+    return np.ascontiguousarray(r, np.uint32), int(n_inputs)
+
+
 class BiquadQ15(_Instance):
     """AudioFilterBiquad: setCoefficients(stage, coef[5]) / update(), batched over channels."""
     _destroy = "msdr_biquad_q15_destroy"
@@ -812,6 +831,16 @@ class Chain(_Instance):
         """F32: a block-cadence call of a chain in per-channel mode as ONE launch (chain_f32pcb_kernel: demodulator, CMSIS-order cascade, int16
         conversion and the next history), bit-identical to the unfused launches, and capturable by graph().  Off by default; every state kept."""
         _ck(self.ctx.lib.msdr_chain_set_block_kernel(self.h, C.c_int(1 if on else 0)))
+
+    def set_input_rows(self, rows, n_inputs=None):
+        """One antenna stream (or a few) feeds the bank: channel c hears row rows[c] of a d_if that is [n_inputs, n] from the next process() /
+        graph() on (integer array [channels]; n_inputs = rows.max() + 1 unless given).  rows = None: back to the identity, d_if [channels, n].
+        Every state kept -- the FIR history stays the channel's own; the per-channel kernel family from the first call on."""
+        if rows is None:
+            _ck(self.ctx.lib.msdr_chain_set_input_rows(self.h, C.c_uint32(0), None))
+            return
+        r, ni = _input_rows("set_input_rows", rows, self.channels, n_inputs)
+        _ck(self.ctx.lib.msdr_chain_set_input_rows(self.h, C.c_uint32(ni), _hp(r)))
 
     def fir_history(self, channel):
         """the raw int16 samples the chain carries for `channel`, oldest first (msdr_chain_get_fir_history)"""
