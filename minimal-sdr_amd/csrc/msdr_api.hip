@@ -1100,7 +1100,7 @@ extern "C" int msdr_fir_q15_set_coeffs_channels(msdr_fir_q15 *S, uint32_t first_
     if (!pCoeffs) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null coefficient array");
     if (first_channel >= S->channels || count > S->channels - first_channel)
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "channels %u .. %llu of %u", first_channel, (unsigned long long)first_channel + count - 1, S->channels);
-    if (pc_lds_bytes(pc_np((int)S->ntaps), 1, true, 1) > 64 * 1024)          // (one wave's two window copies and its tap row must fit the kernel's LDS)
+    if (pc_lds_bytes(pc_np((int)S->ntaps), 1, true, 1) > kPcLdsCap)          // (one wave's two window copies and its tap row must fit the kernel's LDS)
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "per-channel coefficients: the kernel holds filters of up to 10 576 taps (this instance has %u); nothing changed", S->ntaps);
     HIP_TRY(hipStreamSynchronize(S->ctx->stream));
     if (!S->per_channel) {          // every channel starts from the shared coefficients (d_taps: int32, front-padded to ntaps_pad)

@@ -8,11 +8,14 @@
 //   msdr_chain_q15pc.hip   the Q15 chain / the arm_fir_fast_q15 stage with per-channel FIR coefficients: chain_q15pc_kernel
 //   msdr_chain_f32pc.hip   the fp32 chain / the arm_fir_f32 stage with per-channel FIR coefficients: chain_f32pc_kernel
 //   msdr_biquad_df1_pc.hip arm_biquad_cascade_df1_f32 in CMSIS order with per-channel coefficients: biquad_df1_seq_pc_kernel
+//   msdr_chain_oscpc.hip   the two chains above with per-channel oscillator tables: chain_q15pco_kernel, chain_f32pco_kernel
 //   msdr_chain_f32pcb.hip  the fp32 chain with per-channel settings at block cadence, one launch per call: chain_f32pcb_kernel
-// Host-side geometry helpers (LDS sizes, table formats) live with the kernels' headers.  Every launcher returns the HIP error of its launch.
+// Host-side geometry helpers (LDS sizes, table formats) live with the kernels' headers; the launch geometry of the per-receiver chain kernels
+// (PcLaunch, pc_geometry, kPcLdsCap) is msdr_pc_geometry.h, plain C++.  Every launcher returns the HIP error of its launch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "msdr_shared.h"
+#include "msdr_pc_geometry.h"
 
 namespace msdr {
 // chain_mfb_kernel<S, AM> (msdr_chain_mfb.hiph): stages = 0, 1, 2; am = the workgroups' tables are envelope tables.  Returns the HIP error of the launch.
@@ -44,8 +47,8 @@ hipError_t launch_biquad_teensy_pc(hipStream_t stream, int nodes, short *data, i
 // ---- msdr_chain_q15pc.hip ----
 // chain_q15pc_kernel<CPW, FIR_ONLY> (msdr_chain_q15pc.hiph).  The launcher chooses the channels per wave (4 up to 128 samples per call, 2 up to
 // 256, else 1), the waves per workgroup (4, fewer for very long filters: 64 KB of LDS) and the time segmentation from p.n, p.np, p.channels and
-// the number of compute units, fills p.nseg / p.seg_len / p.nw itself and reports the geometry.
-struct PcLaunch { unsigned grid, block; size_t lds_bytes; int cpw, nseg, tile; };
+// the number of compute units (pc_geometry; the Q15 launchers never split by msdr_chain_config.time_segments), fills p.nseg / p.seg_len / p.nw
+// itself and reports the geometry (PcLaunch).
 hipError_t launch_chain_q15pc(hipStream_t stream, bool fir_only, int num_cus, PcParams p, PcLaunch *geo);
 // ---- msdr_chain_f32pc.hip ----
 // chain_f32pc_kernel<CPW, FIR_ONLY, FS4> (msdr_chain_f32pc.hiph).  The same choices as above (np a multiple of 4; 64 KB of LDS); FS4 is the
@@ -68,7 +71,7 @@ hipError_t launch_biquad_df1_seq_pc(hipStream_t stream, int stages, const float 
 // ---- msdr_chain_f32pcb.hip ----
 // chain_f32pcb_kernel<CPW, FS4> (msdr_chain_f32pcb.hiph): mixer, FIR, demod, CMSIS-order cascade, fp32 / int16 store and the next history of one
 // block-cadence call (p.n = 32 .. 512, a multiple of 8) in one launch.  fs4: the Fs/4 mixer's flavour (p.osc unused).  The geometry follows
-// from (p.n, p.np, p.osc_len) alone (f32pcb_geometry); the launcher fills p.nw.  chain_f32pcb_lds: that geometry without a launch -- false where
+// from (p.n, p.np, p.osc_len) alone (f32pcb_geometry: the LDS-fitting step of pc_geometry, one tile, no segments); the launcher fills p.nw.  chain_f32pcb_lds: that geometry without a launch -- false where
 // one wave with one channel does not fit 64 KB of LDS (osc_len = 0: Fs/4).
 bool chain_f32pcb_lds(int n, int np, int osc_len, PcLaunch *geo);
 hipError_t launch_chain_f32pcb(hipStream_t stream, bool fs4, PcbParams p, PcLaunch *geo);

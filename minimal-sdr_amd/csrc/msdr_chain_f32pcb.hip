@@ -12,13 +12,6 @@ bool chain_f32pcb_lds(int n, int np, int osc_len, PcLaunch *geo)
     return true;
 }
 
-template <int CPW>
-static void pfb_launch(hipStream_t stream, bool fs4, unsigned grid, unsigned block, size_t lds, const PcbParams &p)
-{
-    if (fs4) hipLaunchKernelGGL((chain_f32pcb_kernel<CPW, true>), dim3(grid), dim3(block), lds, stream, p);
-    else hipLaunchKernelGGL((chain_f32pcb_kernel<CPW, false>), dim3(grid), dim3(block), lds, stream, p);
-}
-
 hipError_t launch_chain_f32pcb(hipStream_t stream, bool fs4, PcbParams p, PcLaunch *geo)
 {
     if (p.channels <= 0 || p.n < 8 || (p.n & 7) || p.hist_len < 0 || p.stages < 0 || p.stages > kMaxStages || !p.x || !p.out || !p.hist_in || !p.hist_out ||
@@ -30,11 +23,10 @@ hipError_t launch_chain_f32pcb(hipStream_t stream, bool fs4, PcbParams p, PcLaun
     p.nw = (int)g.block / 64;
     const long long per_wg = (long long)g.cpw * p.nw;
     g.grid = (unsigned)(((long long)p.channels + per_wg - 1) / per_wg);
-    switch (g.cpw) {
-    case 4: pfb_launch<4>(stream, fs4, g.grid, g.block, g.lds_bytes, p); break;
-    case 2: pfb_launch<2>(stream, fs4, g.grid, g.block, g.lds_bytes, p); break;
-    default: pfb_launch<1>(stream, fs4, g.grid, g.block, g.lds_bytes, p); break;
-    }
+    pc_dispatch_cpw(g.cpw, [&](auto cpw) {
+        if (fs4) hipLaunchKernelGGL((chain_f32pcb_kernel<decltype(cpw)::value, true>), dim3(g.grid), dim3(g.block), g.lds_bytes, stream, p);
+        else hipLaunchKernelGGL((chain_f32pcb_kernel<decltype(cpw)::value, false>), dim3(g.grid), dim3(g.block), g.lds_bytes, stream, p);
+    });
     if (geo) *geo = g;
     return hipGetLastError();
 }

@@ -272,3 +272,27 @@ def test_out_i16_within_one_lsb(ctx, orc):
             assert np.abs(got[c].astype(np.float64) - wi).max() <= 1, (step, c)
             assert np.abs(got[c]).max() > 100
         chain.close()
+
+
+# ------------------------------------------------------------------------------------------------ 6. equal rows = the shared table, bit for bit
+@pytest.mark.parametrize("n", [128, 256, 1003])
+def test_rows_that_equal_the_shared_table_give_the_taps_chain_bit_for_bit(ctx, n):
+    """chain_f32pco_kernel and chain_f32pc_kernel run the same staging, FIR, demodulator and store functions and differ in the mixer policy
+    alone (the row in LDS / the table in global memory): with every row equal to the shared table the audio is the same bits.  Two calls, so
+    that the second starts from a history and a non-zero table position."""
+    rng = np.random.default_rng(60 + n)
+    ch, nt, L = 7, 30, 24
+    modes, ti, tq = mixed_bank(ch, nt)
+    oi, oq = rows(1, L, seed=4)
+    x = signal(rng, ch, 2 * n)
+    got = {}
+    for kind in ("taps", "rows"):
+        chain = msdr.Chain(ctx, msdr.ARITH_F32, ch, ti[0], tq[0], mixer=msdr.MIXER_NCO, modes=modes, osc_i=oi[0], osc_q=oq[0])
+        chain.set_taps_channels_f32(0, ti, tq)
+        if kind == "rows":
+            chain.set_osc_channels(0, np.tile(oi, (ch, 1)), np.tile(oq, (ch, 1)))
+        got[kind] = run(ctx, chain, x, n)
+        assert chain.info()["kernel"].startswith(PCO if kind == "rows" else "chain_f32pc_kernel"), chain.info()
+        chain.close()
+    assert np.abs(got["taps"]).max() > 1e-3
+    assert np.array_equal(got["taps"].view(np.uint32), got["rows"].view(np.uint32)), np.flatnonzero((got["taps"] != got["rows"]).any(axis=0))[:16]
