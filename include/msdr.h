@@ -548,6 +548,28 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   the first per-channel cascade call -- invalidates it).  msdr_chain_graph_launch is refused (MSDR_STATUS_ARGUMENT_ERROR, nothing
  *   enqueued) after msdr_chain_set_osc / set_osc_channels, msdr_chain_set_mode / set_taps / set_anr / set_biquad_coeffs, msdr_chain_reset,
  *   msdr_chain_set_block_kernel(chain, 0), an odd number of direct calls, and any other live update that rebuilds tables.
+ * msdr_chain_set_block_kernel_q15 (Q15; default off): the same switch for a Q15 chain.  With `on` != 0 a block-cadence call (32 .. 512
+ *   samples, a divisor of 1024) of a chain in per-channel mode (msdr_chain_set_taps_channels / set_osc_channels / set_input_rows) runs
+ *   chain_q15pcb_kernel: mixer, FIR pair, demodulator, the 0 .. 2 AudioFilterBiquad nodes (every channel from its own records, so uniform
+ *   and per-channel node coefficients alike, 1 .. 4 stages) and the next FIR history in ONE launch instead of three.  All arithmetic is
+ *   integer and is the unfused kernels' own: audio, history and node records are theirs bit for bit.  The call is a switch of the host's:
+ *   stream-ordered, every state kept, before or after the chain enters per-channel mode; off, or never called, nothing changes anywhere.
+ *   A call runs the unfused launches exactly as before while any of this holds: another block length; an oscillator generation pending
+ *   (one history length after msdr_chain_set_osc / set_osc_channels); a SYNCAM channel on a chain created with MSDR_CHAIN_SYNCAM_PLL; an
+ *   LMS channel on (msdr_chain_set_anr); one wave's windows, tap rows, oscillator row and output row past 64 KB of LDS.  Both paths work on
+ *   the same history, table position and node records, so a chain moves between them from call to call.  msdr_chain_get_info(): kernel
+ *   begins "chain_q15pcb_kernel"; grid, block, lds_bytes, tile and taps_padded are the launch's; flavour stays 0 as on every Q15 chain.
+ *   An F32 chain and a NULL chain are MSDR_STATUS_ARGUMENT_ERROR (and msdr_chain_set_block_kernel keeps refusing Q15 chains).
+ *   Graphs: msdr_chain_graph_create accepts a Q15 chain in per-channel mode as before; with the switch on a captured tick is one launch.
+ *   The graph stays valid across msdr_chain_set_taps_channels, and across msdr_chain_set_node_coefficients[_channels] on a chain whose
+ *   nodes were per-channel already when it was made -- a change of a channel's stage count included: those calls rewrite rows and records
+ *   in place, and the kernel reads the stage flags from the records at every launch.  msdr_chain_graph_launch is refused
+ *   (MSDR_STATUS_ARGUMENT_ERROR, nothing enqueued) after msdr_chain_set_block_kernel_q15 changed the switch, after msdr_chain_set_anr, and
+ *   after everything that refuses a Q15 per-channel graph already: msdr_chain_set_osc / set_osc_channels, set_mode, set_taps,
+ *   msdr_chain_reset, an odd number of direct calls, msdr_chain_set_input_rows.  The stage instance msdr_fir_q15 is out of scope.
+ *   Measured on one MI355X at 4096 channels x 128 samples with two one-stage per-channel nodes the fused tick is SLOWER than the three
+ *   launches (48.5 against 38.0 us: the node phase runs on one lane per channel; README.md, profiles/block_pc_q15/): measure before turning
+ *   it on.
  * msdr_chain_set_biquad_coeffs (F32): all 5 * num_biquad_stages coefficients of the arm_biquad_cascade_df1_f32 stage, CMSIS
  *   semantics (the filter carries on from the pState arm_biquad_cascade_df1_f32 would hold; see msdr_biquad_df1_f32_set_coeffs).
  *   The number of stages is fixed at creation, as numStages is in CMSIS.
@@ -643,6 +665,7 @@ int msdr_chain_set_osc(msdr_chain *chain, const void *osc_i, const void *osc_q);
 int msdr_chain_set_osc_channels(msdr_chain *chain, uint32_t first_channel, uint32_t count,
                                 const void *osc_i, const void *osc_q);
 int msdr_chain_set_block_kernel(msdr_chain *chain, int on);   /* F32 chains; default off */
+int msdr_chain_set_block_kernel_q15(msdr_chain *chain, int on);   /* Q15 chains; default off */
 int msdr_chain_set_input_rows(msdr_chain *chain, uint32_t n_inputs, const uint32_t *input_row);
 /* ANR_on per channel (host array of `channels` values, or NULL: anr_on_all for every channel); the LMS filter then runs between
  * the demodulator and the biquad nodes / cascade (Minimal-SDR.ino:702-770).  Its state is created on first use and cleared by

@@ -2468,6 +2468,10 @@ struct msdr_chain {
     // every other call runs the unfused launches over the same history, table position and cascade state.  Off by default.
     bool block_pc = false;
     uint64_t block_epoch = 0;             // bumped by every change of block_pc: part of a HIP graph's key
+    // msdr_chain_set_block_kernel_q15 (Q15): the same for chain_q15pcb_kernel (msdr_chain_q15pcb.hiph) -- demodulator, the AudioFilterBiquad nodes
+    // and the next history in ONE launch; every other call runs the unfused launches over the same history, table position and node records
+    bool block_q15 = false;
+    uint64_t block_q15_epoch = 0;         // bumped by every change of block_q15: part of a HIP graph's key
     // msdr_chain_set_input_rows: receiver ch hears row h_in_row[ch] of a d_if that is [n_inputs][n_samples]; n_inputs == 0: the identity, d_if
     // [channels][n_samples].  The per-channel kernels and history_rows_kernel read the device table, which later calls rewrite in place.
     // The FIR history stays per channel, so nothing else of the chain knows about the map.
@@ -2506,6 +2510,9 @@ static const char kPcfKernelName[] = "chain_f32pc_kernel (per-channel taps)";
 static const char kPcfoKernelName[] = "chain_f32pco_kernel (per-channel taps and oscillator tables)";
 static const char kPcbKernelName[] = "chain_f32pcb_kernel (per-channel taps, one launch per block)";
 static const char kPcboKernelName[] = "chain_f32pcb_kernel (per-channel taps and oscillator tables, one launch per block)";
+// ... and of a Q15 chain on its block kernel (msdr_chain_set_block_kernel_q15)
+static const char kQpcbKernelName[] = "chain_q15pcb_kernel (per-channel taps, one launch per block)";
+static const char kQpcboKernelName[] = "chain_q15pcb_kernel (per-channel taps and oscillator tables, one launch per block)";
 static void chain_pcf_row_from(msdr_chain *c, uint32_t ch, const float *ci, const float *cq)
 {
     float *row = c->h_pcf_taps.data() + (size_t)ch * 2 * c->pc_np;
@@ -3695,6 +3702,11 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     if (use_pcf && c->block_pc && mb_n_ok((long long)n_samples) && !p.osc_hist && !(c->f32_pll || c->aux != nullptr || chain_summary(c).any_anr) &&
         (!c->seq_bq || c->seq_bq->stages == 0 || c->seq_bq->sequential))
         use_pcb = chain_f32pcb_lds((int)n_samples, c->pc_np, c->mixer == kMixerFs4 ? 0 : (int)c->osc_len, &pcb_geo);
+    // ---- msdr_chain_set_block_kernel_q15: the same for a Q15 chain in per-channel mode (msdr_chain_q15pcb.hiph) -- where no oscillator generation
+    // is pending, neither the PLL demodulator nor the LMS filter runs between the demodulator and the nodes, and one wave's LDS fits
+    bool use_qpcb = false;
+    if (use_pc && c->block_q15 && mb_n_ok((long long)n_samples) && !p.osc_hist && !pll_active && !(c->anr && (c->d_anr_on || c->anr_all > 0)))
+        use_qpcb = chain_q15pcb_lds((int)n_samples, c->pc_np, c->mixer == kMixerFs4 ? 0 : (int)c->osc_len, nullptr);
     if (use_pcb) { /* (the kernel converts in its store phase: no scratch batch) */ }
     else
     if (f32 && (c->flags & MSDR_CHAIN_OUT_I16)) {
@@ -4074,6 +4086,20 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         }
         kname = c->qm_fr ? "chain_q15mf_kernel full-rate NCO streams" : "chain_q15mf_kernel"; block = (unsigned)nw * 64; nseg = qseg;
     }
+    else if (use_qpcb) {
+        QpcbParams q;
+        memset(&q, 0, sizeof q);
+        q.x = d_if; q.out = (short *)d_audio; q.hist_in = c->d_hist[c->cur]; q.hist_out = c->d_hist[c->cur ^ 1]; q.n = (int)n_samples; q.channels = (int)c->channels;
+        q.hist_len = (int)c->hist_len; q.np = c->pc_np; q.taps = c->d_pc_taps; q.chan_mode = c->d_mode;
+        q.osc = c->opc_active ? c->d_osc_bank : (const void *)c->d_osc; q.osc_len = (int)c->osc_len; q.osc_stride = c->opc_active ? (int)c->osc_len : 0;
+        q.phase0 = (int)c->phase; q.sqrt_kind = c->sqrt_kind; q.in_row = c->n_inputs ? c->d_in_row : nullptr;
+        q.nnodes = (int)c->nnodes; q.defs0 = c->nnodes > 0 ? c->nodes[0]->d_defs : nullptr; q.defs1 = c->nnodes > 1 ? c->nodes[1]->d_defs : nullptr;
+        PcLaunch geo;
+        if (launch_chain_q15pcb(c->ctx->stream, c->mixer == kMixerFs4, q, &geo) != hipSuccess)
+            return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pcb_kernel launch failed");
+        kname = c->opc_active ? kQpcboKernelName : kQpcbKernelName;
+        grid = geo.grid; block = geo.block; lds_used = geo.lds_bytes; nseg = 1; pc_tile = geo.tile;
+    }
     else if (use_pc) {
         PcParams q;
         memset(&q, 0, sizeof q);
@@ -4107,7 +4133,8 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     if (c->anr && (c->d_anr_on || c->anr_all > 0))      // LMS notch / noise reduction (.ino:702-770), then the biquad nodes
         if (int rc = msdr_anr_q15(c->anr, c->d_anr_on, c->anr_all, (q15_t *)d_audio, (uint32_t)n_samples)) return rc;
 
-    if (c->nnodes == 2 && !nodes_fused) {      // biquad1_dac -> biquad2_dac in one pass over the audio
+    if (use_qpcb) { /* (chain_q15pcb_kernel ran the nodes as its third phase, on the same records) */ }
+    else if (c->nnodes == 2 && !nodes_fused) {      // biquad1_dac -> biquad2_dac in one pass over the audio
         const bool slabs = (c->channels & 63u) == 0 && (n_samples & 127u) == 0 && (reinterpret_cast<uintptr_t>(d_audio) & 15) == 0;
         const int per_group = c->nodes[0]->pipe_ch ? c->nodes[0]->pipe_ch : 64;
         // one 128-sample block, the reference's cadence, one stage per node: the pipeline over sub-slabs inside the block (biquad_teensy_blk_kernel),
@@ -4157,13 +4184,13 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         if (int rc = launch_check("f32_to_q15_kernel")) return rc;
     }
 
-    if (!use_mfb && !use_qb && !use_pcb && c->n_inputs) {          // msdr_chain_set_input_rows: each channel's history from the row it heard
+    if (!use_mfb && !use_qb && !use_pcb && !use_qpcb && c->n_inputs) {          // msdr_chain_set_input_rows: each channel's history from the row it heard
         hipLaunchKernelGGL((history_rows_kernel<int16_t>), dim3(grid_1d((long long)c->channels * c->hist_len)), dim3(256), 0, c->ctx->stream,
                            d_if, (const int16_t *)c->d_hist[c->cur], c->d_hist[c->cur ^ 1], (long long)n_samples, (int)c->hist_len,
                            (int)c->channels, (const int *)c->d_in_row);
         if (int rc = launch_check("history_rows_kernel")) return rc;
     } else
-    if (!use_mfb && !use_qb && !use_pcb) {            // (the block kernels write the next history themselves)
+    if (!use_mfb && !use_qb && !use_pcb && !use_qpcb) {            // (the block kernels write the next history themselves)
         hipLaunchKernelGGL((history_kernel<int16_t>), dim3(grid_1d((long long)c->channels * c->hist_len)), dim3(256), 0, c->ctx->stream,
                            d_if, (const int16_t *)c->d_hist[c->cur], c->d_hist[c->cur ^ 1], (long long)n_samples, (int)c->hist_len,
                            (int)c->channels);
@@ -4216,6 +4243,8 @@ struct msdr_chain_graph {
     // that moved or changed its size is not -- and they are the launches of the configuration these epochs stand for
     bool k_block_pc;
     uint64_t k_block_epoch, k_anr_gen;
+    bool k_block_q15;      // chain_q15pcb_kernel (msdr_chain_set_block_kernel_q15): the captured ticks are one launch each, the switch as it was
+    uint64_t k_block_q15_epoch;
     uint64_t k_in_row_epoch;   // msdr_chain_set_input_rows calls so far: each changes what the captured d_if pointers are taken to be
     const void *k_pcf_taps, *k_osc_bank, *k_bq_tab, *k_bq_state;
     size_t k_pcf_cap, k_osc_cap, k_bq_cap;
@@ -4227,6 +4256,7 @@ static void chain_graph_key(const msdr_chain *c, msdr_chain_graph *g)
     g->k_rebuild_gen = c->rebuild_gen; g->k_mode = c->d_mode; g->k_osc = c->d_osc; g->k_osc_pc = c->opc_active; g->k_osc_gen = c->osc_gen;
     g->k_block_pc = c->arith == MSDR_ARITH_F32 && c->pc_active && c->block_pc; g->k_block_epoch = c->block_epoch; g->k_anr_gen = c->anr_gen;
     g->k_in_row_epoch = c->in_row_epoch;
+    g->k_block_q15 = c->arith == MSDR_ARITH_Q15 && c->pc_active && c->block_q15; g->k_block_q15_epoch = c->block_q15_epoch;
     g->k_pcf_taps = c->d_pcf_taps; g->k_pcf_cap = c->pc_active ? (size_t)c->channels * 2 * (size_t)c->pc_np : 0;
     g->k_osc_bank = c->d_osc_bank; g->k_osc_cap = c->opc_active ? (size_t)c->channels * c->osc_len : 0;
     const msdr_biquad_df1_f32 *S = c->seq_bq;
@@ -4304,6 +4334,12 @@ extern "C" int msdr_chain_graph_launch(msdr_chain_graph *g)
         if (now.k_pcf_taps != g->k_pcf_taps || now.k_pcf_cap != g->k_pcf_cap || now.k_osc_bank != g->k_osc_bank || now.k_osc_cap != g->k_osc_cap ||
             now.k_bq_tab != g->k_bq_tab || now.k_bq_cap != g->k_bq_cap || now.k_bq_state != g->k_bq_state)
             return fail(MSDR_STATUS_ARGUMENT_ERROR, "a per-channel table or the cascade's state moved since this graph was made (a first per-channel call, a segmented direct call of the cascade): make the graph again");
+    }
+    if (g->k_block_q15 || now.k_block_q15) {          // the graph holds chain_q15pcb_kernel launches (or the chain would make them now)
+        if (now.k_block_q15 != g->k_block_q15 || now.k_block_q15_epoch != g->k_block_q15_epoch)
+            return fail(MSDR_STATUS_ARGUMENT_ERROR, "msdr_chain_set_block_kernel_q15 changed the chain's block-cadence kernel since this graph was made: make the graph again");
+        if (now.k_anr_gen != g->k_anr_gen)
+            return fail(MSDR_STATUS_ARGUMENT_ERROR, "msdr_chain_set_anr ran since this graph was made (the LMS filter runs between the demodulator and the nodes, which the captured launches know nothing of): make the graph again");
     }
     HIP_TRY(hipGraphLaunch(g->exec, c->ctx->stream));
     c->gen += g->ticks;                                     // (an even number of calls: buffers, table position and caches stay as they are)
@@ -4546,6 +4582,7 @@ static int chain_rebuild(msdr_chain *c, const ChainCfgStore &edited, void **stea
     // ... and so does the bank of per-channel oscillator tables (its pending generations went over with osc_pending above)
     n->opc_active = c->opc_active; std::swap(n->d_osc_bank, c->d_osc_bank); n->osc_gen = c->osc_gen;
     n->block_pc = c->block_pc; n->block_epoch = c->block_epoch;          // (msdr_chain_set_block_kernel holds for the chain's life)
+    n->block_q15 = c->block_q15; n->block_q15_epoch = c->block_q15_epoch;          // (and so does msdr_chain_set_block_kernel_q15)
     n->n_inputs = c->n_inputs; std::swap(n->d_in_row, c->d_in_row); n->in_row_epoch = c->in_row_epoch;       // (the input map too)
     std::swap(*c, *n);
     if (steal_osc) { *steal_osc = n->d_osc; n->d_osc = nullptr; }
@@ -4737,6 +4774,17 @@ extern "C" int msdr_chain_set_block_kernel(msdr_chain *c, int on)
     if (c->arith != MSDR_ARITH_F32) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the block kernel belongs to F32 chains (a Q15 chain with per-channel taps replays as a graph as it is)");
     const bool v = on != 0;
     if (v != c->block_pc) { c->block_pc = v; c->block_epoch++; }
+    return 0;
+}
+
+// The same for a Q15 chain in per-channel mode (chain_q15pcb_kernel); legal before the chain enters that mode, where it waits for it
+extern "C" int msdr_chain_set_block_kernel_q15(msdr_chain *c, int on)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (int rc = bind(c->ctx)) return rc;
+    if (c->arith != MSDR_ARITH_Q15) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the Q15 block kernel belongs to Q15 chains (F32: msdr_chain_set_block_kernel)");
+    const bool v = on != 0;
+    if (v != c->block_q15) { c->block_q15 = v; c->block_q15_epoch++; }
     return 0;
 }
 
@@ -5051,6 +5099,7 @@ extern "C" int msdr_chain_set_anr(msdr_chain *c, const int32_t *anr_on, int32_t 
     HIP_TRY(hipStreamSynchronize(c->ctx->stream));
     hipFree(c->d_anr_on); c->d_anr_on = nullptr;
     c->anr_all = anr_on_all;
+    c->anr_gen++;                                                // (part of the key of a graph of chain_q15pcb_kernel launches)
     if (anr_on) {
         std::vector<int> h(anr_on, anr_on + c->channels);
         if (int rc = upload(c->ctx, h, &c->d_anr_on)) return rc;

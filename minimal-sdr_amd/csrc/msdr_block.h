@@ -10,6 +10,7 @@
 //   msdr_biquad_df1_pc.hip arm_biquad_cascade_df1_f32 in CMSIS order with per-channel coefficients: biquad_df1_seq_pc_kernel
 //   msdr_chain_oscpc.hip   the two chains above with per-channel oscillator tables: chain_q15pco_kernel, chain_f32pco_kernel
 //   msdr_chain_f32pcb.hip  the fp32 chain with per-channel settings at block cadence, one launch per call: chain_f32pcb_kernel
+//   msdr_chain_q15pcb.hip  the Q15 chain with per-channel settings at block cadence, one launch per call: chain_q15pcb_kernel
 // Host-side geometry helpers (LDS sizes, table formats) live with the kernels' headers; the launch geometry of the per-receiver chain kernels
 // (PcLaunch, pc_geometry, kPcLdsCap) is msdr_pc_geometry.h, plain C++.  Every launcher returns the HIP error of its launch.
 #pragma once
@@ -75,4 +76,12 @@ hipError_t launch_biquad_df1_seq_pc(hipStream_t stream, int stages, const float 
 // one wave with one channel does not fit 64 KB of LDS (osc_len = 0: Fs/4).
 bool chain_f32pcb_lds(int n, int np, int osc_len, PcLaunch *geo);
 hipError_t launch_chain_f32pcb(hipStream_t stream, bool fs4, PcbParams p, PcLaunch *geo);
+// ---- msdr_chain_q15pcb.hip ----
+// chain_q15pcb_kernel<CPW, FS4> (msdr_chain_q15pcb.hiph): mixer, FIR pair, demod, 0 .. 2 AudioFilterBiquad nodes (every channel from its own records),
+// int16 store and the next history of one block-cadence call (p.n = 32 .. 512, a multiple of 8) in one launch.  fs4: the Fs/4 mixer's flavour
+// (p.osc unused).  The geometry follows from (p.n, p.np, p.osc_len) alone (qpcb_geometry: the LDS-fitting step of pc_geometry, one tile, no
+// segments); the launcher fills p.nw.  chain_q15pcb_lds: that geometry without a launch -- false where one wave with one channel does not fit
+// 64 KB of LDS (osc_len = 0: Fs/4).
+bool chain_q15pcb_lds(int n, int np, int osc_len, PcLaunch *geo);
+hipError_t launch_chain_q15pcb(hipStream_t stream, bool fs4, QpcbParams p, PcLaunch *geo);
 }  // namespace msdr

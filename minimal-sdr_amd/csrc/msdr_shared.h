@@ -188,4 +188,29 @@ struct PcbParams {
                                // hist_in / hist_out stay rows of the CHANNEL: what that receiver heard
 };
 
+// chain_q15pcb_kernel (msdr_chain_q15pcb.hiph): a whole block-cadence call of the Q15 chain with per-channel settings in one launch
+struct QpcbParams {
+    const int16_t *x;          // [channels][n] IF samples
+    short *out;                // [channels][n] audio behind the nodes
+    const int16_t *hist_in;    // [channels][hist_len] raw history, oldest first
+    int16_t *hist_out;         // [channels][hist_len] the history this call leaves (another buffer than hist_in)
+    int n;                     // 32 .. 512 samples, a multiple of 8
+    int channels;
+    int hist_len;
+    int np;                    // taps per row of the table: numTaps front-padded with zeros to a multiple of 8
+    const int16_t *taps;       // [channels][2][np] (I row, Q row; CMSIS order)
+    const int *chan_mode;      // [channels]
+    const void *osc;           // int2 pairs {osc_q ("cos"), osc_i ("sin")}: channel ch reads osc_len pairs from pair ch * osc_stride on (unused: Fs/4)
+    int osc_len;
+    int osc_stride;            // 0: one table shared by all channels; osc_len: a bank [channels][osc_len]
+    int phase0;                // (absolute index of sample 0 of this call) mod osc_len (mod 4 for Fs/4)
+    int sqrt_kind;
+    int nnodes;                // 0, 1 or 2 AudioFilterBiquad nodes behind the demodulator
+    int *defs0, *defs1;        // their records [channels][32]: coefficient words 0..4, state words 5..7 (read and written in place), word 7 bit 31 =
+                               // another stage follows; every channel is read from its own record
+    int nw;                    // waves per workgroup
+    const int *in_row;         // [channels]: channel ch hears row in_row[ch] of x (msdr_chain_set_input_rows), x being [n_inputs][n]; null: row ch.
+                               // hist_in / hist_out stay rows of the CHANNEL: what that receiver heard
+};
+
 }  // namespace msdr

@@ -325,6 +325,8 @@ public:
     }
     // fp32 chain in per-channel mode: the whole tick in one launch (msdr_chain_set_block_kernel: chain_f32pcb_kernel)
     int setBlockKernel(bool on) { return chain ? msdr_chain_set_block_kernel(chain, on ? 1 : 0) : MSDR_STATUS_ARGUMENT_ERROR; }
+    // Q15 chain in per-channel mode: demodulator, both biquad nodes and the next history in one launch (msdr_chain_set_block_kernel_q15: chain_q15pcb_kernel)
+    int setBlockKernelQ15(bool on) { return chain ? msdr_chain_set_block_kernel_q15(chain, on ? 1 : 0) : MSDR_STATUS_ARGUMENT_ERROR; }
     // which kernel the last tick ran (msdr_chain_get_info)
     int info(msdr_chain_info *out) { return chain ? msdr_chain_get_info(chain, out) : MSDR_STATUS_ARGUMENT_ERROR; }
     // calc_demod_filter() of receiver `channel` (Minimal-SDR.ino:221-223): calc_FIR_coeffs(FIR_AM_coeffs, numTaps, filter_bandwidth, 70, 0, 0.0, 24000)

@@ -103,6 +103,7 @@ def load_library(path=None):
                        ("msdr_biquad_df1_f32_set_coeffs_channels", [_p, C.c_uint32, C.c_uint32, _p]),
                        ("msdr_chain_set_osc_channels", [_p, C.c_uint32, C.c_uint32, _p, _p]),
                        ("msdr_chain_set_block_kernel", [_p, C.c_int]),
+                       ("msdr_chain_set_block_kernel_q15", [_p, C.c_int]),
                        ("msdr_chain_set_input_rows", [_p, C.c_uint32, _p]),
                        ("msdr_chain_get_fir_history", [_p, C.c_uint32, _p, C.c_uint32, _p]),
                        ("msdr_chain_get_cmsis_state", [_p, C.c_uint32, _p])):
@@ -831,6 +832,12 @@ class Chain(_Instance):
         """F32: a block-cadence call of a chain in per-channel mode as ONE launch (chain_f32pcb_kernel: demodulator, CMSIS-order cascade, int16
         conversion and the next history), bit-identical to the unfused launches, and capturable by graph().  Off by default; every state kept."""
         _ck(self.ctx.lib.msdr_chain_set_block_kernel(self.h, C.c_int(1 if on else 0)))
+
+    def set_block_kernel_q15(self, on):
+        """Q15: a block-cadence call of a chain in per-channel mode as ONE launch (chain_q15pcb_kernel: demodulator, the AudioFilterBiquad nodes from
+        every channel's own records and the next history), bit-identical to the three unfused launches; a graph() tick is then one launch.  Off by
+        default; every state kept."""
+        _ck(self.ctx.lib.msdr_chain_set_block_kernel_q15(self.h, C.c_int(1 if on else 0)))
 
     def set_input_rows(self, rows, n_inputs=None):
         """One antenna stream (or a few) feeds the bank: channel c hears row rows[c] of a d_if that is [n_inputs, n] from the next process() /
