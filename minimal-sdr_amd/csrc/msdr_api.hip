@@ -24,6 +24,7 @@
 #include "msdr_block.h"
 #include "msdr_design.h"
 #include "msdr_cascade_state.h"
+#include "msdr_kstack.h"
 
 #include <algorithm>
 #include <atomic>
@@ -2955,17 +2956,11 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
             }
             for (int m = 0; m < 32; m++) for (int k = 0; k < NS; k++) iirc[kMwIirGfix + m * 4 + k] = (m - k >= 0) ? (float)gap[m - k] : 0.0f;
             if (Rmax * std::ldexp(1.0, kMwIirSigExp) > 60000.0) iirfold = false;
-            // response fragments for the correction MFMA: A operand, lane (m, kg), element j: kg = 1 and j < NS: R[m][j] 2^e, else 0
-            _Float16 *rh = reinterpret_cast<_Float16 *>(iirc.data() + kMwIirRfrag), *rl = rh + 512;
-            for (int l = 0; l < 64; l++)
-                for (int j = 0; j < 8; j++) {
-                    const double val = ((l >> 5) == 1 && j < NS) ? Rr[l & 31][j] * std::ldexp(1.0, kMwIirSigExp) : 0.0;
-                    const _Float16 vh = (_Float16)val;
-                    rh[l * 8 + j] = vh; rl[l * 8 + j] = (_Float16)(val - (double)vh);
-#if defined(MSDR_MUTATE) && MSDR_MUTATE == 5       /* `make mutants`, never the product: the lo halves of the cascade's response fragments dropped (rl, and lf / df below) */
-                    rl[l * 8 + j] = (_Float16)0.0f;
-#endif
-                }
+            // response fragments for the correction MFMA (A operands, msdr_kstack.h): the stacked [R_hi | R_hi ; R_lo] 2^e, then R_lo 2^e alone
+            {
+                _Float16 *rf = reinterpret_cast<_Float16 *>(iirc.data() + kMwIirRfrag);
+                kstack_fill(Rr, std::ldexp(1.0, kMwIirSigExp), rf, rf + kKstackHalves);
+            }
             iirc[kMwIirCoef + 0] = (S_ == 2) ? (float)sec_a1[1] : 0.0f;       // the last section's feedback: w_(S-1)[n] = y[n] - a1 y[n-1] - a2 y[n-2]
             iirc[kMwIirCoef + 1] = (S_ == 2) ? (float)sec_a2[1] : 0.0f;
             // ---- envelope modes: the cascade cannot go into the FIR (the envelope is in between), so its zero-state response runs as
@@ -3013,19 +3008,11 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
                         const double val = (m >= kk) ? hfull[m - kk] * std::ldexp(1.0, kMwIirEnvExp) : 0.0;
                         const _Float16 vh = (_Float16)val;
                         lf[st2 * 1024 + l * 8 + j] = vh; lf[st2 * 1024 + 512 + l * 8 + j] = (_Float16)(val - (double)vh);
-#if defined(MSDR_MUTATE) && MSDR_MUTATE == 5
+#if defined(MSDR_MUTATE) && MSDR_MUTATE == 5       /* `make mutants`, never the product: the lo halves of the cascade's response fragments dropped (here, and kstack_fill's) */
                         lf[st2 * 1024 + 512 + l * 8 + j] = (_Float16)0.0f;
 #endif
                     }
-            for (int l = 0; l < 64; l++)
-                for (int j = 0; j < 8; j++) {
-                    const double val = ((l >> 5) == 1 && j < 4) ? Rd[l & 31][j] * std::ldexp(1.0, kMwIirEnvExp) : 0.0;
-                    const _Float16 vh = (_Float16)val;
-                    df[l * 8 + j] = vh; df[512 + l * 8 + j] = (_Float16)(val - (double)vh);
-#if defined(MSDR_MUTATE) && MSDR_MUTATE == 5
-                    df[512 + l * 8 + j] = (_Float16)0.0f;
-#endif
-                }
+            kstack_fill(Rd, std::ldexp(1.0, kMwIirEnvExp), df, df + kKstackHalves);       // (MSDR_MUTATE == 5 drops its lo pieces too)
         }
         // A retune (msdr_chain_set_mode) hands the cascade's state and numerator history of the OLD mode / tap set to the kernel of
         // the NEW one, which takes them in through fp16 at its own table's scale: the scale of every table must therefore hold
