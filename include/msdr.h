@@ -716,6 +716,37 @@ enum { MSDR_FLAVOUR_OSC_PC = 0x20000u };
  * [n_inputs][n_samples] (always beside MSDR_FLAVOUR_TAPS_PC). */
 enum { MSDR_FLAVOUR_SHARED_IF = 0x40000u };
 int msdr_chain_get_info(msdr_chain *chain, msdr_chain_info *info);
+/* Which kernel ran the serial recurrences (introspection for tests: tests/q15_ladder_cases.py is the table of every branch below, and
+ * tests/test_gpu_q15_ladders.py holds each of them to the oracle bit for bit).  Each getter returns a static string -- the kernel's name
+ * with its template arguments, set in the branch that made the launch and handed to the launch's error check as well -- "" before the
+ * first call, NULL for a NULL instance.  All of these kernels are bit-exact, so the name is the only way to tell them apart.  The ladders,
+ * first match wins; "aligned" = the data pointer is a multiple of 16 bytes; "one stage" = set_coefficients never named a stage above 0:
+ *   msdr_biquad_q15_last_kernel (the last msdr_biquad_q15_update):
+ *     per-channel records (set_coefficients_channels was called) ........................... "biquad_teensy_pc_kernel<1>"
+ *     one stage, blockSize % 128 == 0, aligned, channels % P == 0 ........................... "biquad_teensy_pipe4_kernel<1,P>"
+ *       P = channels per workgroup, fixed at create time: MSDR_BIQUAD_PIPE_CH = 16 / 32 / 64 if set, else 64 from 16 384 channels,
+ *       32 from 8192, 16 below
+ *     otherwise .......................................................................... "biquad_teensy_kernel<1>"
+ *   msdr_chain_node_kernel (the biquad nodes of the last msdr_chain_process; "" for no nodes and for fp32 chains):
+ *     msdr_chain_set_block_kernel_q15 on and the block kernel took the call, any nodes ....... "chain_q15pcb_kernel"
+ *     one node ........................................................................... what msdr_biquad_q15_update reports
+ *     two nodes, uniform records, one stage each, n == 128 on the block path (info().kernel = chain_q15mb_kernel), no PLL / LMS
+ *       channel, MSDR_Q15_NO_FUSE unset at create time, one tile per wave on three or more waves (the host's choice wherever the
+ *       tiles leave it free: every small batch) ........................................... "chain_q15mb_kernel"
+ *     two nodes, per-channel records in either ........................................... "biquad_teensy_pc_kernel<2>"
+ *     one stage each, n == 128, aligned, and MSDR_BIQUAD_BLK (create time) = 1, or unset and ceil(channels / 16) <= the device's
+ *       CU count; MSDR_BIQUAD_BLK=0: never ................................................. "biquad_teensy_blk_kernel"
+ *     one stage each, n % 128 == 0, aligned, channels % P == 0 (P of node 0, as above) ...... "biquad_teensy_pipe4_kernel<2,P>"
+ *     n % 128 == 0, aligned, channels % 64 == 0 (so: a node with two or more stages) ........ "biquad_teensy_pipe_kernel"
+ *     otherwise .......................................................................... "biquad_teensy_kernel<2>"
+ *     Under msdr_chain_graph_create it is what the recording enqueued; replays do not change it.
+ *   msdr_frontend_last_kernel (the last msdr_frontend_update):
+ *     stages == MSDR_FE_ALL, d_adc and d_out aligned, channels % P == 0 ...................... "frontend_pipe4_kernel<P>"
+ *       P fixed at create time: MSDR_FRONTEND_PIPE_CH = 16 / 32 / 64 if set, else by the same channel counts as above
+ *     otherwise .......................................................................... "frontend_kernel" */
+const char *msdr_chain_node_kernel(msdr_chain *chain);
+const char *msdr_biquad_q15_last_kernel(msdr_biquad_q15 *S);
+const char *msdr_frontend_last_kernel(msdr_frontend *fe);
 /* Introspection for tests: what a chain carries from call to call.  get_fir_history: *hist_len = the raw int16 samples the chain keeps per
  * channel (a property of the kernels it runs), and, where hist != NULL (capacity >= that many), channel's samples, oldest first.
  * get_cmsis_state (F32 chains whose cascade runs behind the kernel: MSDR_FLAVOUR_SEQ_CASCADE): 4 * num_biquad_stages floats, as

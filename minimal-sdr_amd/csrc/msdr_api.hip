@@ -1681,9 +1681,10 @@ struct msdr_biquad_q15 {
     uint32_t channels;
     int *d_defs;      // [channels][32]
     int max_stage;    // highest stage index given to setCoefficients so far (-1: none): stages above 0 chain through the records' flag bits
-    int pipe_ch;      // channels per workgroup of biquad_teensy_pipe4_kernel (64 / 32 / 16), 0: never that kernel (read at create time)
+    int pipe_ch;      // channels per workgroup of biquad_teensy_pipe4_kernel: 64 / 32 / 16 (read at create time)
     bool per_channel; // set by the first msdr_biquad_q15_set_coefficients_channels, for the instance's life: the records may differ from channel to
                       // channel, so update() runs biquad_teensy_pc_kernel (every lane its own coefficients and stage count, msdr_biquad_pc.hiph)
+    const char *last_kernel = "";     // msdr_biquad_q15_last_kernel: the kernel the last update() launched, set in the branch that launches it
 };
 static int tq4_pipe_ch_at_create(uint32_t channels)
 {
@@ -1769,26 +1770,30 @@ extern "C" int msdr_biquad_q15_update(msdr_biquad_q15 *S, q15_t *d_data, uint32_
     if (!d_data) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null buffer");
     if (blockSize & 1u) return fail(MSDR_STATUS_LENGTH_ERROR, "AudioFilterBiquad processes sample pairs: blockSize must be even");
     if (S->per_channel) {                                       // records differ from channel to channel: nothing of them is wave-uniform
+        S->last_kernel = "biquad_teensy_pc_kernel<1>";
         if (launch_biquad_teensy_pc(S->ctx->stream, 1, (short *)d_data, S->d_defs, nullptr, (int)S->channels, (long long)blockSize) != hipSuccess)
             return fail(MSDR_STATUS_HIP_ERROR, "biquad_teensy_pc_kernel<1> launch failed");
-        return launch_check("biquad_teensy_pc_kernel<1>");
+        return launch_check(S->last_kernel);
     }
-    if (S->max_stage == 0 && (blockSize & 127u) == 0 && (reinterpret_cast<uintptr_t>(d_data) & 15) == 0 && S->pipe_ch) {
+    if (S->max_stage == 0 && (blockSize & 127u) == 0 && (reinterpret_cast<uintptr_t>(d_data) & 15) == 0) {
         // one stage, slab-shaped batch: the recursion alone on one wave, the input products element-wise on the others (msdr_kernels.hiph)
         const int per_group = S->pipe_ch;
 #define MSDR_TQ4_LAUNCH(CH_)                                                                                                                               \
         if (per_group == CH_ && S->channels % CH_ == 0) {                                                                                                  \
+            S->last_kernel = "biquad_teensy_pipe4_kernel<1," #CH_ ">";                                                                                     \
             hipLaunchKernelGGL((biquad_teensy_pipe4_kernel<1, CH_>), dim3(S->channels / CH_), dim3(tq4_threads(CH_)), tq4_lds_bytes(CH_), S->ctx->stream,  \
                                (short *)d_data, S->d_defs, (int *)nullptr, (int)S->channels, (long long)blockSize);                                        \
-            return launch_check("biquad_teensy_pipe4_kernel<1>");                                                                                          \
+            return launch_check(S->last_kernel);                                                                                                           \
         }
         MSDR_TQ4_LAUNCH(64) MSDR_TQ4_LAUNCH(32) MSDR_TQ4_LAUNCH(16)
 #undef MSDR_TQ4_LAUNCH
     }
+    S->last_kernel = "biquad_teensy_kernel<1>";
     hipLaunchKernelGGL((biquad_teensy_kernel<1>), dim3((S->channels + 63) / 64), dim3(64), 0, S->ctx->stream, d_data, S->d_defs,
                        (int *)nullptr, (int)S->channels, (long long)blockSize);
-    return launch_check("biquad_teensy_kernel");
+    return launch_check(S->last_kernel);
 }
+extern "C" const char *msdr_biquad_q15_last_kernel(msdr_biquad_q15 *S) { return S ? S->last_kernel : nullptr; }
 extern "C" int msdr_biquad_q15_get_definition(msdr_biquad_q15 *S, uint32_t channel, int32_t definition[32])
 {
     if (!S || !definition || channel >= S->channels) return fail(MSDR_STATUS_ARGUMENT_ERROR, "bad argument");
@@ -1923,7 +1928,8 @@ struct msdr_frontend {
     msdr_ctx *ctx;
     uint32_t channels;
     int *d_state;          // [channels][kFeStateInts]
-    int pipe_ch;           // channels per workgroup of frontend_pipe4_kernel (64 / 32 / 16), 0: the two-wave pipeline, -1: no pipeline (read at create time)
+    int pipe_ch;           // channels per workgroup of frontend_pipe4_kernel: 64 / 32 / 16 (read at create time)
+    const char *last_kernel = "";     // msdr_frontend_last_kernel: the kernel the last update() launched, set in the branch that launches it
 };
 
 static int fe_edit(msdr_frontend *fe, const std::function<void(uint32_t, int *)> &f)
@@ -1991,26 +1997,24 @@ extern "C" int msdr_frontend_update(msdr_frontend *fe, const void *d_adc, q15_t 
     if (!d_adc || !d_out) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null buffer");
     if (blockSize % 128u) return fail(MSDR_STATUS_LENGTH_ERROR, "the front end runs in AUDIO_BLOCK_SAMPLES = 128 blocks: blockSize %u is not a multiple", blockSize);
     if (stages & ~MSDR_FE_ALL) return fail(MSDR_STATUS_ARGUMENT_ERROR, "unknown stage bits");
-    if (stages == MSDR_FE_ALL && fe->pipe_ch >= 0 && (reinterpret_cast<uintptr_t>(d_adc) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15) == 0) {
+    if (stages == MSDR_FE_ALL && (reinterpret_cast<uintptr_t>(d_adc) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_out) & 15) == 0) {
         // the recursion alone on one wave, everything element-wise on the others (msdr_frontend.hiph)
 #define MSDR_FE4_LAUNCH(CH_)                                                                                                                              \
         if (fe->pipe_ch == CH_ && fe->channels % CH_ == 0) {                                                                                              \
+            fe->last_kernel = "frontend_pipe4_kernel<" #CH_ ">";                                                                                          \
             hipLaunchKernelGGL(frontend_pipe4_kernel<CH_>, dim3(fe->channels / CH_), dim3(fe4_threads(CH_)), fe4_lds_bytes(CH_), fe->ctx->stream,         \
                                (const unsigned short *)d_adc, (short *)d_out, fe->d_state, (int)fe->channels, (long long)blockSize);                      \
-            return launch_check("frontend_pipe4_kernel");                                                                                                 \
+            return launch_check(fe->last_kernel);                                                                                                         \
         }
         MSDR_FE4_LAUNCH(64) MSDR_FE4_LAUNCH(32) MSDR_FE4_LAUNCH(16)
 #undef MSDR_FE4_LAUNCH
-        if ((fe->channels & 63u) == 0) {   // DC block on one wave, gain + AGC on the next: a two-wave slab pipeline
-            hipLaunchKernelGGL(frontend_pipe_kernel, dim3(fe->channels / 64), dim3(128), 0, fe->ctx->stream, (const unsigned short *)d_adc,
-                               (short *)d_out, fe->d_state, (int)fe->channels, (long long)blockSize);
-            return launch_check("frontend_pipe_kernel");
-        }
     }
+    fe->last_kernel = "frontend_kernel";
     hipLaunchKernelGGL(frontend_kernel, dim3((fe->channels + 63) / 64), dim3(64), 0, fe->ctx->stream, (const unsigned short *)d_adc,
                        (short *)d_out, fe->d_state, (int)fe->channels, (long long)blockSize, (int)stages);
-    return launch_check("frontend_kernel");
+    return launch_check(fe->last_kernel);
 }
+extern "C" const char *msdr_frontend_last_kernel(msdr_frontend *fe) { return fe ? fe->last_kernel : nullptr; }
 extern "C" int msdr_frontend_get_state(msdr_frontend *fe, uint32_t channel, int32_t state[MSDR_FE_STATE_WORDS])
 {
     if (!fe || !state) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
@@ -2404,6 +2408,7 @@ struct msdr_chain {
     bool dry_run = false;                // msdr_chain_graph_create: msdr_chain_process prepares a block-cadence call (tables, caches) and returns before its launches
     bool block_off = false;              // MSDR_NO_BLOCK=1 at create time: keep the wave-stream kernels at every call length (A/B runs, tests)
     bool no_fuse = false;                // MSDR_Q15_NO_FUSE=1 at create time: the biquad nodes as a kernel behind chain_q15mb_kernel, not its second phase
+    const char *node_kernel = "";        // msdr_chain_node_kernel: the kernel that ran the biquad nodes in the last call, set in the branch that launches it
     int blk_force = -1;                  // MSDR_BIQUAD_BLK at create time (0: never biquad_teensy_blk_kernel, 1: always where it applies; -1: the host's rule)
     std::vector<std::vector<float>> h_coef_i, h_coef_q;   // host copies for msdr_chain_set_mode
     std::vector<double> h_osc, h_cnum;                    // oscillator pairs {cos, sin}; combined numerator
@@ -3882,6 +3887,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     uint32_t flavour = 0;                // msdr_chain_info.flavour: MSDR_FLAVOUR_* of the launches below, set where each one is made
     uint32_t env_scan = 0;               // msdr_chain_info.env_scan: how the folded envelope flavour of chain_mfw_kernel scanned its row states
     bool nodes_fused = false;            // Q15 block cadence: the biquad nodes ran inside chain_q15mb_kernel
+    const char *node_kname = "";         // msdr_chain_node_kernel: the kernel that runs the biquad nodes of this call ("": no nodes, fp32 chains)
     unsigned block = kThreads;
     size_t lds_used = lds;
     int pc_tile = 0;
@@ -4026,6 +4032,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
             grid += bp.wgs; block = bp.nw * 64;
         }
         kname = nodes_fused ? "chain_q15mb_kernel (block tiles) + both biquad nodes" : "chain_q15mb_kernel (channel-batched block tiles)";
+        if (nodes_fused) node_kname = "chain_q15mb_kernel";
     }
     else if (use_qm) {
         // channels grouped by (tap set, flavour): a workgroup's waves share one table; one launch per group in use
@@ -4085,6 +4092,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         if (launch_chain_q15pcb(c->ctx->stream, c->mixer == kMixerFs4, q, &geo) != hipSuccess)
             return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pcb_kernel launch failed");
         kname = c->opc_active ? kQpcboKernelName : kQpcbKernelName;
+        if (c->nnodes) node_kname = "chain_q15pcb_kernel";
         grid = geo.grid; block = geo.block; lds_used = geo.lds_bytes; nseg = 1; pc_tile = geo.tile;
     }
     else if (use_pc) {
@@ -4123,44 +4131,55 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     if (use_qpcb) { /* (chain_q15pcb_kernel ran the nodes as its third phase, on the same records) */ }
     else if (c->nnodes == 2 && !nodes_fused) {      // biquad1_dac -> biquad2_dac in one pass over the audio
         const bool slabs = (c->channels & 63u) == 0 && (n_samples & 127u) == 0 && (reinterpret_cast<uintptr_t>(d_audio) & 15) == 0;
-        const int per_group = c->nodes[0]->pipe_ch ? c->nodes[0]->pipe_ch : 64;
+        const int per_group = c->nodes[0]->pipe_ch;
         // one 128-sample block, the reference's cadence, one stage per node: the pipeline over sub-slabs inside the block (biquad_teensy_blk_kernel),
         // ANY channel count -- the reference's own single receiver included (1 channel: 27 -> 12 us per tick; its rows past the end idle) --
         // while its 16-channel workgroups find a CU each (4096 channels: 15.1 -> 13.2 us per tick; at 8192 the slab kernel is ahead again,
         // 16.6 vs 17.3, tools/r05_nodes_x.sh); MSDR_BIQUAD_BLK=0 / 1 at create time overrides
         const uint32_t blk_wgs = (c->channels + kTqbCh - 1) / kTqbCh;
         if (chain_nodes_per_channel(c)) {      // every channel its own records: one lane = one channel with its own coefficients, any shape
+            node_kname = "biquad_teensy_pc_kernel<2>";
             if (launch_biquad_teensy_pc(c->ctx->stream, 2, (short *)d_audio, c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels, (long long)n_samples) != hipSuccess)
                 return fail(MSDR_STATUS_HIP_ERROR, "biquad_teensy_pc_kernel<2> launch failed");
         } else
         if (n_samples == 128 && (reinterpret_cast<uintptr_t>(d_audio) & 15) == 0 && c->nodes[0]->max_stage == 0 && c->nodes[1]->max_stage == 0 &&
-            (c->blk_force >= 1 || (c->blk_force < 0 && blk_wgs <= (uint32_t)c->ctx->num_cus)))
+            (c->blk_force >= 1 || (c->blk_force < 0 && blk_wgs <= (uint32_t)c->ctx->num_cus))) {
+            node_kname = "biquad_teensy_blk_kernel";
             hipLaunchKernelGGL(biquad_teensy_blk_kernel, dim3(blk_wgs), dim3(kTqbThreads), tqb_lds_bytes(), c->ctx->stream, (short *)d_audio,
                                c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels);
-        else
+        } else
         if ((n_samples & 127u) == 0 && (reinterpret_cast<uintptr_t>(d_audio) & 15) == 0 && c->channels % (unsigned)per_group == 0 &&
             c->nodes[0]->max_stage == 0 && c->nodes[1]->max_stage == 0) {
             // one stage per node (the reference's configuration): the recursions alone on two waves, the input products element-wise on the others
-            if (per_group == 64)
+            if (per_group == 64) {
+                node_kname = "biquad_teensy_pipe4_kernel<2,64>";
                 hipLaunchKernelGGL((biquad_teensy_pipe4_kernel<2, 64>), dim3(c->channels / 64), dim3(tq4_threads(64)), tq4_lds_bytes(64), c->ctx->stream, (short *)d_audio,
                                    c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels, (long long)n_samples);
-            else if (per_group == 32)
+            } else if (per_group == 32) {
+                node_kname = "biquad_teensy_pipe4_kernel<2,32>";
                 hipLaunchKernelGGL((biquad_teensy_pipe4_kernel<2, 32>), dim3(c->channels / 32), dim3(tq4_threads(32)), tq4_lds_bytes(32), c->ctx->stream, (short *)d_audio,
                                    c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels, (long long)n_samples);
-            else
+            } else {
+                node_kname = "biquad_teensy_pipe4_kernel<2,16>";
                 hipLaunchKernelGGL((biquad_teensy_pipe4_kernel<2, 16>), dim3(c->channels / 16), dim3(tq4_threads(16)), tq4_lds_bytes(16), c->ctx->stream, (short *)d_audio,
                                    c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels, (long long)n_samples);
+            }
         }
-        else if (slabs)
+        else if (slabs) {
+            node_kname = "biquad_teensy_pipe_kernel";
             hipLaunchKernelGGL(biquad_teensy_pipe_kernel, dim3(c->channels / 64), dim3(128), 0, c->ctx->stream, (short *)d_audio,
                                c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels, (long long)n_samples);     // node per wave, slab pipeline
-        else
+        } else {
+            node_kname = "biquad_teensy_kernel<2>";
             hipLaunchKernelGGL((biquad_teensy_kernel<2>), dim3((c->channels + 63) / 64), dim3(64), 0, c->ctx->stream, (short *)d_audio,
                                c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels, (long long)n_samples);
-        if (int rc = launch_check("biquad_teensy_kernel<2>")) return rc;
+        }
+        if (int rc = launch_check(node_kname)) return rc;
     } else if (c->nnodes == 1) {
         if (int rc = msdr_biquad_q15_update(c->nodes[0], (q15_t *)d_audio, (uint32_t)n_samples)) return rc;
+        node_kname = c->nodes[0]->last_kernel;
     }
+    c->node_kernel = node_kname;
 
     // rows f2 / f3 inside the fp32 chain: PLL / LMS channels are redone behind the main kernel (before the history moves on: a rebuilt
     // auxiliary chain takes over the history and table position this call started from)
@@ -5103,6 +5122,7 @@ extern "C" int msdr_chain_destroy(msdr_chain *c)
     return 0;
 }
 
+extern "C" const char *msdr_chain_node_kernel(msdr_chain *c) { return c ? c->node_kernel : nullptr; }
 extern "C" int msdr_chain_get_info(msdr_chain *c, msdr_chain_info *info)
 {
     if (!c || !info) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");

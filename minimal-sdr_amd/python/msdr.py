@@ -524,6 +524,12 @@ def _input_rows(what, rows, channels, n_inputs):
     return np.ascontiguousarray(r, np.uint32), int(n_inputs)
 
 
+def _kernel_name(f, h):
+    f.restype = C.c_char_p
+    f.argtypes = [_p]
+    return f(h).decode()
+
+
 class BiquadQ15(_Instance):
     """AudioFilterBiquad: setCoefficients(stage, coef[5]) / update(), batched over channels."""
     _destroy = "msdr_biquad_q15_destroy"
@@ -545,6 +551,10 @@ class BiquadQ15(_Instance):
 
     def update(self, d_data, n):
         _ck(self.ctx.lib.msdr_biquad_q15_update(self.h, d_data.ptr, n))
+
+    def last_kernel(self):
+        """msdr_biquad_q15_last_kernel: the kernel the last update() launched, with its template arguments ("" before the first)."""
+        return _kernel_name(self.ctx.lib.msdr_biquad_q15_last_kernel, self.h)
 
     def definition(self, channel=0):
         d = np.zeros(32, np.int32)
@@ -575,6 +585,10 @@ class Frontend(_Instance):
     def update(self, d_adc, d_out, n, stages=FE_ALL):
         _ck(self.ctx.lib.msdr_frontend_update(self.h, d_adc.ptr if hasattr(d_adc, "ptr") else d_adc,
                                               d_out.ptr if hasattr(d_out, "ptr") else d_out, C.c_uint32(n), C.c_uint32(stages)))
+
+    def last_kernel(self):
+        """msdr_frontend_last_kernel: the kernel the last update() launched, with its template arguments ("" before the first)."""
+        return _kernel_name(self.ctx.lib.msdr_frontend_last_kernel, self.h)
 
     def state(self, channel=0):
         st = np.zeros(32, np.int32)
@@ -886,6 +900,10 @@ class Chain(_Instance):
         every state kept; the cascade runs in CMSIS order behind the demodulator kernel (biquad_df1_seq_pc_kernel) from the first call on."""
         c = _cascade_per_channel("set_biquad_coeffs_channels", coeffs, self.stages)
         _ck(self.ctx.lib.msdr_chain_set_biquad_coeffs_channels(self.h, C.c_uint32(first_channel), C.c_uint32(c.shape[0]), _hp(c)))
+
+    def node_kernel(self):
+        """msdr_chain_node_kernel: the kernel that ran the biquad nodes in the last process() ("" for no nodes, fp32 chains, before the first call)."""
+        return _kernel_name(self.ctx.lib.msdr_chain_node_kernel, self.h)
 
     def info(self):
         i = ChainInfo()

@@ -77,6 +77,7 @@ def test_every_channel_its_own_notch(ctx, orc, channels, block):
     for call in range(3):                                        # state carried from call to call
         x = signal(rng, channels, block)
         got = run_update(ctx, S, x, misalign=(call == 1))
+        assert S.last_kernel() == "biquad_teensy_pc_kernel<1>"
         for c in range(channels):
             assert np.array_equal(got[c], orc.biquad_teensy_update(nodes[c], x[c])), (call, c)
     check_definitions(S, nodes, range(channels))
@@ -107,6 +108,7 @@ def test_mixed_stage_counts_inside_one_wave(ctx, orc, channels, block):
     for call in range(3):
         x = signal(rng, channels, block)
         got = run_update(ctx, S, x)
+        assert S.last_kernel() == "biquad_teensy_pc_kernel<1>"
         for c in range(channels):
             assert np.array_equal(got[c], orc.biquad_teensy_update(nodes[c], x[c])), (call, c)
     check_definitions(S, nodes, range(channels))
@@ -148,6 +150,8 @@ def test_same_coefficients_everywhere_equal_the_uniform_call(ctx, channels, bloc
     for call in range(3):
         x = signal(rng, channels, block)
         assert np.array_equal(run_update(ctx, U, x), run_update(ctx, P, x)), call
+        assert U.last_kernel() == ("biquad_teensy_pipe4_kernel<1,16>" if (channels, block) in ((64, 1024), (128, 256)) else "biquad_teensy_kernel<1>")
+        assert P.last_kernel() == "biquad_teensy_pc_kernel<1>"
     for c in (0, channels - 1):
         assert np.array_equal(U.definition(c), P.definition(c)), c
 
@@ -170,6 +174,8 @@ def test_hand_over_from_the_uniform_kernels_mid_stream(ctx, orc, channels, block
                 orc_set(orc, nodes[c], 0, rows[c - lo])
         x = signal(rng, channels, block)
         got = run_update(ctx, S, x)
+        uniform = "biquad_teensy_pipe4_kernel<1,16>" if block % 128 == 0 and channels % 16 == 0 else "biquad_teensy_kernel<1>"
+        assert S.last_kernel() == (uniform if call < 2 else "biquad_teensy_pc_kernel<1>"), (call, S.last_kernel())
         for c in range(channels):
             assert np.array_equal(got[c], orc.biquad_teensy_update(nodes[c], x[c])), (call, c)
     check_definitions(S, nodes, range(channels))
@@ -228,6 +234,7 @@ def _chain_case(ctx, orc, ch, block):
         for o in range(0, x.shape[1], step):
             dx, dy = ctx.to_device(x[:, o:o + step]), ctx.array((ch, step), np.int16)
             chain.process(dx, dy, step)
+            assert chain.node_kernel() == "biquad_teensy_pc_kernel<2>"
             got[:, o:o + step] = dy.download()
         for c in range(ch):
             want = orc.chain_q15(x[c], orclib.AM, taps, taps, biquads=nodes[c], state=states[c])
@@ -279,6 +286,7 @@ def test_graph_made_before_is_refused_and_one_made_after_replays_bit_exactly(ctx
         o += B * T
 
     g = chain.graph(dxs, dys, B)                                 # uniform nodes: the fused tick
+    assert chain.node_kernel() == "chain_q15mb_kernel"
     replay(g)
     chain.set_node_coefficients_channels(1, 0, 0, rows)
     with pytest.raises(msdr.MsdrError) as e:                     # its launches keep a node's coefficients uniform
@@ -286,6 +294,7 @@ def test_graph_made_before_is_refused_and_one_made_after_replays_bit_exactly(ctx
     assert e.value.status == msdr.STATUS_ARGUMENT_ERROR
     g.close()
     g = chain.graph(dxs, dys, B)                                 # demodulator kernel + biquad_teensy_pc_kernel<2>
+    assert chain.node_kernel() == "biquad_teensy_pc_kernel<2>"
     for _ in range(3):
         replay(g)
     g.close()

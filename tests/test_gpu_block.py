@@ -340,7 +340,9 @@ def test_block_q15_reference_graph_64_ticks_bit_exact(ctx, orc, golden, mixer, s
 def test_block_q15_nodes_sub_slab_pipeline_bit_exact(ctx, orc, golden, monkeypatch, ch):
     """biquad1_dac -> biquad2_dac at block cadence on channel counts the sub-slab kernel takes (multiples of 16: biquad_teensy_blk_kernel, the
     two recursions pipelined over 16-sample sub-slabs inside the one 128-sample block): 40 ticks against the oracle, state carried from tick to
-    tick, full-scale and -32768 inputs; and the same stream through the slab kernels (MSDR_BIQUAD_BLK=0): identical."""
+    tick, full-scale and -32768 inputs; and the same stream through the slab kernels (MSDR_BIQUAD_BLK=0): identical.  Chain.node_kernel() names
+    the kernel of every tick; at 4096 channels the host's own rule (256 workgroups <= the device's CU count) depends on the device's
+    partitioning, so the sub-slab kernel is forced there (MSDR_BIQUAD_BLK=1)."""
     rng = np.random.default_rng(640 + ch)
     ticks = 40
     taps = golden["fir/taps_am102"]
@@ -351,12 +353,14 @@ def test_block_q15_nodes_sub_slab_pipeline_bit_exact(ctx, orc, golden, monkeypat
     outs = []
     monkeypatch.setenv("MSDR_Q15_NO_FUSE", "1")                 # (the node kernels on their own: where the chain kernel takes the nodes in, this test would compare it with itself)
     for force in (None, "0"):
-        if force is None:
+        if force is None and ch == 4096:
+            monkeypatch.setenv("MSDR_BIQUAD_BLK", "1")
+        elif force is None:
             monkeypatch.delenv("MSDR_BIQUAD_BLK", raising=False)
         else:
             monkeypatch.setenv("MSDR_BIQUAD_BLK", force)
         chain = msdr.Chain(ctx, msdr.ARITH_Q15, ch, taps, taps, mode=orclib.AM, biquad_nodes=[[lp], [nt]])
-        outs.append(run_chain(ctx, chain, x, np.int16, 128))
+        outs.append(run_chain(ctx, chain, x, np.int16, 128, node_kernel="biquad_teensy_blk_kernel" if force is None else "biquad_teensy_pipe4_kernel<2,16>"))
         assert _is_qblock(chain), chain.info()["kernel"]
     monkeypatch.delenv("MSDR_BIQUAD_BLK", raising=False)
     monkeypatch.delenv("MSDR_Q15_NO_FUSE", raising=False)
@@ -404,6 +408,7 @@ def test_block_q15_nodes_inside_the_chain_kernel_bit_exact(ctx, orc, golden, mon
             got[:, t * 128:(t + 1) * 128] = dy.download()
             want_name = "chain_q15mb_kernel (block tiles) + both biquad nodes" if fuse else "chain_q15mb_kernel (channel-batched block tiles)"
             assert chain.info()["kernel"] == want_name, chain.info()["kernel"]
+            assert chain.node_kernel() == ("chain_q15mb_kernel" if fuse else "biquad_teensy_blk_kernel"), (t, chain.node_kernel())
         outs.append(got)
     monkeypatch.delenv("MSDR_Q15_NO_FUSE", raising=False)
     monkeypatch.delenv("MSDR_MB_NW", raising=False)

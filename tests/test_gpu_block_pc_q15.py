@@ -153,6 +153,13 @@ def test_fused_ticks_are_the_unfused_ticks_bit_for_bit(ctx, case):
         assert np.array_equal(ga, gb), (tag, what, t)
         assert fused(a) == want_a and unfused(a) == (not want_a), (tag, what, t, a.info())
         assert fused(b) == want_b and unfused(b) == (not want_b), (tag, what, t, b.info())
+        for chain, want in ((a, want_a), (b, want_b)):           # which kernel ran the nodes: the block kernel's third phase, or a kernel behind
+            if want:
+                assert chain.node_kernel() == ("chain_q15pcb_kernel" if nodes[0] else ""), (tag, what, t, chain.node_kernel())
+            elif nodes[1] == "pc":
+                assert chain.node_kernel() == "biquad_teensy_pc_kernel<%d>" % nodes[0], (tag, what, t, chain.node_kernel())
+            else:
+                assert chain.node_kernel() != "chain_q15pcb_kernel" and (chain.node_kernel() == "") == (nodes[0] == 0), (tag, what, t, chain.node_kernel())
         return ga
 
     loud = 0
@@ -199,6 +206,7 @@ def test_fused_bank_is_the_oracle_per_receiver(ctx, orc):
     for t in range(ticks):
         got[:, t * B:(t + 1) * B] = call(ctx, chain, x[:, t * B:(t + 1) * B])
         assert fused(chain) == (t > 0), (t, chain.info())          # (tick 0: the history still holds samples of the table before set_osc_channels)
+        assert chain.node_kernel() == ("chain_q15pcb_kernel" if t > 0 else "biquad_teensy_pc_kernel<2>"), (t, chain.node_kernel())
     for c in range(ch):
         st = {}
         nodes = [orc.biquad_teensy_new([lp]), orc.biquad_teensy_new([nrows[c]])]

@@ -20,8 +20,9 @@ CHAIN = [("AM", orclib.AM, "fir/taps_am102", "fir/taps_am102"),
          ("CW", orclib.CW, "taps/FIR_CW_I_coeffs", "taps/FIR_CW_Q_coeffs")]
 
 
-def run_chain(ctx, chain, x, out_dtype, block=None):
-    """x: [channels, n] int16. block=None -> one call; else consecutive calls of `block` samples."""
+def run_chain(ctx, chain, x, out_dtype, block=None, node_kernel=None):
+    """x: [channels, n] int16. block=None -> one call; else consecutive calls of `block` samples.
+    node_kernel: what Chain.node_kernel() must report after every call (the kernel that ran the biquad nodes)."""
     ch, n = x.shape
     out = np.empty((ch, n), out_dtype)
     step = block or n
@@ -29,6 +30,8 @@ def run_chain(ctx, chain, x, out_dtype, block=None):
         m = min(step, n - o)
         dx, dy = ctx.to_device(x[:, o:o + m]), ctx.array((ch, m), out_dtype)
         chain.process(dx, dy, m)
+        if node_kernel is not None:
+            assert chain.node_kernel() == node_kernel, (o, m, chain.node_kernel(), chain.info()["kernel"])
         out[:, o:o + m] = dy.download()
     return out
 
@@ -784,7 +787,7 @@ def test_chain_q15_two_biquad_nodes_pipeline(ctx, orc, golden, ch):
     hs = orc.biquad_design(orclib.BQ_HIGHSHELF, np.float32(2000.0), 9.0, 0.8)
     for nodes in ([lr, [nt]], [[nt], [hs, nt]]):
         chain = msdr.Chain(ctx, msdr.ARITH_Q15, ch, taps, taps, mode=orclib.LSB, biquad_nodes=nodes)
-        got = run_chain(ctx, chain, x, np.int16, 2 * B)                           # five calls of two slabs each
+        got = run_chain(ctx, chain, x, np.int16, 2 * B, node_kernel="biquad_teensy_pipe_kernel")      # five calls of two slabs each
         for c in list(range(0, ch, 13)) + [1, ch - 1]:
             want = orc.chain_q15(x[c], orclib.LSB, taps, taps, biquads=[orc.biquad_teensy_new(nd) for nd in nodes])
             assert np.array_equal(got[c], want), (ch, c)
@@ -794,8 +797,10 @@ def test_chain_q15_two_biquad_nodes_pipeline(ctx, orc, golden, ch):
 @pytest.mark.parametrize("block", [B, 2 * B, 3 * B, None])
 def test_chain_q15_one_stage_nodes_on_the_slab_pipeline(ctx, orc, golden, block, per_group, monkeypatch):
     """The reference's configuration -- one stage per node (low-pass .ino:391-393, Q = 15 notch .ino:356) -- on whole 64-channel groups:
-    biquad_teensy_pipe4_kernel<2> (the two recursions alone on two waves).  Calls of one, two and three slabs (the pipeline's start-up
-    and drain paths) and one long call; full-scale square wave; state carried from call to call."""
+    biquad_teensy_pipe4_kernel<2, per_group> (the two recursions alone on two waves) for calls of two and three slabs (the pipeline's
+    start-up and drain paths) and one long call.  Calls of ONE slab are the block cadence: there the nodes run as the second phase of
+    chain_q15mb_kernel, whatever per_group says (the node kernels at that length: tests/test_gpu_q15_ladders.py, tests/test_gpu_block.py).
+    Full-scale square wave; state carried from call to call."""
     monkeypatch.setenv("MSDR_BIQUAD_PIPE_CH", str(per_group))      # channels per workgroup (read when the nodes are created)
     rng = np.random.default_rng(7)
     ch, n = 128, 12 * B
@@ -805,7 +810,7 @@ def test_chain_q15_one_stage_nodes_on_the_slab_pipeline(ctx, orc, golden, block,
     lp = orc.biquad_design(orclib.BQ_LOWPASS, np.float32(5400 * CORR), 0.54)
     nt = orc.biquad_design(orclib.BQ_NOTCH, np.float32(3000 * CORR), 15.0)
     chain = msdr.Chain(ctx, msdr.ARITH_Q15, ch, taps, taps, mode=orclib.AM, biquad_nodes=[[lp], [nt]])
-    got = run_chain(ctx, chain, x, np.int16, block)
+    got = run_chain(ctx, chain, x, np.int16, block, node_kernel="chain_q15mb_kernel" if block == B else "biquad_teensy_pipe4_kernel<2,%d>" % per_group)
     for c in (0, 1, 63, 64, 127):
         want = orc.chain_q15(x[c], orclib.AM, taps, taps, biquads=[orc.biquad_teensy_new([lp]), orc.biquad_teensy_new([nt])])
         assert np.array_equal(got[c], want), (block, c)
@@ -821,7 +826,7 @@ def test_chain_q15_node_slab_pipeline_on_multiples_of_16_channels(ctx, orc, gold
     lp = orc.biquad_design(orclib.BQ_LOWPASS, np.float32(5400 * CORR), 0.54)
     nt = orc.biquad_design(orclib.BQ_NOTCH, np.float32(3000 * CORR), 15.0)
     chain = msdr.Chain(ctx, msdr.ARITH_Q15, ch, taps, taps, mode=orclib.AM, biquad_nodes=[[lp], [nt]])
-    got = run_chain(ctx, chain, x, np.int16, 2 * B)
+    got = run_chain(ctx, chain, x, np.int16, 2 * B, node_kernel="biquad_teensy_pipe4_kernel<2,16>")
     for c in range(ch):
         want = orc.chain_q15(x[c], orclib.AM, taps, taps, biquads=[orc.biquad_teensy_new([lp]), orc.biquad_teensy_new([nt])])
         assert np.array_equal(got[c], want), c

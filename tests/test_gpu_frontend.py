@@ -80,6 +80,7 @@ def test_frontend_slab_pipeline_channels_per_workgroup(ctx, orc, per_group, call
         m = min(call_blocks, nblk - b0) * B
         dx, dy = ctx.to_device(np.ascontiguousarray(x[:, b0 * B:b0 * B + m])), ctx.array((ch, m), np.int16)
         fe.update(dx, dy, m)
+        assert fe.last_kernel() == "frontend_pipe4_kernel<%d>" % per_group
         got[:, b0 * B:b0 * B + m] = dy.download()
     for c in range(ch):
         f = orc.frontend_new(first_conversion=int(x[c, 0]))
@@ -99,6 +100,7 @@ def test_frontend_in_place_on_the_slab_pipeline(ctx, orc):
     fe.prime(x[:, 0])
     d = ctx.to_device(x.view(np.int16))
     fe.update(d, d, nblk * B)
+    assert fe.last_kernel() == "frontend_pipe4_kernel<16>"       # (64 channels: the host's rule takes 16 per workgroup)
     got = d.download()
     for c in (0, 17, 63):
         f = orc.frontend_new(first_conversion=int(x[c, 0]))

@@ -227,6 +227,7 @@ def test_biquad_q15_bit_exact(ctx, orc, n_stage):
             x[:, :] = 32767                                       # drive into saturation
         d = ctx.to_device(x)
         node.update(d, 2 * B)
+        assert node.last_kernel() == "biquad_teensy_kernel<1>"   # (70 channels: no multiple of the slab pipeline's 16)
         got = d.download()
         for c in range(ch):
             assert np.array_equal(got[c], orc.biquad_teensy_update(refs[c], x[c])), (blk, c)
@@ -254,6 +255,7 @@ def test_biquad_q15_slab_pipeline_on_channel_counts_that_are_not_whole_waves(ctx
         x = _rand16(rng, (ch, nb * B), 20000)
         d = ctx.to_device(x)
         node.update(d, nb * B)
+        assert node.last_kernel() == "biquad_teensy_pipe4_kernel<1,16>"
         got = d.download()
         for c in range(ch):
             assert np.array_equal(got[c], orc.biquad_teensy_update(refs[c], x[c])), (nb, c)
@@ -282,6 +284,7 @@ def test_biquad_q15_one_stage_node_on_the_slab_pipeline(ctx, orc, kind, per_grou
             x[:, : n // 2] = 32767
         d = ctx.to_device(x)
         node.update(d, n)
+        assert node.last_kernel() == "biquad_teensy_pipe4_kernel<1,%d>" % per_group
         got = d.download()
         for c in (0, 1, 63, 64, 127):
             assert np.array_equal(got[c], orc.biquad_teensy_update(refs[c], x[c])), (blk, c)
@@ -292,6 +295,7 @@ def test_biquad_q15_one_stage_node_on_the_slab_pipeline(ctx, orc, kind, per_grou
     x = _rand16(rng, (ch, 2 * B), 6000)
     d = ctx.to_device(x)
     node.update(d, 2 * B)
+    assert node.last_kernel() == "biquad_teensy_kernel<1>"
     assert np.array_equal(d.download()[1], orc.biquad_teensy_update(refs[1], x[1]))
 
 
