@@ -681,7 +681,8 @@ typedef struct {
     uint32_t grid, block, lds_bytes;
     uint32_t time_segments, warmup, tile;
     uint32_t taps_padded;
-    uint32_t mfma_ksteps;            /* matrix-core kernel: 16-sample k-steps (3 MFMAs each) per 1024-output wave tile, else 0 */
+    uint32_t mfma_ksteps;            /* matrix-core kernel: k-steps (3 MFMAs each) issued per 1024-output wave tile, else 0; a run's first and last
+                                        16-sample step merged into one 2:4-sparse step (chain_mfw_kernel) count as one */
     uint32_t env_scan;               /* chain_mfw_kernel, envelope tables with a 1- or 2-section cascade as matrix products: how the row states
                                       * were scanned in the last call.  0 = that flavour did not run; 1 = every section (2 x 2 or 4 x 4 matrices);
                                       * 2 / 3 = section 0 / 1 is row-local (its transition over a 32-sample row is nothing in fp32: it takes no

@@ -25,6 +25,7 @@
 #include "msdr_design.h"
 #include "msdr_cascade_state.h"
 #include "msdr_kstack.h"
+#include "msdr_sparse24.h"
 
 #include <algorithm>
 #include <atomic>
@@ -2375,6 +2376,8 @@ struct msdr_chain {
     // matrix-core path (msdr_chain_mfma.hiph): any short-period oscillator, any mode
     bool mf_ok;
     int mf_halo, mf_bsteps, mf_stride;
+    int mf_xsteps = 0;                   // 2 KB steps of merged first + last k-steps behind the dense fragments (msdr_sparse24.h); wave-stream kernel only
+    int mf_merged[2] = {0, 0};           // runs every SSB table / every envelope table merges: k-steps the wave-stream kernel does NOT issue
     char *d_mf_tab;
     BiquadCascadeTables<kMfL> *d_bq_mf;
     BiquadCascadeTables<32> *d_bq_mf32;
@@ -2880,7 +2883,12 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
         bool compact = fr && N >= 128;
         if (const char *e = getenv("MSDR_FR_COMPACT")) compact = fr && atoi(e) != 0;
         const int CS = compact ? mw_compact_stride(H) : 0;
-        int bsteps = 0;
+        int bsteps = 0, xsteps = 0;
+        int merged_min[2] = {1 << 30, 1 << 30};     // [SSB tables, envelope tables]
+        // the first and last k-step of a run as one 2:4-sparse step (msdr_sparse24.h): de-interleaved fragment tables; MSDR_MFW_SPARSE=0 at
+        // create time keeps every run dense (A/B runs, tests)
+        bool sparse_on = !fr;
+        if (const char *e = getenv("MSDR_MFW_SPARSE")) sparse_on = sparse_on && atoi(e) != 0;
         const bool ok = true;
         std::vector<double> M[2];
         M[0].resize((size_t)KIv * 32); M[1].resize((size_t)KIv * 32);
@@ -3201,10 +3209,53 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
                     T.h.cs = CS; T.h.bstep = compact ? 32 : 2048;
                     T.h.nsteps = ns;
                     bsteps = std::max(bsteps, ns);
+                    int nmerged = 0;
+                    if (sparse_on && !compact) {
+                        // where no entry of a run's first block meets one of its last block (every Toeplitz table; decided on the numbers), the pair
+                        // becomes one merged step behind the dense fragments, which stay complete: the other readers of this table see no change
+                        for (int o = 0; o < (v == 2 ? 2 : 1); o++)
+                            for (int src = 0; src < 2; src++) {
+                                const MfmaTableHeader::Run &R = T.h.run[o][src];
+                                if (R.cnt < 2) continue;
+                                uint16_t shi[kSp24FragHalfs], slo[kSp24FragHalfs];
+                                uint32_t sidx[64];
+                                if (!sparse24_merge(&M[o][(size_t)(2 * (16 * R.j0) + src) * 32], &M[o][(size_t)(2 * (16 * (R.j0 + R.cnt - 1)) + src) * 32], 64, scale,
+                                                    shi, slo, sidx)) continue;
+                                const size_t base = T.frags.size();
+                                T.frags.resize(base + kSp24Bytes / 2, (_Float16)0.0f);
+                                memcpy(&T.frags[base], shi, sizeof shi); memcpy(&T.frags[base + kSp24FragHalfs], slo, sizeof slo);
+                                memcpy(&T.frags[base + 2 * kSp24FragHalfs], sidx, sizeof sidx);
+                                T.h.sp[o][src] = (int)(base * 2);
+                                nmerged++;
+                            }
+                        T.h.xsteps = (int)((T.frags.size() * 2 + 2047) / 2048) - ns;
+                        T.frags.resize((size_t)(ns + T.h.xsteps) * 1024, (_Float16)0.0f);
+                        xsteps = std::max(xsteps, ns + T.h.xsteps);        // (for now: the steps this table takes in all)
+                    }
+                    merged_min[v == 2] = std::min(merged_min[v == 2], nmerged);
                 }
         }
+        // the LDS region holds the largest table, merged steps included: xsteps = what that adds to the dense steps.  Where it would cost a
+        // wave per SIMD (the rule below that picks the waves per workgroup) every run stays dense: a tile rate is worth more than two steps.
+        xsteps = std::max(0, xsteps - bsteps);
+        if (xsteps > 0) {
+            auto waves_on_cu = [&](int steps) {
+                int best_eff = 0;
+                for (int w = 1; w <= 16; w++) {
+                    const size_t l = mw_lds_bytes(H, steps, w, fr);
+                    if (l > 160 * 1024) break;
+                    const int on_cu = std::min<int>((int)((160 * 1024) / l), 16 / w) * w;
+                    best_eff = std::max(best_eff, on_cu >= 4 ? 4 * (on_cu / 4) : on_cu);
+                }
+                return best_eff;
+            };
+            if (waves_on_cu(bsteps + xsteps) < waves_on_cu(bsteps)) {
+                for (Tab &T : tabs) { T.frags.resize((size_t)T.h.nsteps * 1024); T.h.xsteps = 0; memset(T.h.sp, 0, sizeof T.h.sp); }
+                xsteps = 0; merged_min[0] = merged_min[1] = 0;
+            }
+        }
         if (ok && bsteps > 0) {
-            const int stride = kMfHdrBytes + bsteps * 2048;
+            const int stride = kMfHdrBytes + (bsteps + xsteps) * 2048;
             std::vector<char> blob((size_t)stride * tabs.size(), 0);
             for (size_t t = 0; t < tabs.size(); t++) {
                 memcpy(blob.data() + t * stride, &tabs[t].h, sizeof(MfmaTableHeader));
@@ -3223,6 +3274,7 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
             }
             if (!rc) {
                 c->mf_ok = true; c->mf_halo = H; c->mf_bsteps = bsteps; c->mf_stride = stride; c->mf_compact = compact;
+                c->mf_xsteps = xsteps; c->mf_merged[0] = merged_min[0]; c->mf_merged[1] = merged_min[1];
                 // wave-stream variant: waves per workgroup that put the most waves on a CU (<= 16: the kernel's <= 128 VGPRs allow
                 // 4 per SIMD) under the 160 KB of LDS -- counted in whole waves per SIMD.  A SIMD's tile rate is the same from two waves
                 // on (profiles/r03/c3_trims.txt), so a workgroup is as slow as its fullest SIMD: 13 waves (4 + 3 + 3 + 3) ran 4 % behind
@@ -3232,7 +3284,7 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
                 if (const char *e = getenv("MSDR_DBG_NW")) wcap = std::max(1, std::min(16, atoi(e)));    // stamps build: a lone wave per SIMD etc.
 #endif
                 for (int w = 1; w <= wcap; w++) {
-                    const size_t l = mw_lds_bytes(H, bsteps, w, fr);
+                    const size_t l = mw_lds_bytes(H, bsteps + xsteps, w, fr);
                     if (l > 160 * 1024) break;
                     const int wgs = std::min<int>((int)((160 * 1024) / l), wcap / w);
                     const int on_cu = wgs * w, eff = on_cu >= 4 ? 4 * (on_cu / 4) : on_cu;
@@ -3240,7 +3292,7 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
                 }
                 if (const char *e = getenv("MSDR_MFW_NW")) {     // A/B runs: a given number of waves per workgroup, where it fits (one workgroup per CU then)
                     const int w = atoi(e);
-                    if (w >= 1 && w <= 16 && mw_lds_bytes(H, bsteps, w, fr) <= 160 * 1024) { c->mfw_nw = w; best = w * std::max<int>(1, std::min<int>((int)((160 * 1024) / mw_lds_bytes(H, bsteps, w, fr)), 16 / w)); }
+                    if (w >= 1 && w <= 16 && mw_lds_bytes(H, bsteps + xsteps, w, fr) <= 160 * 1024) { c->mfw_nw = w; best = w * std::max<int>(1, std::min<int>((int)((160 * 1024) / mw_lds_bytes(H, bsteps + xsteps, w, fr)), 16 / w)); }
                 }
                 c->mfw_waves_per_cu = best;
                 if (best > 0) rc = dzalloc(ctx, (size_t)c->channels * kBqStateFloats, &c->d_bq_state_alt);
@@ -3729,7 +3781,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         const bool need_ssb = chain_summary(c).any_ssb, need_env = chain_summary(c).any_env;
         use_mfb = c->nstages == 0 || ((!need_ssb || c->mfw_ssb_fold) && (!need_env || c->mfw_am_fold));
     }
-    p.mf_tab = c->d_mf_tab; p.mf_stride = c->mf_stride; p.mf_halo = c->mf_halo; p.mf_bsteps = c->mf_bsteps; p.bq_mf = c->d_bq_mf; p.bq_mf32 = c->d_bq_mf32;
+    p.mf_tab = c->d_mf_tab; p.mf_stride = c->mf_stride; p.mf_halo = c->mf_halo; p.mf_bsteps = c->mf_bsteps; p.mf_xsteps = c->mf_xsteps; p.bq_mf = c->d_bq_mf; p.bq_mf32 = c->d_bq_mf32;
     // the same for the Q15 chain (msdr_chain_q15mb.hiph); SYNCAM channels under the PLL hand I and Q to a kernel behind: the streaming kernel
     bool use_qb = false;
     if (use_qm && chain_summary(c).qm_sets_ok && !c->block_off && !c->qm_fr && !pll_active && mb_n_ok((long long)n_samples) && (int)c->hist_len == c->qm_halo &&
@@ -3877,7 +3929,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         if (n_samples % c->osc_len) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the oscillator's position changes from call to call at this block length: not capturable");
         return 0;
     }
-    const size_t lds = use_mfw ? mw_lds_bytes(c->mf_halo, c->mf_bsteps, c->mfw_nw, c->mf_fr) : use_fold ? fold_lds_bytes(p.ntaps_pad) : chain_lds_bytes(p.ntaps_pad);
+    const size_t lds = use_mfw ? mw_lds_bytes(c->mf_halo, c->mf_bsteps + c->mf_xsteps, c->mfw_nw, c->mf_fr) : use_fold ? fold_lds_bytes(p.ntaps_pad) : chain_lds_bytes(p.ntaps_pad);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (c->timing && c->events.size() < 8192) {
         HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
@@ -3886,6 +3938,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     const char *kname = f32 ? "chain_kernel<ArithF32>" : "chain_kernel<ArithQ15>";
     uint32_t flavour = 0;                // msdr_chain_info.flavour: MSDR_FLAVOUR_* of the launches below, set where each one is made
     uint32_t env_scan = 0;               // msdr_chain_info.env_scan: how the folded envelope flavour of chain_mfw_kernel scanned its row states
+    int merged_steps = -1;               // chain_mfw_kernel: k-steps per tile that went into merged steps (the least over the launches), -1 = no such launch
     bool nodes_fused = false;            // Q15 block cadence: the biquad nodes ran inside chain_q15mb_kernel
     const char *node_kname = "";         // msdr_chain_node_kernel: the kernel that runs the biquad nodes of this call ("": no nodes, fp32 chains)
     unsigned block = kThreads;
@@ -3937,6 +3990,8 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
                 continue;
             }
             (void)launch_chain_mfw(c->ctx->stream, (int)c->nstages, part == 1, fold, c->mf_fr, rowlocal, g, block, lds, q);
+            const int part_merged = mw_merges_steps((int)c->nstages, part == 1, fold, c->mf_fr, rowlocal) ? c->mf_merged[part] : 0;
+            merged_steps = merged_steps < 0 ? part_merged : std::min(merged_steps, part_merged);
             if (int rc = launch_check("chain_mfw_kernel")) return rc;
             if (fold) flavour |= part == 0 ? MSDR_FLAVOUR_SSB_FOLD : MSDR_FLAVOUR_ENV_FOLD;
             if (c->mf_fr) flavour |= MSDR_FLAVOUR_FULL_RATE | (c->mf_compact ? MSDR_FLAVOUR_COMPACT : 0u) | ((part == 1 && c->mf_share_iq) ? MSDR_FLAVOUR_SHARED_IQ : 0u);
@@ -4218,7 +4273,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     c->info.env_scan = env_scan; c->info.flavour = f32 ? flavour : 0u;
     c->info.time_segments = (uint32_t)nseg; c->info.warmup = (uint32_t)p.warm; c->info.tile = (uint32_t)((use_pc || use_pcf) ? pc_tile : kTile);
     c->info.taps_padded = (use_pc || use_pcf) ? (uint32_t)c->pc_np : c->ntaps_pad;
-    c->info.mfma_ksteps = use_mf ? (uint32_t)c->mf_bsteps : use_qm ? (uint32_t)c->qm_bsteps : 0u;
+    c->info.mfma_ksteps = use_mf ? (uint32_t)(c->mf_bsteps - std::max(merged_steps, 0)) : use_qm ? (uint32_t)c->qm_bsteps : 0u;
     return 0;
 }
 

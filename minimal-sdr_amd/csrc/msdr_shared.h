@@ -96,6 +96,7 @@ struct ChainParams {
     int mf_stride;
     int mf_halo;               // H: window samples before the tile, a multiple of 32 >= ntaps - 1
     int mf_bsteps;             // k-steps the LDS B region holds (max n0 + n1 over the tables)
+    int mf_xsteps;             // wave-stream kernel: 2 KB steps of merged first + last k-steps behind them (msdr_sparse24.h), 0 = none
     const void *bq_mf;         // BiquadCascadeTables<16>: 16-sample chunks
     const void *bq_mf32;       // BiquadCascadeTables<32>: 32-sample blocks (msdr_biquad_paired.hiph)
     int mf_waves;              // waves per workgroup: 4 or 8
