@@ -303,6 +303,18 @@ static int dzalloc(msdr_ctx *ctx, size_t count, T **d)
     }
     return 0;
 }
+// grows a device buffer to at least `need` elements (zeroed; what it held is gone): waits for the stream's work on the old block first, and
+// leaves pointer and capacity zero on failure
+template <typename T>
+static int grow_device(msdr_ctx *ctx, T **d, size_t *cap, size_t need)
+{
+    if (need <= *cap) return 0;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    hipFree(*d); *d = nullptr; *cap = 0;
+    if (int rc = dzalloc(ctx, need, d)) return rc;
+    *cap = need;
+    return 0;
+}
 static int grid_1d(long long total, int block = 256)
 {
     long long g = (total + block - 1) / block;
@@ -3661,12 +3673,7 @@ static int chain_block_tiles(msdr_chain *c, int n_, const std::function<int(uint
             }
         }
     }
-    if (tab.size() > c->btiles_cap) {
-        HIP_TRY(hipStreamSynchronize(c->ctx->stream));
-        hipFree(c->d_btiles); c->d_btiles = nullptr; c->btiles_cap = 0;
-        if (int rc = dzalloc(c->ctx, tab.size(), &c->d_btiles)) return rc;
-        c->btiles_cap = tab.size();
-    }
+    if (int rc = grow_device(c->ctx, &c->d_btiles, &c->btiles_cap, tab.size())) return rc;
     HIP_TRY(hipMemcpyAsync(c->d_btiles, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, c->ctx->stream));
     HIP_TRY(hipStreamSynchronize(c->ctx->stream));        // `tab` is a local
     c->btiles_mode_gen = c->mode_gen; c->btiles_n = (long long)n_;
@@ -3674,18 +3681,267 @@ static int chain_block_tiles(msdr_chain *c, int n_, const std::function<int(uint
 }
 
 static int chain_leave_generic(msdr_chain *c);
-extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_audio, uint64_t n_samples)
-{
-    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
-    if (int rc = bind(c->ctx)) return rc;
-    if (n_samples == 0) return 0;
-    if (!d_if || !d_audio) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null buffer");
-    if (n_samples > (1ull << 31) - 4096) return fail(MSDR_STATUS_LENGTH_ERROR, "n_samples too large for one call");
-    const bool f32 = (c->arith == MSDR_ARITH_F32);
-    if (!f32 && c->nnodes && (n_samples & 1u))
-        return fail(MSDR_STATUS_LENGTH_ERROR, "AudioFilterBiquad processes sample pairs: n_samples must be even");
 
-    ChainParams p;
+// ---- msdr_chain_process: which demodulator kernel a call runs, decided once (chain_decide), one function per path ------------------------------
+enum ChainPath {
+    kPathF32Pcb, kPathF32Pc, kPathMfb, kPathMfw, kPathFold, kPathF32Generic,         // fp32
+    kPathQ15Mb, kPathQ15Mf, kPathQ15Pcb, kPathQ15Pc, kPathQ15Generic                 // Q15
+};
+static bool path_per_channel(ChainPath k) { return k == kPathF32Pcb || k == kPathF32Pc || k == kPathQ15Pcb || k == kPathQ15Pc; }     // per-channel FIR coefficients
+static bool path_block(ChainPath k) { return k == kPathF32Pcb || k == kPathMfb || k == kPathQ15Mb || k == kPathQ15Pcb; }             // block cadence: the kernel writes the next history itself
+static bool path_mfw(ChainPath k) { return k == kPathMfb || k == kPathMfw; }           // the wave-stream kernel's tile, warm-up and tables
+static bool path_qm(ChainPath k) { return k == kPathQ15Mb || k == kPathQ15Mf; }        // the Q15 matrix-core tables
+
+// MSDR_CHAIN_OUT_I16: the kernel converts in its store phase where nothing runs behind it; otherwise the fp32 audio goes to a scratch batch and
+// is converted last
+enum ChainI16 { kI16None, kI16InKernel, kI16ViaScratch };
+
+struct ChainDecision {
+    ChainPath path;
+    bool pll_active;           // Q15: SYNCAM channels go through the PLL demodulator behind the kernel
+    bool anr_active;           // Q15: the LMS filter runs behind the kernel
+    bool post_active;          // fp32: PLL / LMS channels are redone behind the kernel through the auxiliary chain
+    bool mf;                   // fp32: the call's parameters describe the matrix-core tables (also where mfw_nw == 0 sends it to the generic kernel)
+    ChainI16 i16;
+    bool nodes_fused;          // Q15 block cadence: the biquad nodes run inside chain_q15mb_kernel
+};
+
+static bool chain_post_active(msdr_chain *c) { return c->f32_pll || c->aux != nullptr || chain_summary(c).any_anr; }
+static bool chain_anr_active(const msdr_chain *c) { return c->anr && (c->d_anr_on || c->anr_all > 0); }
+// the two biquad nodes as chain_q15mb_kernel's second phase: the reference's configuration (one stage per node), one 128-sample block;
+// MSDR_Q15_NO_FUSE=1 at create time: the node kernel behind it as before.  Asked twice, and the two must agree: the tile table is built
+// with three or more waves per workgroup where this holds (chain_prepare), the call fuses where additionally nothing runs between the
+// demodulator and the nodes and every launch has one tile per wave on three or more waves (chain_decide, chain_prepare).  With the LMS
+// filter on, the table is therefore sized for fusing although the call does not fuse.
+static bool chain_nodes_fusable(const msdr_chain *c, uint64_t n_samples)
+{
+    return c->nnodes == 2 && c->nodes[0]->max_stage == 0 && c->nodes[1]->max_stage == 0 && n_samples == 128 && !c->no_fuse && !chain_nodes_per_channel(c);
+}
+
+// Makes no HIP call and changes nothing but chain_summary's cache.  Precedence, first eligible wins:
+//   fp32: f32pcb, f32pc (both: per-channel taps only), mfb, mfw, fold, generic.  A chain with mf_ok but mfw_nw == 0 takes the generic kernel,
+//         not the folded one.  force_generic (history samples that arrived under an earlier oscillator table are still in reach,
+//         msdr_chain_set_osc: the as-written kernel mixes each with the table of its own time) leaves the per-channel kernels and generic.
+//   Q15:  q15mb, q15mf (matrix-core tables, no per-channel taps), q15pcb, q15pc (per-channel taps only), generic.
+static ChainDecision chain_decide(msdr_chain *c, const int16_t *d_if, const void *d_audio, uint64_t n_samples)
+{
+    ChainDecision d;
+    memset(&d, 0, sizeof d);
+    const bool block_n = mb_n_ok((long long)n_samples), osc_pending = !c->osc_pending.empty();
+    const bool in_aligned = (reinterpret_cast<uintptr_t>(d_if) & 15) == 0, out_aligned = (reinterpret_cast<uintptr_t>(d_audio) & 15) == 0;
+    const int pc_osc_len = c->mixer == kMixerFs4 ? 0 : (int)c->osc_len;
+    const bool uniform_fast = !c->pc_active && !c->force_generic;       // the kernels that share one tap table and mix with the current oscillator table alone
+    d.pll_active = c->pll && chain_summary(c).any_syncam;
+    d.anr_active = chain_anr_active(c);
+    if (c->arith == MSDR_ARITH_F32) {
+        d.post_active = chain_post_active(c);
+        d.mf = uniform_fast && c->mf_ok;
+        const bool mfw = d.mf && c->mfw_nw > 0;
+        // where the wave-stream kernels write: int16 straight to d_audio when nothing runs behind them, else fp32 to the scratch batch (a
+        // device allocation of its own: aligned)
+        const bool want_i16 = (c->flags & MSDR_CHAIN_OUT_I16) != 0, mfw_i16_direct = !c->seq_bq && !d.post_active;
+        const bool mfw_out_aligned = (want_i16 && !mfw_i16_direct) || out_aligned;
+        // msdr_chain_set_block_kernel: the whole block-cadence call of a per-channel chain in one launch (msdr_chain_f32pcb.hiph) -- where no
+        // oscillator generation is pending, nothing runs behind the kernel but a CMSIS-order cascade, and one wave's LDS fits
+        if (c->pc_active && c->block_pc && block_n && !osc_pending && !d.post_active &&
+            (!c->seq_bq || c->seq_bq->stages == 0 || c->seq_bq->sequential) && chain_f32pcb_lds((int)n_samples, c->pc_np, pc_osc_len, nullptr))
+            d.path = kPathF32Pcb;
+        else if (c->pc_active) d.path = kPathF32Pc;                  // per-channel taps: chain_f32pc_kernel in place of every uniform demodulator kernel
+        // block cadence (msdr_chain_mfb.hiph): one AUDIO_BLOCK (or another short block) per call -- channel-batched tiles, the next history
+        // written by the kernel itself.  Taken where the wave-stream kernel would run its folded flavours (or no cascade at all).
+        else if (mfw && !c->block_off && !c->mf_fr && c->nstages <= 2 && block_n && (int)c->hist_len == c->mf_halo && in_aligned && mfw_out_aligned &&
+                 mb_lds_bytes(c->mf_halo, (int)n_samples, c->mf_bsteps, 1, 1) <= 160 * 1024 &&
+                 (uint64_t)c->channels * std::max<uint64_t>((uint64_t)c->hist_len * 2, n_samples * 4) < (1ull << 32) &&       // (the kernel addresses with 32-bit byte offsets)
+                 (c->nstages == 0 || ((!chain_summary(c).any_ssb || c->mfw_ssb_fold) && (!chain_summary(c).any_env || c->mfw_am_fold))))
+            d.path = kPathMfb;
+        else if (mfw) d.path = kPathMfw;
+        // the folded kernel needs a short-period oscillator; AM additionally the exact Fs/4 pattern
+        else if (uniform_fast && !d.mf && c->fold_P > 0 && (c->fold_fs4_exact || !chain_summary(c).any_env)) d.path = kPathFold;
+        else d.path = kPathF32Generic;
+        d.i16 = !want_i16 ? kI16None : (d.path == kPathF32Pcb || (path_mfw(d.path) && mfw_i16_direct)) ? kI16InKernel : kI16ViaScratch;
+    } else {
+        const bool qm = uniform_fast && c->d_qm_tab != nullptr && chain_summary(c).qm_sets_ok;        // (a tap >= 32640: the VALU kernel runs)
+        // block cadence for the Q15 chain (msdr_chain_q15mb.hiph); SYNCAM channels under the PLL hand I and Q to a kernel behind: the streaming kernel
+        if (qm && !c->block_off && !c->qm_fr && !d.pll_active && block_n && (int)c->hist_len == c->qm_halo && in_aligned && out_aligned &&
+            qb_lds_bytes(c->qm_halo, (int)n_samples, c->qm_bsteps, 1, 1) <= 160 * 1024 &&
+            (uint64_t)c->channels * std::max<uint64_t>((uint64_t)c->hist_len * 2, n_samples * 2) < (1ull << 32))
+            d.path = kPathQ15Mb;
+        else if (qm) d.path = kPathQ15Mf;
+        // msdr_chain_set_block_kernel_q15: the whole call of a per-channel chain in one launch (msdr_chain_q15pcb.hiph) -- where no oscillator
+        // generation is pending, neither the PLL demodulator nor the LMS filter runs between the demodulator and the nodes, and one wave's LDS fits
+        else if (c->pc_active && c->block_q15 && block_n && !osc_pending && !d.pll_active && !d.anr_active &&
+                 chain_q15pcb_lds((int)n_samples, c->pc_np, pc_osc_len, nullptr))
+            d.path = kPathQ15Pcb;
+        else if (c->pc_active) d.path = kPathQ15Pc;                  // per-channel taps: chain_q15pc_kernel in place of every uniform demodulator kernel
+        else d.path = kPathQ15Generic;
+        d.nodes_fused = d.path == kPathQ15Mb && chain_nodes_fusable(c, n_samples) && !d.anr_active;       // (no PLL on this path; chain_prepare adds the per-launch checks)
+    }
+    return d;
+}
+
+// msdr_chain_graph_create's preparation pass: whether the launches of this call are fixed (capturable into a HIP graph); null, or why not
+static const char *chain_not_capturable(const msdr_chain *c, const ChainDecision &d, uint64_t n_samples)
+{
+    const bool f32 = c->arith == MSDR_ARITH_F32;
+    if (d.path == kPathF32Pcb)            // chain_f32pcb_kernel: one launch, its geometry fixed by the call's shape
+        return n_samples % c->osc_len ? "the oscillator's position changes from call to call at this block length: not capturable" : nullptr;
+    if (d.path == kPathF32Pc && c->block_pc) return "the block kernel does not take this call (32 .. 512 samples, a divisor of 1024; no pending oscillator change; no PLL / LMS channels; 64 KB of LDS): chain_f32pc_kernel's launch geometry is chosen per call, not capturable";
+    if (d.path == kPathF32Pc) return "an fp32 chain with per-channel FIR coefficients (chain_f32pc_kernel: launch geometry chosen per call) is not capturable";
+    if (path_per_channel(d.path)) {       // Q15: the demodulator kernel + the kernels behind it + the history kernel, a fixed set of launches at a block-cadence length
+        if (!mb_n_ok((long long)n_samples)) return "not a block-cadence call (32 .. 512 samples, a divisor of 1024): nothing to capture";
+        if (d.pll_active) return "the PLL demodulator runs behind the kernel: not capturable";
+        if (!c->osc_pending.empty()) return "a pending oscillator change (the history still holds samples of an earlier table): not capturable";
+    } else
+    if (d.path != kPathMfb && d.path != kPathQ15Mb) return "not a block-cadence call (32 .. 512 samples, a divisor of 1024, 16-byte aligned buffers, matrix-core tables, no pending oscillator change): nothing to capture";
+    if (c->seq_bq) return "the cascade runs in CMSIS order behind the kernel (a kernel of its own with host-side sizing): not capturable";
+    if (d.i16 == kI16ViaScratch) return "int16 audio through the scratch batch: not capturable";
+    if (f32 && d.post_active) return "PLL / LMS channels run behind the kernel through an auxiliary chain: not capturable";
+    if (!f32 && d.anr_active) return "the LMS filter runs behind the kernel: not capturable";
+    if (n_samples % c->osc_len) return "the oscillator's position changes from call to call at this block length: not capturable";
+    return nullptr;
+}
+
+// ---- time segmentation (DESIGN.md "IIR along time") ------------------------------------------
+struct ChainTiles {
+    int tile;
+    long long tiles, warm_tiles;
+    bool can_split, mfw;
+};
+static ChainTiles chain_tiles(const msdr_chain *c, ChainPath path, uint64_t n_samples)
+{
+    ChainTiles t;
+    t.mfw = path_mfw(path);
+    t.tile = t.mfw ? kMwTile : path == kPathFold ? kFoldTile : kChainTile;
+    t.tiles = ((long long)n_samples + t.tile - 1) / t.tile;
+    t.warm_tiles = 0;
+    t.can_split = true;
+    if (c->nstages) {
+        long long w = c->warmup_cfg;
+        if (w == 0) {
+            if (c->pole_radius >= 0.99999) t.can_split = false;        // marginal/unstable: never re-converges
+            else if (c->pole_radius > 0) w = (long long)std::ceil(std::log(t.mfw ? 1e-8 : 1e-10) / std::log(c->pole_radius)) + 64 * c->nstages;
+        }
+        t.warm_tiles = (w + t.tile - 1) / t.tile;
+#if defined(MSDR_MUTATE) && MSDR_MUTATE == 3           /* `make mutants`, never the product: time segments start their cascade from zero state, no re-convergence */
+        t.warm_tiles = 0;
+#endif
+        if (t.warm_tiles > 64 * (t.mfw ? 4 : 1)) t.can_split = false;
+    }
+    return t;
+}
+// segment count for `nch` channels that are launched together
+static long long chain_choose_nseg(const msdr_chain *c, const ChainTiles &t, long long nch)
+{
+    long long ns_ = 1;
+    if (c->time_segments == 1 || !t.can_split || nch <= 0) return 1;
+    if (t.mfw && c->time_segments == 0) {
+        // one unit per wave, all units equally long: the launch takes ceil(units / resident waves) rounds of (segment + warm-up)
+        // tiles.  Pick the segment count that minimises that product (an exact multiple of the resident waves wins).
+        const long long slots = (long long)c->mfw_waves_per_cu * c->ctx->num_cus;
+        const long long max_nseg = std::max<long long>(1, t.tiles / std::max<long long>(4, 8 * t.warm_tiles));
+        const long long kmax = std::min<long long>(max_nseg, std::max<long long>(1, (8 * slots + nch - 1) / nch));
+        double best = 1e300;
+        for (long long k = 1; k <= kmax; k++) {
+            const long long st = (t.tiles + k - 1) / k, ns = (t.tiles + st - 1) / st;
+            const long long rounds = (nch * ns + slots - 1) / slots;
+            const double cost = (double)rounds * (double)(st + (ns > 1 ? t.warm_tiles : 0));
+            if (cost < best * 0.999) { best = cost; ns_ = ns; }
+        }
+    } else {
+        long long min_seg_tiles = std::max<long long>(4, 32 * t.warm_tiles);   // <= ~3 % redone work
+        long long max_nseg = std::max<long long>(1, t.tiles / min_seg_tiles);
+        long long want = c->time_segments > 1 ? c->time_segments : std::max<long long>(1, (2048 + nch - 1) / nch);
+        ns_ = std::max<long long>(1, std::min(want, max_nseg));
+    }
+    const long long st = (t.tiles + ns_ - 1) / ns_;
+    return (t.tiles + st - 1) / st;
+}
+
+// what a call's launches were: msdr_chain_info and msdr_chain_node_kernel are filled from this
+struct ChainLaunch {
+    const char *kname;
+    unsigned grid, block;
+    size_t lds_bytes;
+    long long nseg;
+    int tile;
+    uint32_t flavour;            // MSDR_FLAVOUR_* of the launches, set where each one is made
+    uint32_t env_scan;           // how the folded envelope flavour of chain_mfw_kernel scanned its row states
+    int merged_steps;            // chain_mfw_kernel: k-steps per tile that went into merged steps (the least over the launches), -1 = no such launch
+    const char *node_kname;      // the kernel that runs the biquad nodes of this call ("": no nodes, fp32 chains)
+};
+
+// the wave-stream kernels' table set of a channel: three per tap set (LSB, USB, envelope)
+static int chain_fset_of(const msdr_chain *c, uint32_t ch)
+{
+    const int m = c->h_mode[ch];
+    return c->h_tapset[ch] * 3 + (m == MSDR_MODE_LSB ? 0 : m == MSDR_MODE_USB ? 1 : 2);
+}
+
+// the wave-stream unit table: (channel, segment) per wave; the waves of a workgroup share one tap table, so channels are grouped by
+// table set and every group is padded to whole workgroups.  SSB-table units and envelope-table units are two launches
+// (two kernels), each with the segmentation that fills the GPU with its own channels.
+static int chain_mfw_units(msdr_chain *c, const ChainTiles &t)
+{
+    if (c->units_mode_gen == c->mode_gen && c->units_tiles == t.tiles) return 0;
+    const int nw = c->mfw_nw;
+    std::vector<uint32_t> order(c->channels);
+    for (uint32_t i = 0; i < c->channels; i++) order[i] = i;
+    auto fset_of = [&](uint32_t ch) { return chain_fset_of(c, ch); };
+    auto env_of = [&](uint32_t ch) { return fset_of(ch) % 3 == 2 ? 1 : 0; };
+    auto key_of = [&](uint32_t ch) { return env_of(ch) * 1000000 + fset_of(ch); };      // SSB tables first, envelope tables after
+    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key_of(a) < key_of(b); });
+    long long count[2] = {0, 0};
+    for (uint32_t ch : order) count[env_of(ch)]++;
+    for (int part = 0; part < 2; part++) {
+        c->part_nseg[part] = chain_choose_nseg(c, t, count[part]);
+        c->part_seg_len[part] = ((t.tiles + c->part_nseg[part] - 1) / c->part_nseg[part]) * t.tile;
+    }
+    std::vector<int> units;
+    units.reserve(((size_t)c->channels * std::max(c->part_nseg[0], c->part_nseg[1]) + 3 * MSDR_MAX_TAPSETS * nw) * 2);
+    size_t ssb_units = 0;
+    for (size_t i = 0; i < order.size(); i++) {
+        if (i > 0 && fset_of(order[i]) != fset_of(order[i - 1]))
+            while ((units.size() / 2) % nw) { units.push_back(-1); units.push_back(0); }
+        if (env_of(order[i]) && (i == 0 || !env_of(order[i - 1]))) ssb_units = units.size() / 2;      // first envelope-table unit
+        for (long long sg = 0; sg < c->part_nseg[env_of(order[i])]; sg++) { units.push_back((int)order[i]); units.push_back((int)sg); }
+    }
+    while ((units.size() / 2) % nw) { units.push_back(-1); units.push_back(0); }
+    if (order.empty() || !env_of(order.back())) ssb_units = units.size() / 2;                               // no envelope tables at all
+    if (int rc = grow_device(c->ctx, &c->d_units, &c->units_cap, units.size())) return rc;
+    HIP_TRY(hipMemcpyAsync(c->d_units, units.data(), units.size() * sizeof(int), hipMemcpyHostToDevice, c->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(c->ctx->stream));        // `units` is a local
+    c->units_mode_gen = c->mode_gen; c->units_tiles = t.tiles; c->units_wgs = (uint32_t)(units.size() / 2 / nw);
+    c->units_wgs_ssb = (uint32_t)(ssb_units / nw);
+    return 0;
+}
+
+// chain_q15mf_kernel's channel order: channels grouped by (tap set, flavour) -- a workgroup's waves share one table; one launch per group in use
+static int chain_qm_order(msdr_chain *c)
+{
+    if (c->qm_order_gen == c->mode_gen) return 0;
+    const int env_flavour = (c->sqrt_kind == 1) ? 2 : 1;
+    auto flavour_of = [&](uint32_t ch) { const int m = c->h_mode[ch]; return (m == MSDR_MODE_LSB || m == MSDR_MODE_USB) ? 0 : env_flavour; };
+    std::vector<int> order;
+    c->qm_group_start.assign((size_t)c->tapsets * 3, 0); c->qm_group_count.assign((size_t)c->tapsets * 3, 0);
+    for (uint32_t s = 0; s < c->tapsets; s++)
+        for (int fl = 0; fl < 3; fl++) {
+            const size_t gi = (size_t)s * 3 + fl;
+            c->qm_group_start[gi] = (uint32_t)order.size();
+            for (uint32_t ch = 0; ch < c->channels; ch++)
+                if ((uint32_t)c->h_tapset[ch] == s && flavour_of(ch) == fl) order.push_back((int)ch);
+            c->qm_group_count[gi] = (uint32_t)order.size() - c->qm_group_start[gi];
+        }
+    if (!c->d_qm_order) HIP_TRY(hipMalloc((void **)&c->d_qm_order, (size_t)c->channels * sizeof(int)));
+    HIP_TRY(hipMemcpyAsync(c->d_qm_order, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice, c->ctx->stream));
+    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+    c->qm_order_gen = c->mode_gen;
+    return 0;
+}
+
+// everything the decided path needs from the host before its launches: buffers grown, tables built and uploaded, `p` and the defaults of
+// `r` filled.  A dry run (msdr_chain_graph_create) stops behind this.
+static int chain_prepare(msdr_chain *c, ChainDecision &d, const ChainTiles &t, const int16_t *d_if, void *d_audio, uint64_t n_samples, ChainParams &p, ChainLaunch &r)
+{
     memset(&p, 0, sizeof p);
     p.x = d_if; p.out = d_audio; p.hist_in = c->d_hist[c->cur]; p.hist_out = c->d_hist[c->cur ^ 1];
     p.n = (long long)n_samples; p.channels = (int)c->channels;
@@ -3693,35 +3949,10 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     p.chan_mode = c->d_mode; p.chan_tapset = c->d_tapset; p.mixer = c->mixer; p.osc = c->d_osc; p.osc_len = (int)c->osc_len;
     p.phase0 = (int)c->phase; p.in_scale = c->in_scale; p.sqrt_kind = c->sqrt_kind;
     p.nstages = (int)c->nstages; p.bq = c->d_bq; p.bq_state = c->d_bq_state;
-
-    // ---- kernel choice: the folded kernel needs a short-period oscillator; AM additionally the exact Fs/4 pattern
-    bool use_fold = f32 && c->fold_P > 0;
-    if (use_fold && !c->fold_fs4_exact)
-        if (chain_summary(c).any_env) use_fold = false;
-    bool pll_active = false;
-    if (c->pll) {
-        pll_active = chain_summary(c).any_syncam;
-        if (pll_active) {
-            const size_t need = (size_t)c->channels * n_samples;
-            if (need > c->pll_q_cap) {
-                HIP_TRY(hipStreamSynchronize(c->ctx->stream));
-                hipFree(c->d_pll_q); c->d_pll_q = nullptr; c->pll_q_cap = 0;
-                HIP_TRY(hipMalloc((void **)&c->d_pll_q, need * sizeof(int16_t)));
-                c->pll_q_cap = need;
-            }
-            p.syncam_q = c->d_pll_q;
-        }
+    if (d.pll_active) {
+        if (int rc = grow_device(c->ctx, &c->d_pll_q, &c->pll_q_cap, (size_t)c->channels * n_samples)) return rc;
+        p.syncam_q = c->d_pll_q;
     }
-    // (history samples that arrived under an earlier oscillator table are still in reach, msdr_chain_set_osc: the as-written kernel mixes
-    //  each with the table of its own time; the fast kernels come back once the history has turned over)
-    if (c->force_generic) use_fold = false;
-    const bool use_pcf = f32 && c->pc_active;                    // per-channel taps, fp32: chain_f32pc_kernel in place of every uniform demodulator kernel
-    if (use_pcf) use_fold = false;
-    const bool use_mf = f32 && c->mf_ok && !c->force_generic && !use_pcf;
-    const bool use_mfw = use_mf && c->mfw_nw > 0;
-    const bool use_pc = !f32 && c->pc_active;                    // per-channel taps: chain_q15pc_kernel in place of every uniform demodulator kernel
-    bool use_qm = !f32 && c->d_qm_tab != nullptr && !c->force_generic && !use_pc;
-    p.osc_hist = nullptr;
     if (!c->osc_pending.empty()) {
         OscHistory oh;
         memset(&oh, 0, sizeof oh);
@@ -3734,546 +3965,462 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         HIP_TRY(hipStreamSynchronize(c->ctx->stream));                  // (`oh` is a local; this path runs for one history length after a table change)
         p.osc_hist = c->d_osc_hist;
     }
-    // ---- MSDR_CHAIN_OUT_I16: int16 audio.  The matrix-core kernels convert in their store phase when nothing runs behind them;
-    // otherwise the fp32 audio goes to a scratch block batch and is converted last.
-    void *fout = d_audio;                                        // where the fp32 passes of this call read and write the audio
-    bool i16_via_scratch = false;
-    // ---- msdr_chain_set_block_kernel: the whole block-cadence call of a per-channel chain in one launch (msdr_chain_f32pcb.hiph) -- where no
-    // oscillator generation is pending, nothing runs behind the kernel but a CMSIS-order cascade, and one wave's LDS fits
-    bool use_pcb = false;
-    PcLaunch pcb_geo;
-    memset(&pcb_geo, 0, sizeof pcb_geo);
-    if (use_pcf && c->block_pc && mb_n_ok((long long)n_samples) && !p.osc_hist && !(c->f32_pll || c->aux != nullptr || chain_summary(c).any_anr) &&
-        (!c->seq_bq || c->seq_bq->stages == 0 || c->seq_bq->sequential))
-        use_pcb = chain_f32pcb_lds((int)n_samples, c->pc_np, c->mixer == kMixerFs4 ? 0 : (int)c->osc_len, &pcb_geo);
-    // ---- msdr_chain_set_block_kernel_q15: the same for a Q15 chain in per-channel mode (msdr_chain_q15pcb.hiph) -- where no oscillator generation
-    // is pending, neither the PLL demodulator nor the LMS filter runs between the demodulator and the nodes, and one wave's LDS fits
-    bool use_qpcb = false;
-    if (use_pc && c->block_q15 && mb_n_ok((long long)n_samples) && !p.osc_hist && !pll_active && !(c->anr && (c->d_anr_on || c->anr_all > 0)))
-        use_qpcb = chain_q15pcb_lds((int)n_samples, c->pc_np, c->mixer == kMixerFs4 ? 0 : (int)c->osc_len, nullptr);
-    if (use_pcb) { /* (the kernel converts in its store phase: no scratch batch) */ }
-    else
-    if (f32 && (c->flags & MSDR_CHAIN_OUT_I16)) {
-        const bool post_active = c->f32_pll || c->aux != nullptr || chain_summary(c).any_anr;
-        if (use_mfw && !c->seq_bq && !post_active) p.dbg |= kChainOutI16;
-        else {
-            const size_t need = (size_t)c->channels * n_samples;
-            if (need > c->f32_scratch_floats) {
-                HIP_TRY(hipStreamSynchronize(c->ctx->stream));
-                hipFree(c->d_f32_scratch); c->d_f32_scratch = nullptr; c->f32_scratch_floats = 0;
-                HIP_TRY(hipMalloc((void **)&c->d_f32_scratch, need * sizeof(float)));
-                c->f32_scratch_floats = need;
-            }
-            fout = c->d_f32_scratch; p.out = fout; i16_via_scratch = true;
-        }
-    }
-    if (use_qm)
-        if (!chain_summary(c).qm_sets_ok) use_qm = false;                                  // a tap >= 32640: the VALU kernel runs
-    if (use_mf) use_fold = false;
-    const int kTile = use_mfw ? kMwTile : use_fold ? kFoldTile : kChainTile;
-    // ---- block cadence (msdr_chain_mfb.hiph): one AUDIO_BLOCK (or another short block) per call -- channel-batched tiles, the next
-    // history written by the kernel itself.  Taken where the wave-stream kernel would run its folded flavours (or no cascade at all).
-    bool use_mfb = false;
-    if (use_mfw && !c->block_off && !c->mf_fr && c->nstages <= 2 && mb_n_ok((long long)n_samples) && (int)c->hist_len == c->mf_halo &&
-        (reinterpret_cast<uintptr_t>(d_if) & 15) == 0 && (reinterpret_cast<uintptr_t>(p.out) & 15) == 0 &&
-        mb_lds_bytes(c->mf_halo, (int)n_samples, c->mf_bsteps, 1, 1) <= 160 * 1024 &&
-        (uint64_t)c->channels * std::max<uint64_t>((uint64_t)c->hist_len * 2, n_samples * 4) < (1ull << 32)) {       // (the kernel addresses with 32-bit byte offsets)
-        const bool need_ssb = chain_summary(c).any_ssb, need_env = chain_summary(c).any_env;
-        use_mfb = c->nstages == 0 || ((!need_ssb || c->mfw_ssb_fold) && (!need_env || c->mfw_am_fold));
+    if (d.i16 == kI16InKernel && path_mfw(d.path)) p.dbg |= kChainOutI16;       // (chain_f32pcb_kernel: PcbParams.out_i16)
+    if (d.i16 == kI16ViaScratch) {
+        if (int rc = grow_device(c->ctx, &c->d_f32_scratch, &c->f32_scratch_floats, (size_t)c->channels * n_samples)) return rc;
+        p.out = c->d_f32_scratch;                                    // where the fp32 passes of this call read and write the audio
     }
     p.mf_tab = c->d_mf_tab; p.mf_stride = c->mf_stride; p.mf_halo = c->mf_halo; p.mf_bsteps = c->mf_bsteps; p.mf_xsteps = c->mf_xsteps; p.bq_mf = c->d_bq_mf; p.bq_mf32 = c->d_bq_mf32;
-    // the same for the Q15 chain (msdr_chain_q15mb.hiph); SYNCAM channels under the PLL hand I and Q to a kernel behind: the streaming kernel
-    bool use_qb = false;
-    if (use_qm && chain_summary(c).qm_sets_ok && !c->block_off && !c->qm_fr && !pll_active && mb_n_ok((long long)n_samples) && (int)c->hist_len == c->qm_halo &&
-        (reinterpret_cast<uintptr_t>(d_if) & 15) == 0 && (reinterpret_cast<uintptr_t>(d_audio) & 15) == 0 &&
-        qb_lds_bytes(c->qm_halo, (int)n_samples, c->qm_bsteps, 1, 1) <= 160 * 1024 &&
-        (uint64_t)c->channels * std::max<uint64_t>((uint64_t)c->hist_len * 2, n_samples * 2) < (1ull << 32)) use_qb = true;
-    const int osc_P = use_mf ? c->mf_P : c->fold_P;            // the matrix-core tables exist for periods up to 32, the VALU fold tables up to 4
+    const int osc_P = d.mf ? c->mf_P : c->fold_P;              // the matrix-core tables exist for periods up to 32, the VALU fold tables up to 4
     p.ftaps = c->d_ftaps; p.chan_fset = c->d_fset; p.fold_period = osc_P; p.bq_fold = c->d_bq_fold;
     p.fold_rot = osc_P ? (int)(c->phase % osc_P) : 0;
 
-    // ---- time segmentation (DESIGN.md "IIR along time") ------------------------------------------
-    const long long tiles = ((long long)n_samples + kTile - 1) / kTile;
-    long long warm_tiles = 0;
-    bool can_split = true;
-    if (c->nstages) {
-        long long w = c->warmup_cfg;
-        if (w == 0) {
-            if (c->pole_radius >= 0.99999) can_split = false;        // marginal/unstable: never re-converges
-            else if (c->pole_radius > 0) w = (long long)std::ceil(std::log(use_mfw ? 1e-8 : 1e-10) / std::log(c->pole_radius)) + 64 * c->nstages;
-        }
-        warm_tiles = (w + kTile - 1) / kTile;
-#if defined(MSDR_MUTATE) && MSDR_MUTATE == 3           /* `make mutants`, never the product: time segments start their cascade from zero state, no re-convergence */
-        warm_tiles = 0;
-#endif
-        if (warm_tiles > 64 * (use_mfw ? 4 : 1)) can_split = false;
-    }
-    // segment count for `nch` channels that are launched together
-    auto choose_nseg = [&](long long nch) -> long long {
-        long long ns_ = 1;
-        if (c->time_segments == 1 || !can_split || nch <= 0) return 1;
-        if (use_mfw && c->time_segments == 0) {
-            // one unit per wave, all units equally long: the launch takes ceil(units / resident waves) rounds of (segment + warm-up)
-            // tiles.  Pick the segment count that minimises that product (an exact multiple of the resident waves wins).
-            const long long slots = (long long)c->mfw_waves_per_cu * c->ctx->num_cus;
-            const long long max_nseg = std::max<long long>(1, tiles / std::max<long long>(4, 8 * warm_tiles));
-            const long long kmax = std::min<long long>(max_nseg, std::max<long long>(1, (8 * slots + nch - 1) / nch));
-            double best = 1e300;
-            for (long long k = 1; k <= kmax; k++) {
-                const long long st = (tiles + k - 1) / k, ns = (tiles + st - 1) / st;
-                const long long rounds = (nch * ns + slots - 1) / slots;
-                const double cost = (double)rounds * (double)(st + (ns > 1 ? warm_tiles : 0));
-                if (cost < best * 0.999) { best = cost; ns_ = ns; }
-            }
-        } else {
-            long long min_seg_tiles = std::max<long long>(4, 32 * warm_tiles);   // <= ~3 % redone work
-            long long max_nseg = std::max<long long>(1, tiles / min_seg_tiles);
-            long long want = c->time_segments > 1 ? c->time_segments : std::max<long long>(1, (2048 + nch - 1) / nch);
-            ns_ = std::max<long long>(1, std::min(want, max_nseg));
-        }
-        const long long st = (tiles + ns_ - 1) / ns_;
-        return (tiles + st - 1) / st;
-    };
-    long long nseg = choose_nseg(c->channels);
-    long long seg_tiles = (tiles + nseg - 1) / nseg;
-    p.nseg = (int)nseg; p.seg_len = seg_tiles * kTile; p.warm = (int)(nseg > 1 ? warm_tiles * kTile : 0);
+    r.nseg = chain_choose_nseg(c, t, c->channels);
+    const long long seg_tiles = (t.tiles + r.nseg - 1) / r.nseg;
+    p.nseg = (int)r.nseg; p.seg_len = seg_tiles * t.tile; p.warm = (int)(r.nseg > 1 ? t.warm_tiles * t.tile : 0);
+    r.kname = ""; r.node_kname = "";
+    r.grid = (unsigned)(c->channels * r.nseg); r.block = kThreads; r.tile = t.tile;
+    r.lds_bytes = t.mfw ? mw_lds_bytes(c->mf_halo, c->mf_bsteps + c->mf_xsteps, c->mfw_nw, c->mf_fr) : d.path == kPathFold ? fold_lds_bytes(p.ntaps_pad) : chain_lds_bytes(p.ntaps_pad);
+    r.flavour = 0; r.env_scan = 0; r.merged_steps = -1;
 
-    unsigned grid = (unsigned)(c->channels * nseg);
-    if (use_mfb) {
-        auto fset_of = [&](uint32_t ch) { const int m = c->h_mode[ch]; return c->h_tapset[ch] * 3 + (m == MSDR_MODE_LSB ? 0 : m == MSDR_MODE_USB ? 1 : 2); };
-        if (int rc = chain_block_tiles(c, (int)n_samples, [&](uint32_t ch) { return fset_of(ch) % 3 == 2 ? 1 : 0; }, fset_of,
+    switch (d.path) {
+    case kPathMfb:
+        if (int rc = chain_block_tiles(c, (int)n_samples, [&](uint32_t ch) { return chain_fset_of(c, ch) % 3 == 2 ? 1 : 0; }, [&](uint32_t ch) { return chain_fset_of(c, ch); },
                                        [&](int w, int tpw) { return mb_lds_bytes(c->mf_halo, (int)n_samples, c->mf_bsteps, w, tpw); })) return rc;
-        nseg = 1; p.nseg = 1; p.warm = 0;
+        r.nseg = 1; p.nseg = 1; p.warm = 0;
         p.bq_state_out = c->d_bq_state_alt; p.mw_iir = c->d_mw_iir;
-    } else if (use_qb) {
+        break;
+    case kPathQ15Mb:
         if (int rc = chain_block_tiles(c, (int)n_samples, [&](uint32_t ch) { const int m = c->h_mode[ch]; return (m == MSDR_MODE_LSB || m == MSDR_MODE_USB) ? 0 : 1; },
                                        [&](uint32_t ch) { return c->h_tapset[ch]; },
                                        [&](int w, int tpw) { return qb_lds_bytes(c->qm_halo, (int)n_samples, c->qm_bsteps, w, tpw); },
-                                       (c->nnodes == 2 && c->nodes[0]->max_stage == 0 && c->nodes[1]->max_stage == 0 && n_samples == 128 && !c->no_fuse &&
-                                        !chain_nodes_per_channel(c)) ? 3 : 0)) return rc;
-        nseg = 1; p.nseg = 1; p.warm = 0;
-    } else
-    if (use_mfw) {
-        // unit table: (channel, segment) per wave; the waves of a workgroup share one tap table, so channels are grouped by
-        // table set and every group is padded to whole workgroups.  SSB-table units and envelope-table units are two launches
-        // (two kernels), each with the segmentation that fills the GPU with its own channels.
-        const int nw = c->mfw_nw;
-        if (c->units_mode_gen != c->mode_gen || c->units_tiles != tiles) {
-            std::vector<uint32_t> order(c->channels);
-            for (uint32_t i = 0; i < c->channels; i++) order[i] = i;
-            auto fset_of = [&](uint32_t ch) { const int m = c->h_mode[ch]; return c->h_tapset[ch] * 3 + (m == MSDR_MODE_LSB ? 0 : m == MSDR_MODE_USB ? 1 : 2); };
-            auto env_of = [&](uint32_t ch) { return fset_of(ch) % 3 == 2 ? 1 : 0; };
-            auto key_of = [&](uint32_t ch) { return env_of(ch) * 1000000 + fset_of(ch); };      // SSB tables first, envelope tables after
-            std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key_of(a) < key_of(b); });
-            long long count[2] = {0, 0};
-            for (uint32_t ch : order) count[env_of(ch)]++;
-            for (int part = 0; part < 2; part++) {
-                c->part_nseg[part] = choose_nseg(count[part]);
-                c->part_seg_len[part] = ((tiles + c->part_nseg[part] - 1) / c->part_nseg[part]) * kTile;
-            }
-            std::vector<int> units;
-            units.reserve(((size_t)c->channels * std::max(c->part_nseg[0], c->part_nseg[1]) + 3 * MSDR_MAX_TAPSETS * nw) * 2);
-            size_t ssb_units = 0;
-            for (size_t i = 0; i < order.size(); i++) {
-                if (i > 0 && fset_of(order[i]) != fset_of(order[i - 1]))
-                    while ((units.size() / 2) % nw) { units.push_back(-1); units.push_back(0); }
-                if (env_of(order[i]) && (i == 0 || !env_of(order[i - 1]))) ssb_units = units.size() / 2;      // first envelope-table unit
-                for (long long sg = 0; sg < c->part_nseg[env_of(order[i])]; sg++) { units.push_back((int)order[i]); units.push_back((int)sg); }
-            }
-            while ((units.size() / 2) % nw) { units.push_back(-1); units.push_back(0); }
-            if (order.empty() || !env_of(order.back())) ssb_units = units.size() / 2;                               // no envelope tables at all
-            if (units.size() > c->units_cap) {
-                HIP_TRY(hipStreamSynchronize(c->ctx->stream));
-                hipFree(c->d_units); c->d_units = nullptr; c->units_cap = 0;
-                if (int rc = dzalloc(c->ctx, units.size(), &c->d_units)) return rc;
-                c->units_cap = units.size();
-            }
-            HIP_TRY(hipMemcpyAsync(c->d_units, units.data(), units.size() * sizeof(int), hipMemcpyHostToDevice, c->ctx->stream));
-            HIP_TRY(hipStreamSynchronize(c->ctx->stream));        // `units` is a local
-            c->units_mode_gen = c->mode_gen; c->units_tiles = tiles; c->units_wgs = (uint32_t)(units.size() / 2 / nw);
-            c->units_wgs_ssb = (uint32_t)(ssb_units / nw);
+                                       chain_nodes_fusable(c, n_samples) ? 3 : 0)) return rc;
+        r.nseg = 1; p.nseg = 1; p.warm = 0;
+        // the nodes fuse where every launch of this call has one tile per wave on three or more waves (small batches: up to 16 384 channels
+        // of one flavour on this part)
+        for (int part = 0; part < 2 && d.nodes_fused; part++) {
+            const msdr_chain::BlockPart &bp = c->bpart[part];
+            if (bp.wgs && (bp.tpw != 1 || bp.nw < 3 || qb_nodes_lds_bytes(c->qm_halo, 128, c->qm_bsteps, (int)bp.nw) > 160 * 1024)) d.nodes_fused = false;
         }
-        nseg = (c->units_wgs_ssb > 0) ? c->part_nseg[0] : c->part_nseg[1];            // reported by msdr_chain_get_info
-        p.warm = (int)(nseg > 1 ? warm_tiles * kTile : 0);
-        grid = c->units_wgs;
-        p.mf_units = c->d_units; p.mf_nw = nw; p.bq_state_out = c->d_bq_state_alt; p.mw_iir = c->d_mw_iir;
+        break;
+    case kPathMfw:
+        if (int rc = chain_mfw_units(c, t)) return rc;
+        r.nseg = (c->units_wgs_ssb > 0) ? c->part_nseg[0] : c->part_nseg[1];            // reported by msdr_chain_get_info
+        p.warm = (int)(r.nseg > 1 ? t.warm_tiles * t.tile : 0);
+        r.grid = c->units_wgs;
+        p.mf_units = c->d_units; p.mf_nw = c->mfw_nw; p.bq_state_out = c->d_bq_state_alt; p.mw_iir = c->d_mw_iir;
 #ifdef MSDR_STAMPS
-        { const char *e = getenv("MSDR_DBG"); p.dbg = (p.dbg & kChainOutI16) | (e ? (atoi(e) & ~kChainOutI16) : 0); }
-        static unsigned long long *stamp_buf = nullptr;
-        const size_t stamp_n = (size_t)grid * nw * 8;
-        if (!stamp_buf) HIP_TRY(hipMalloc(&stamp_buf, (1u << 20) * 8 * sizeof(unsigned long long)));
-        HIP_TRY(hipMemsetAsync(stamp_buf, 0, stamp_n * 8, c->ctx->stream));
-        p.dbg_buf = stamp_buf;
+        {
+            { const char *e = getenv("MSDR_DBG"); p.dbg = (p.dbg & kChainOutI16) | (e ? (atoi(e) & ~kChainOutI16) : 0); }
+            static unsigned long long *stamp_buf = nullptr;
+            const size_t stamp_n = (size_t)r.grid * c->mfw_nw * 8;
+            if (!stamp_buf) HIP_TRY(hipMalloc(&stamp_buf, (1u << 20) * 8 * sizeof(unsigned long long)));
+            HIP_TRY(hipMemsetAsync(stamp_buf, 0, stamp_n * 8, c->ctx->stream));
+            p.dbg_buf = stamp_buf;
+        }
 #endif
+        break;
+    case kPathQ15Mf:
+        if (int rc = chain_qm_order(c)) return rc;
+        break;
+    default: break;
+    }
+    return 0;
+}
+
+// the fields the four per-channel parameter blocks share (the kernels' translation units own the structs)
+template <typename Q>
+static void pc_params(Q &q, const msdr_chain *c, const ChainParams &p)
+{
+    memset(&q, 0, sizeof q);
+    q.x = p.x; q.hist_in = p.hist_in; q.n = (decltype(q.n))p.n; q.channels = p.channels; q.hist_len = p.hist_len; q.np = c->pc_np; q.chan_mode = c->d_mode;
+    q.osc = c->opc_active ? c->d_osc_bank : (const void *)c->d_osc;        // per-channel oscillator tables: the bank in place of the shared table
+    q.osc_len = p.osc_len; q.phase0 = p.phase0; q.in_row = c->n_inputs ? c->d_in_row : nullptr;
+}
+static void pc_geometry_of(const PcLaunch &geo, ChainLaunch &r)
+{
+    r.grid = geo.grid; r.block = geo.block; r.lds_bytes = geo.lds_bytes; r.nseg = geo.nseg; r.tile = geo.tile;
+}
+
+// ---- one function per path: its launches, and what they were ------------------------------------------------------------------------------------
+static int chain_launch_f32pcb(msdr_chain *c, const ChainDecision &, const ChainParams &p, ChainLaunch &r)
+{
+    PcbParams q;
+    pc_params(q, c, p);
+    q.out = p.out; q.hist_out = p.hist_out; q.taps = c->d_pcf_taps; q.osc_stride = c->opc_active ? (int)c->osc_len : 0;
+    q.in_scale = c->in_scale; q.out_i16 = (c->flags & MSDR_CHAIN_OUT_I16) ? 1 : 0;
+    if (c->seq_bq && c->seq_bq->stages > 0) {          // the cascade's own table and state: direct calls of the stage, unfused calls and these share them
+        q.stages = (int)c->seq_bq->stages; q.bq_state = c->seq_bq->d_state;
+        q.bq_tab = c->seq_bq->per_channel ? c->seq_bq->d_pc_coeffs : c->seq_bq->d_coeffs; q.bq_stride = c->seq_bq->per_channel ? kSbqTabFloats : 0;
+        r.flavour |= MSDR_FLAVOUR_SEQ_CASCADE | (c->seq_bq->per_channel ? (uint32_t)MSDR_FLAVOUR_CASCADE_PC : 0u);
+    }
+    PcLaunch geo;
+    if (launch_chain_f32pcb(c->ctx->stream, c->mixer == kMixerFs4, q, &geo) != hipSuccess)
+        return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pcb_kernel launch failed");
+    r.kname = c->opc_active ? kPcboKernelName : kPcbKernelName;
+    pc_geometry_of(geo, r); r.nseg = 1;
+    r.flavour |= MSDR_FLAVOUR_BLOCK | MSDR_FLAVOUR_TAPS_PC | (c->opc_active ? (uint32_t)MSDR_FLAVOUR_OSC_PC : 0u) | (c->n_inputs ? (uint32_t)MSDR_FLAVOUR_SHARED_IF : 0u);
+    return 0;
+}
+
+static int chain_launch_f32pc(msdr_chain *c, const ChainDecision &, const ChainParams &p, ChainLaunch &r)
+{
+    PcfParams q;
+    pc_params(q, c, p);
+    q.out = (float *)p.out; q.taps = c->d_pcf_taps; q.mixer = c->mixer; q.in_scale = c->in_scale; q.osc_hist = p.osc_hist;
+    PcLaunch geo;
+    if (c->opc_active) {
+        if (launch_chain_f32pco(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, q, &geo) != hipSuccess)
+            return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pco_kernel launch failed");
+        r.kname = kPcfoKernelName; r.flavour |= MSDR_FLAVOUR_OSC_PC;
+    } else {
+        if (launch_chain_f32pc(c->ctx->stream, false, c->ctx->num_cus, (int)c->time_segments, q, &geo) != hipSuccess)
+            return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pc_kernel launch failed");
+        r.kname = kPcfKernelName;
+    }
+    pc_geometry_of(geo, r);
+    r.flavour |= MSDR_FLAVOUR_TAPS_PC | (geo.nseg > 1 ? MSDR_FLAVOUR_SEGMENTED : 0u) | (c->n_inputs ? (uint32_t)MSDR_FLAVOUR_SHARED_IF : 0u);
+    return 0;
+}
+
+static int chain_launch_mfb(msdr_chain *c, const ChainDecision &, const ChainParams &p, ChainLaunch &r)
+{
+    static const char *const names[3] = {"chain_mfb_kernel<0> (channel-batched block tiles)", "chain_mfb_kernel<1> (channel-batched block tiles)",
+                                         "chain_mfb_kernel<2> (channel-batched block tiles)"};
+    r.grid = 0;
+    for (int part = 0; part < 2; part++) {
+        const msdr_chain::BlockPart &bp = c->bpart[part];
+        if (bp.wgs == 0) continue;
+        ChainParams q = p;
+        q.mf_units = c->d_btiles + bp.offset; q.mf_nw = (int)bp.nw; q.nseg = (int)bp.tpw;
+        r.lds_bytes = mb_lds_bytes(c->mf_halo, (int)p.n, c->mf_bsteps, (int)bp.nw, (int)bp.tpw);
+        if (launch_chain_mfb(c->ctx->stream, (int)c->nstages, part == 1, bp.wgs, bp.nw * 64, r.lds_bytes, q) != hipSuccess)
+            return fail(MSDR_STATUS_HIP_ERROR, "chain_mfb_kernel launch failed");
+        r.grid += bp.wgs; r.block = bp.nw * 64;
+        r.flavour |= MSDR_FLAVOUR_BLOCK | (part == 0 ? MSDR_FLAVOUR_SSB_UNITS : MSDR_FLAVOUR_ENV_UNITS);
+        if (c->nstages > 0) r.flavour |= (part == 0 ? MSDR_FLAVOUR_SSB_FOLD : MSDR_FLAVOUR_ENV_FOLD);      // (the block kernel runs a cascade folded or not at all)
+    }
+    r.kname = names[c->nstages];
+    if (c->nstages > 0) std::swap(c->d_bq_state, c->d_bq_state_alt);      // the kernel read bq_state and wrote bq_state_out
+    return 0;
+}
+
+static int chain_launch_mfw(msdr_chain *c, const ChainDecision &, const ChainTiles &t, const ChainParams &p, ChainLaunch &r)
+{
+    r.block = (unsigned)c->mfw_nw * 64;
+    // SSB-table units and envelope-table units are separate launches of separate kernels (register allocation per flavour)
+    for (int part = 0; part < 2; part++) {
+        const unsigned g = part == 0 ? c->units_wgs_ssb : c->units_wgs - c->units_wgs_ssb;
+        if (g == 0) continue;
+        ChainParams q = p;
+        q.mf_units = c->d_units + (size_t)(part == 0 ? 0 : c->units_wgs_ssb) * c->mfw_nw * 2;
+        q.nseg = (int)c->part_nseg[part]; q.seg_len = c->part_seg_len[part]; q.warm = (int)(c->part_nseg[part] > 1 ? t.warm_tiles * t.tile : 0);
+        const bool fold = part == 0 ? c->mfw_ssb_fold : c->mfw_am_fold;
+        const int rowlocal = (part == 1 && fold && !c->mf_fr && !c->d_at_tab) ? c->mfw_am_rowlocal : 0;
+        if (part == 1 && fold && !c->d_at_tab) r.env_scan = 1u + (uint32_t)rowlocal;
+        r.flavour |= part == 0 ? MSDR_FLAVOUR_SSB_UNITS : MSDR_FLAVOUR_ENV_UNITS;
+        if (c->part_nseg[part] > 1) r.flavour |= MSDR_FLAVOUR_SEGMENTED;
+        if (part == 1 && c->d_at_tab) {
+            // envelope units on the taps-in-registers kernel: the same unit table read with this kernel's own workgroup size
+            ChainParams a = q;
+            const long long entries = (long long)g * c->mfw_nw;
+            a.mf_tab = c->d_at_tab; a.mf_stride = c->at_stride; a.mf_nw = c->at_nw; a.fold_rot = (int)entries;
+            const unsigned ag = (unsigned)((entries + c->at_nw - 1) / c->at_nw);
+            const size_t alds = at_lds_bytes(c->at_ns, c->at_nw);
+            (void)launch_chain_amtr(c->ctx->stream, c->at_ns, (int)c->nstages, ag, (unsigned)c->at_nw * 64, alds, a);
+            if (int rc2 = launch_check("chain_amtr_kernel")) return rc2;
+            r.flavour |= MSDR_FLAVOUR_AMTR;
+            continue;
+        }
+        (void)launch_chain_mfw(c->ctx->stream, (int)c->nstages, part == 1, fold, c->mf_fr, rowlocal, g, r.block, r.lds_bytes, q);
+        const int part_merged = mw_merges_steps((int)c->nstages, part == 1, fold, c->mf_fr, rowlocal) ? c->mf_merged[part] : 0;
+        r.merged_steps = r.merged_steps < 0 ? part_merged : std::min(r.merged_steps, part_merged);
+        if (int rc = launch_check("chain_mfw_kernel")) return rc;
+        if (fold) r.flavour |= part == 0 ? MSDR_FLAVOUR_SSB_FOLD : MSDR_FLAVOUR_ENV_FOLD;
+        if (c->mf_fr) r.flavour |= MSDR_FLAVOUR_FULL_RATE | (c->mf_compact ? MSDR_FLAVOUR_COMPACT : 0u) | ((part == 1 && c->mf_share_iq) ? MSDR_FLAVOUR_SHARED_IQ : 0u);
+    }
+    static const char *const names[5] = {"chain_mfw_kernel<0>", "chain_mfw_kernel<1>", "chain_mfw_kernel<2>", "chain_mfw_kernel<3>", "chain_mfw_kernel<4>"};
+    static const char *const names_fr[5] = {"chain_mfw_kernel<0> full-rate NCO streams", "chain_mfw_kernel<1> full-rate NCO streams", "chain_mfw_kernel<2> full-rate NCO streams",
+                                            "chain_mfw_kernel<3> full-rate NCO streams", "chain_mfw_kernel<4> full-rate NCO streams"};
+    r.kname = c->mf_fr ? names_fr[c->nstages] : names[c->nstages];
+    if (c->d_at_tab && c->units_wgs > c->units_wgs_ssb) r.kname = c->units_wgs_ssb ? "chain_mfw_kernel + chain_amtr_kernel" : "chain_amtr_kernel";
+    std::swap(c->d_bq_state, c->d_bq_state_alt);          // the kernel read bq_state and wrote bq_state_out
+#ifdef MSDR_STAMPS
+    if (getenv("MSDR_STAMP_PRINT")) {
+        HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+        std::vector<unsigned long long> h((size_t)r.grid * c->mfw_nw * 8);
+        HIP_TRY(hipMemcpy(h.data(), p.dbg_buf, h.size() * 8, hipMemcpyDeviceToHost));
+        double sum[8] = {0}; size_t cnt = 0;
+        for (size_t u = 0; u < h.size() / 8; u++) { if (!h[u * 8 + 0] && !h[u * 8 + 1]) continue; cnt++; for (int k = 0; k < 8; k++) sum[k] += (double)h[u * 8 + k]; }
+        const double tl = (double)((p.n + kMwTile - 1) / kMwTile) * c->channels / std::max<size_t>(cnt, 1);
+        fprintf(stderr, "stamps (cycles per tile per wave, %zu units, %.1f tiles each): prefetch-issue %.0f | mfma %.0f | demod+swap %.0f | iir %.0f | store %.0f | halo %.0f | vmwait %.0f | stage %.0f\n",
+                cnt, tl, sum[0] / cnt / tl, sum[1] / cnt / tl, sum[2] / cnt / tl, sum[3] / cnt / tl, sum[4] / cnt / tl, sum[5] / cnt / tl, sum[6] / cnt / tl, sum[7] / cnt / tl);
+    }
+#endif
+    return 0;
+}
+
+static int chain_launch_fold(msdr_chain *c, const ChainDecision &, const ChainParams &p, ChainLaunch &r)
+{
+    (void)launch_chain_fold(c->ctx->stream, c->fold_P, r.grid, r.lds_bytes, p);
+    r.flavour |= MSDR_FLAVOUR_VALU_FOLD | ((uint32_t)c->fold_P << MSDR_FLAVOUR_FOLD_PERIOD_SHIFT) | (r.nseg > 1 ? MSDR_FLAVOUR_SEGMENTED : 0u);
+    r.kname = c->fold_P == 4 ? "chain_fold_kernel<4>" : c->fold_P == 2 ? "chain_fold_kernel<2>" : "chain_fold_kernel<1>";
+    return 0;
+}
+
+static int chain_launch_generic(msdr_chain *c, const ChainDecision &d, const ChainParams &p, ChainLaunch &r)
+{
+    const bool q15 = d.path == kPathQ15Generic;
+    (void)launch_chain_generic(c->ctx->stream, q15, r.grid, r.lds_bytes, p);
+    if (r.nseg > 1) r.flavour |= MSDR_FLAVOUR_SEGMENTED;
+    r.kname = q15 ? "chain_kernel<ArithQ15>" : "chain_kernel<ArithF32>";
+    return 0;
+}
+
+static int chain_launch_q15mb(msdr_chain *c, const ChainDecision &d, const ChainParams &p, ChainLaunch &r)
+{
+    r.grid = 0;
+    for (int part = 0; part < 2; part++) {
+        const msdr_chain::BlockPart &bp = c->bpart[part];
+        if (bp.wgs == 0) continue;
+        ChainParams q = p;
+        q.mf_tab = c->d_qm_tab; q.mf_stride = c->qm_stride; q.mf_halo = c->qm_halo; q.mf_bsteps = c->qm_bsteps;
+        q.mf_units = c->d_btiles + bp.offset; q.mf_nw = (int)bp.nw; q.nseg = (int)bp.tpw;
+        r.lds_bytes = d.nodes_fused ? qb_nodes_lds_bytes(c->qm_halo, 128, c->qm_bsteps, (int)bp.nw) : qb_lds_bytes(c->qm_halo, (int)p.n, c->qm_bsteps, (int)bp.nw, (int)bp.tpw);
+        if (d.nodes_fused) { q.bq_state = reinterpret_cast<float *>(c->nodes[0]->d_defs); q.bq_state_out = reinterpret_cast<float *>(c->nodes[1]->d_defs); }
+        const int flavour = part == 0 ? 0 : (c->sqrt_kind == 1 ? 2 : 1);
+        if (launch_chain_q15mb(c->ctx->stream, flavour, d.nodes_fused, bp.wgs, bp.nw * 64, r.lds_bytes, q) != hipSuccess)
+            return fail(MSDR_STATUS_HIP_ERROR, "chain_q15mb_kernel launch failed");
+        r.grid += bp.wgs; r.block = bp.nw * 64;
+    }
+    r.kname = d.nodes_fused ? "chain_q15mb_kernel (block tiles) + both biquad nodes" : "chain_q15mb_kernel (channel-batched block tiles)";
+    if (d.nodes_fused) r.node_kname = "chain_q15mb_kernel";
+    return 0;
+}
+
+static int chain_launch_q15mf(msdr_chain *c, const ChainDecision &, const ChainParams &p, ChainLaunch &r)
+{
+    const long long qtiles = (p.n + kQmTile - 1) / kQmTile;
+    ChainParams q = p;
+    q.mf_tab = c->d_qm_tab; q.mf_stride = c->qm_stride; q.mf_halo = c->qm_halo; q.mf_bsteps = c->qm_bsteps; q.warm = 0; q.mf_units = c->d_qm_order;
+    int nw = 8;
+    long long qseg = 1;
+    for (size_t gi = 0; gi < c->qm_group_count.size(); gi++) {
+        const long long cnt = c->qm_group_count[gi];
+        if (!cnt) continue;
+        // every launch fills the GPU on its own: aim at two rounds of 16 waves per CU, at least two tiles per segment
+        qseg = (8192 + cnt - 1) / cnt;
+        qseg = std::max<long long>(1, std::min<long long>(qseg, std::max<long long>(1, qtiles / 2)));
+        if (c->time_segments > 0) qseg = std::max<long long>(1, std::min<long long>(c->time_segments, qtiles));
+        const long long qseg_len = ((qtiles + qseg - 1) / qseg) * kQmTile;
+        qseg = (p.n + qseg_len - 1) / qseg_len;
+        nw = 8;
+        while (nw > 1 && cnt * qseg < 256LL * nw) nw >>= 1;
+        while (nw > 1 && qm_lds_bytes(c->qm_halo, c->qm_bsteps, nw, c->qm_fr) > 80 * 1024) nw >>= 1;     // two workgroups per CU
+        const size_t qlds = qm_lds_bytes(c->qm_halo, c->qm_bsteps, nw, c->qm_fr);
+        q.mf_nw = nw; q.nseg = (int)qseg; q.seg_len = qseg_len;
+        q.fold_period = (int)c->qm_group_start[gi]; q.fold_rot = (int)cnt; q.mf_waves = (int)(gi / 3);
+        r.grid = (unsigned)((cnt * qseg + nw - 1) / nw);
+        (void)launch_chain_q15mf(c->ctx->stream, (int)(gi % 3), c->qm_fr, r.grid, (unsigned)nw * 64, qlds, q);
+        if (int rc = launch_check("chain_q15mf_kernel")) return rc;
+    }
+    r.kname = c->qm_fr ? "chain_q15mf_kernel full-rate NCO streams" : "chain_q15mf_kernel"; r.block = (unsigned)nw * 64; r.nseg = qseg;
+    return 0;
+}
+
+static int chain_launch_q15pcb(msdr_chain *c, const ChainDecision &, const ChainParams &p, ChainLaunch &r)
+{
+    QpcbParams q;
+    pc_params(q, c, p);
+    q.out = (short *)p.out; q.hist_out = p.hist_out; q.taps = c->d_pc_taps; q.osc_stride = c->opc_active ? (int)c->osc_len : 0; q.sqrt_kind = c->sqrt_kind;
+    q.nnodes = (int)c->nnodes; q.defs0 = c->nnodes > 0 ? c->nodes[0]->d_defs : nullptr; q.defs1 = c->nnodes > 1 ? c->nodes[1]->d_defs : nullptr;
+    PcLaunch geo;
+    if (launch_chain_q15pcb(c->ctx->stream, c->mixer == kMixerFs4, q, &geo) != hipSuccess)
+        return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pcb_kernel launch failed");
+    r.kname = c->opc_active ? kQpcboKernelName : kQpcbKernelName;
+    if (c->nnodes) r.node_kname = "chain_q15pcb_kernel";         // (the kernel runs the nodes as its third phase, on the same records)
+    pc_geometry_of(geo, r); r.nseg = 1;
+    return 0;
+}
+
+static int chain_launch_q15pc(msdr_chain *c, const ChainDecision &, const ChainParams &p, ChainLaunch &r)
+{
+    PcParams q;
+    pc_params(q, c, p);
+    q.out = (short *)p.out; q.taps = c->d_pc_taps; q.mixer = c->mixer; q.sqrt_kind = c->sqrt_kind; q.syncam_q = p.syncam_q; q.osc_hist = p.osc_hist;
+    PcLaunch geo;
+    if (c->opc_active) {
+        if (launch_chain_q15pco(c->ctx->stream, c->ctx->num_cus, q, &geo) != hipSuccess)
+            return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pco_kernel launch failed");
+        r.kname = "chain_q15pco_kernel (per-channel taps and oscillator tables)";
+    } else {
+        if (launch_chain_q15pc(c->ctx->stream, false, c->ctx->num_cus, q, &geo) != hipSuccess)
+            return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pc_kernel launch failed");
+        r.kname = "chain_q15pc_kernel (per-channel taps)";
+    }
+    pc_geometry_of(geo, r);
+    return 0;
+}
+
+// biquad1_dac -> biquad2_dac in one pass over the audio
+static int chain_two_nodes(msdr_chain *c, void *d_audio, uint64_t n_samples, const char **name)
+{
+    const char *node_kname = "";
+    const bool slabs = (c->channels & 63u) == 0 && (n_samples & 127u) == 0 && (reinterpret_cast<uintptr_t>(d_audio) & 15) == 0;
+    const int per_group = c->nodes[0]->pipe_ch;
+    // one 128-sample block, the reference's cadence, one stage per node: the pipeline over sub-slabs inside the block (biquad_teensy_blk_kernel),
+    // ANY channel count -- the reference's own single receiver included (1 channel: 27 -> 12 us per tick; its rows past the end idle) --
+    // while its 16-channel workgroups find a CU each (4096 channels: 15.1 -> 13.2 us per tick; at 8192 the slab kernel is ahead again,
+    // 16.6 vs 17.3, tools/r05_nodes_x.sh); MSDR_BIQUAD_BLK=0 / 1 at create time overrides
+    const uint32_t blk_wgs = (c->channels + kTqbCh - 1) / kTqbCh;
+    if (chain_nodes_per_channel(c)) {      // every channel its own records: one lane = one channel with its own coefficients, any shape
+        node_kname = "biquad_teensy_pc_kernel<2>";
+        if (launch_biquad_teensy_pc(c->ctx->stream, 2, (short *)d_audio, c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels, (long long)n_samples) != hipSuccess)
+            return fail(MSDR_STATUS_HIP_ERROR, "biquad_teensy_pc_kernel<2> launch failed");
+    } else
+    if (n_samples == 128 && (reinterpret_cast<uintptr_t>(d_audio) & 15) == 0 && c->nodes[0]->max_stage == 0 && c->nodes[1]->max_stage == 0 &&
+        (c->blk_force >= 1 || (c->blk_force < 0 && blk_wgs <= (uint32_t)c->ctx->num_cus))) {
+        node_kname = "biquad_teensy_blk_kernel";
+        hipLaunchKernelGGL(biquad_teensy_blk_kernel, dim3(blk_wgs), dim3(kTqbThreads), tqb_lds_bytes(), c->ctx->stream, (short *)d_audio,
+                           c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels);
+    } else
+    if ((n_samples & 127u) == 0 && (reinterpret_cast<uintptr_t>(d_audio) & 15) == 0 && c->channels % (unsigned)per_group == 0 &&
+        c->nodes[0]->max_stage == 0 && c->nodes[1]->max_stage == 0) {
+        // one stage per node (the reference's configuration): the recursions alone on two waves, the input products element-wise on the others
+        if (per_group == 64) {
+            node_kname = "biquad_teensy_pipe4_kernel<2,64>";
+            hipLaunchKernelGGL((biquad_teensy_pipe4_kernel<2, 64>), dim3(c->channels / 64), dim3(tq4_threads(64)), tq4_lds_bytes(64), c->ctx->stream, (short *)d_audio,
+                               c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels, (long long)n_samples);
+        } else if (per_group == 32) {
+            node_kname = "biquad_teensy_pipe4_kernel<2,32>";
+            hipLaunchKernelGGL((biquad_teensy_pipe4_kernel<2, 32>), dim3(c->channels / 32), dim3(tq4_threads(32)), tq4_lds_bytes(32), c->ctx->stream, (short *)d_audio,
+                               c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels, (long long)n_samples);
+        } else {
+            node_kname = "biquad_teensy_pipe4_kernel<2,16>";
+            hipLaunchKernelGGL((biquad_teensy_pipe4_kernel<2, 16>), dim3(c->channels / 16), dim3(tq4_threads(16)), tq4_lds_bytes(16), c->ctx->stream, (short *)d_audio,
+                               c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels, (long long)n_samples);
+        }
+    }
+    else if (slabs) {
+        node_kname = "biquad_teensy_pipe_kernel";
+        hipLaunchKernelGGL(biquad_teensy_pipe_kernel, dim3(c->channels / 64), dim3(128), 0, c->ctx->stream, (short *)d_audio,
+                           c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels, (long long)n_samples);     // node per wave, slab pipeline
+    } else {
+        node_kname = "biquad_teensy_kernel<2>";
+        hipLaunchKernelGGL((biquad_teensy_kernel<2>), dim3((c->channels + 63) / 64), dim3(64), 0, c->ctx->stream, (short *)d_audio,
+                           c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels, (long long)n_samples);
+    }
+    *name = node_kname;
+    return launch_check(node_kname);
+}
+
+extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_audio, uint64_t n_samples)
+{
+    // ---- validate
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (int rc = bind(c->ctx)) return rc;
+    if (n_samples == 0) return 0;
+    if (!d_if || !d_audio) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null buffer");
+    if (n_samples > (1ull << 31) - 4096) return fail(MSDR_STATUS_LENGTH_ERROR, "n_samples too large for one call");
+    const bool f32 = (c->arith == MSDR_ARITH_F32);
+    if (!f32 && c->nnodes && (n_samples & 1u))
+        return fail(MSDR_STATUS_LENGTH_ERROR, "AudioFilterBiquad processes sample pairs: n_samples must be even");
+
+    // ---- decide, prepare
+    ChainDecision d = chain_decide(c, d_if, d_audio, n_samples);
+    const ChainTiles t = chain_tiles(c, d.path, n_samples);
+    ChainParams p;
+    ChainLaunch r;
+    if (int rc = chain_prepare(c, d, t, d_if, d_audio, n_samples, p, r)) return rc;
+    void *const fout = p.out;                                    // where the fp32 passes of this call read and write the audio
+    if (c->dry_run) {            // msdr_chain_graph_create: everything a block-cadence call needs from the host is in place now; make no launch
+        const char *why = chain_not_capturable(c, d, n_samples);
+        return why ? fail(MSDR_STATUS_ARGUMENT_ERROR, "%s", why) : 0;
     }
 
-    if (c->dry_run) {
-        // msdr_chain_graph_create's preparation pass: everything a block-cadence call needs from the host is in place now; say whether the
-        // launches that follow are fixed (capturable into a HIP graph) -- and make none
-        if (use_pcb) {           // chain_f32pcb_kernel: one launch, its geometry fixed by the call's shape
-            if (n_samples % c->osc_len) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the oscillator's position changes from call to call at this block length: not capturable");
-            return 0;
-        }
-        if (use_pcf && c->block_pc) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the block kernel does not take this call (32 .. 512 samples, a divisor of 1024; no pending oscillator change; no PLL / LMS channels; 64 KB of LDS): chain_f32pc_kernel's launch geometry is chosen per call, not capturable");
-        if (use_pcf) return fail(MSDR_STATUS_ARGUMENT_ERROR, "an fp32 chain with per-channel FIR coefficients (chain_f32pc_kernel: launch geometry chosen per call) is not capturable");
-        if (use_pc) {            // chain_q15pc_kernel / chain_q15pco_kernel + the kernels behind it + the history kernel: a fixed set of launches at a block-cadence length
-            if (!mb_n_ok((long long)n_samples)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "not a block-cadence call (32 .. 512 samples, a divisor of 1024): nothing to capture");
-            if (pll_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the PLL demodulator runs behind the kernel: not capturable");
-            if (p.osc_hist) return fail(MSDR_STATUS_ARGUMENT_ERROR, "a pending oscillator change (the history still holds samples of an earlier table): not capturable");
-        } else
-        if (!use_mfb && !use_qb) return fail(MSDR_STATUS_ARGUMENT_ERROR, "not a block-cadence call (32 .. 512 samples, a divisor of 1024, 16-byte aligned buffers, matrix-core tables, no pending oscillator change): nothing to capture");
-        if (c->seq_bq) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the cascade runs in CMSIS order behind the kernel (a kernel of its own with host-side sizing): not capturable");
-        if (i16_via_scratch) return fail(MSDR_STATUS_ARGUMENT_ERROR, "int16 audio through the scratch batch: not capturable");
-        if (f32 && (c->f32_pll || c->aux || chain_summary(c).any_anr)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "PLL / LMS channels run behind the kernel through an auxiliary chain: not capturable");
-        if (!f32 && c->anr && (c->d_anr_on || c->anr_all > 0)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the LMS filter runs behind the kernel: not capturable");
-        if (n_samples % c->osc_len) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the oscillator's position changes from call to call at this block length: not capturable");
-        return 0;
-    }
-    const size_t lds = use_mfw ? mw_lds_bytes(c->mf_halo, c->mf_bsteps + c->mf_xsteps, c->mfw_nw, c->mf_fr) : use_fold ? fold_lds_bytes(p.ntaps_pad) : chain_lds_bytes(p.ntaps_pad);
+    // ---- the demodulator kernel
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (c->timing && c->events.size() < 8192) {
         HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
         HIP_TRY(hipEventRecord(e0, c->ctx->stream));
     }
-    const char *kname = f32 ? "chain_kernel<ArithF32>" : "chain_kernel<ArithQ15>";
-    uint32_t flavour = 0;                // msdr_chain_info.flavour: MSDR_FLAVOUR_* of the launches below, set where each one is made
-    uint32_t env_scan = 0;               // msdr_chain_info.env_scan: how the folded envelope flavour of chain_mfw_kernel scanned its row states
-    int merged_steps = -1;               // chain_mfw_kernel: k-steps per tile that went into merged steps (the least over the launches), -1 = no such launch
-    bool nodes_fused = false;            // Q15 block cadence: the biquad nodes ran inside chain_q15mb_kernel
-    const char *node_kname = "";         // msdr_chain_node_kernel: the kernel that runs the biquad nodes of this call ("": no nodes, fp32 chains)
-    unsigned block = kThreads;
-    size_t lds_used = lds;
-    int pc_tile = 0;
-    if (use_mfb) {
-        static const char *const names[3] = {"chain_mfb_kernel<0> (channel-batched block tiles)", "chain_mfb_kernel<1> (channel-batched block tiles)",
-                                             "chain_mfb_kernel<2> (channel-batched block tiles)"};
-        grid = 0;
-        for (int part = 0; part < 2; part++) {
-            const msdr_chain::BlockPart &bp = c->bpart[part];
-            if (bp.wgs == 0) continue;
-            ChainParams q = p;
-            q.mf_units = c->d_btiles + bp.offset; q.mf_nw = (int)bp.nw; q.nseg = (int)bp.tpw;
-            lds_used = mb_lds_bytes(c->mf_halo, (int)n_samples, c->mf_bsteps, (int)bp.nw, (int)bp.tpw);
-            if (launch_chain_mfb(c->ctx->stream, (int)c->nstages, part == 1, bp.wgs, bp.nw * 64, lds_used, q) != hipSuccess)
-                return fail(MSDR_STATUS_HIP_ERROR, "chain_mfb_kernel launch failed");
-            grid += bp.wgs; block = bp.nw * 64;
-            flavour |= MSDR_FLAVOUR_BLOCK | (part == 0 ? MSDR_FLAVOUR_SSB_UNITS : MSDR_FLAVOUR_ENV_UNITS);
-            if (c->nstages > 0) flavour |= (part == 0 ? MSDR_FLAVOUR_SSB_FOLD : MSDR_FLAVOUR_ENV_FOLD);      // (the block kernel runs a cascade folded or not at all)
-        }
-        kname = names[c->nstages];
-        if (c->nstages > 0) std::swap(c->d_bq_state, c->d_bq_state_alt);      // the kernel read bq_state and wrote bq_state_out
-    } else
-    if (use_mfw) {
-        block = (unsigned)c->mfw_nw * 64;
-        // SSB-table units and envelope-table units are separate launches of separate kernels (register allocation per flavour)
-        for (int part = 0; part < 2; part++) {
-            const unsigned g = part == 0 ? c->units_wgs_ssb : c->units_wgs - c->units_wgs_ssb;
-            if (g == 0) continue;
-            ChainParams q = p;
-            q.mf_units = c->d_units + (size_t)(part == 0 ? 0 : c->units_wgs_ssb) * c->mfw_nw * 2;
-            q.nseg = (int)c->part_nseg[part]; q.seg_len = c->part_seg_len[part]; q.warm = (int)(c->part_nseg[part] > 1 ? warm_tiles * kTile : 0);
-            const bool fold = part == 0 ? c->mfw_ssb_fold : c->mfw_am_fold;
-            const int rowlocal = (part == 1 && fold && !c->mf_fr && !c->d_at_tab) ? c->mfw_am_rowlocal : 0;
-            if (part == 1 && fold && !c->d_at_tab) env_scan = 1u + (uint32_t)rowlocal;
-            flavour |= part == 0 ? MSDR_FLAVOUR_SSB_UNITS : MSDR_FLAVOUR_ENV_UNITS;
-            if (c->part_nseg[part] > 1) flavour |= MSDR_FLAVOUR_SEGMENTED;
-            if (part == 1 && c->d_at_tab) {
-                // envelope units on the taps-in-registers kernel: the same unit table read with this kernel's own workgroup size
-                ChainParams a = q;
-                const long long entries = (long long)g * c->mfw_nw;
-                a.mf_tab = c->d_at_tab; a.mf_stride = c->at_stride; a.mf_nw = c->at_nw; a.fold_rot = (int)entries;
-                const unsigned ag = (unsigned)((entries + c->at_nw - 1) / c->at_nw);
-                const size_t alds = at_lds_bytes(c->at_ns, c->at_nw);
-                (void)launch_chain_amtr(c->ctx->stream, c->at_ns, (int)c->nstages, ag, (unsigned)c->at_nw * 64, alds, a);
-                if (int rc2 = launch_check("chain_amtr_kernel")) return rc2;
-                flavour |= MSDR_FLAVOUR_AMTR;
-                continue;
-            }
-            (void)launch_chain_mfw(c->ctx->stream, (int)c->nstages, part == 1, fold, c->mf_fr, rowlocal, g, block, lds, q);
-            const int part_merged = mw_merges_steps((int)c->nstages, part == 1, fold, c->mf_fr, rowlocal) ? c->mf_merged[part] : 0;
-            merged_steps = merged_steps < 0 ? part_merged : std::min(merged_steps, part_merged);
-            if (int rc = launch_check("chain_mfw_kernel")) return rc;
-            if (fold) flavour |= part == 0 ? MSDR_FLAVOUR_SSB_FOLD : MSDR_FLAVOUR_ENV_FOLD;
-            if (c->mf_fr) flavour |= MSDR_FLAVOUR_FULL_RATE | (c->mf_compact ? MSDR_FLAVOUR_COMPACT : 0u) | ((part == 1 && c->mf_share_iq) ? MSDR_FLAVOUR_SHARED_IQ : 0u);
-        }
-        static const char *const names[5] = {"chain_mfw_kernel<0>", "chain_mfw_kernel<1>", "chain_mfw_kernel<2>", "chain_mfw_kernel<3>", "chain_mfw_kernel<4>"};
-        static const char *const names_fr[5] = {"chain_mfw_kernel<0> full-rate NCO streams", "chain_mfw_kernel<1> full-rate NCO streams", "chain_mfw_kernel<2> full-rate NCO streams",
-                                                "chain_mfw_kernel<3> full-rate NCO streams", "chain_mfw_kernel<4> full-rate NCO streams"};
-        kname = c->mf_fr ? names_fr[c->nstages] : names[c->nstages];
-        if (c->d_at_tab && c->units_wgs > c->units_wgs_ssb) kname = c->units_wgs_ssb ? "chain_mfw_kernel + chain_amtr_kernel" : "chain_amtr_kernel";
-        std::swap(c->d_bq_state, c->d_bq_state_alt);          // the kernel read bq_state and wrote bq_state_out
-#ifdef MSDR_STAMPS
-        if (getenv("MSDR_STAMP_PRINT")) {
-            HIP_TRY(hipStreamSynchronize(c->ctx->stream));
-            std::vector<unsigned long long> h((size_t)grid * c->mfw_nw * 8);
-            HIP_TRY(hipMemcpy(h.data(), p.dbg_buf, h.size() * 8, hipMemcpyDeviceToHost));
-            double sum[8] = {0}; size_t cnt = 0;
-            for (size_t u = 0; u < h.size() / 8; u++) { if (!h[u * 8 + 0] && !h[u * 8 + 1]) continue; cnt++; for (int k = 0; k < 8; k++) sum[k] += (double)h[u * 8 + k]; }
-            const double tl = (double)((n_samples + kMwTile - 1) / kMwTile) * c->channels / std::max<size_t>(cnt, 1);
-            fprintf(stderr, "stamps (cycles per tile per wave, %zu units, %.1f tiles each): prefetch-issue %.0f | mfma %.0f | demod+swap %.0f | iir %.0f | store %.0f | halo %.0f | vmwait %.0f | stage %.0f\n",
-                    cnt, tl, sum[0] / cnt / tl, sum[1] / cnt / tl, sum[2] / cnt / tl, sum[3] / cnt / tl, sum[4] / cnt / tl, sum[5] / cnt / tl, sum[6] / cnt / tl, sum[7] / cnt / tl);
-        }
-#endif
+    int rc = 0;
+    switch (d.path) {
+    case kPathF32Pcb:     rc = chain_launch_f32pcb(c, d, p, r); break;
+    case kPathF32Pc:      rc = chain_launch_f32pc(c, d, p, r); break;
+    case kPathMfb:        rc = chain_launch_mfb(c, d, p, r); break;
+    case kPathMfw:        rc = chain_launch_mfw(c, d, t, p, r); break;
+    case kPathFold:       rc = chain_launch_fold(c, d, p, r); break;
+    case kPathF32Generic: rc = chain_launch_generic(c, d, p, r); break;
+    case kPathQ15Mb:      rc = chain_launch_q15mb(c, d, p, r); break;
+    case kPathQ15Mf:      rc = chain_launch_q15mf(c, d, p, r); break;
+    case kPathQ15Pcb:     rc = chain_launch_q15pcb(c, d, p, r); break;
+    case kPathQ15Pc:      rc = chain_launch_q15pc(c, d, p, r); break;
+    case kPathQ15Generic: rc = chain_launch_generic(c, d, p, r); break;
     }
-    else if (use_fold) {
-        (void)launch_chain_fold(c->ctx->stream, c->fold_P, grid, lds, p);
-        flavour |= MSDR_FLAVOUR_VALU_FOLD | ((uint32_t)c->fold_P << MSDR_FLAVOUR_FOLD_PERIOD_SHIFT) | (nseg > 1 ? MSDR_FLAVOUR_SEGMENTED : 0u);
-        kname = c->fold_P == 4 ? "chain_fold_kernel<4>" : c->fold_P == 2 ? "chain_fold_kernel<2>" : "chain_fold_kernel<1>";
-    }
-    else if (use_pcb) {
-        PcbParams q;
-        memset(&q, 0, sizeof q);
-        q.x = d_if; q.out = d_audio; q.hist_in = c->d_hist[c->cur]; q.hist_out = c->d_hist[c->cur ^ 1]; q.n = (int)n_samples; q.channels = (int)c->channels;
-        q.hist_len = (int)c->hist_len; q.np = c->pc_np; q.taps = c->d_pcf_taps; q.chan_mode = c->d_mode;
-        q.osc = c->opc_active ? c->d_osc_bank : (const void *)c->d_osc; q.osc_len = (int)c->osc_len; q.osc_stride = c->opc_active ? (int)c->osc_len : 0;
-        q.phase0 = (int)c->phase; q.in_scale = c->in_scale; q.out_i16 = (c->flags & MSDR_CHAIN_OUT_I16) ? 1 : 0;
-        q.in_row = c->n_inputs ? c->d_in_row : nullptr;
-        if (c->seq_bq && c->seq_bq->stages > 0) {          // the cascade's own table and state: direct calls of the stage, unfused calls and these share them
-            q.stages = (int)c->seq_bq->stages; q.bq_state = c->seq_bq->d_state;
-            q.bq_tab = c->seq_bq->per_channel ? c->seq_bq->d_pc_coeffs : c->seq_bq->d_coeffs; q.bq_stride = c->seq_bq->per_channel ? kSbqTabFloats : 0;
-            flavour |= MSDR_FLAVOUR_SEQ_CASCADE | (c->seq_bq->per_channel ? (uint32_t)MSDR_FLAVOUR_CASCADE_PC : 0u);
-        }
-        PcLaunch geo;
-        if (launch_chain_f32pcb(c->ctx->stream, c->mixer == kMixerFs4, q, &geo) != hipSuccess)
-            return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pcb_kernel launch failed");
-        kname = c->opc_active ? kPcboKernelName : kPcbKernelName;
-        grid = geo.grid; block = geo.block; lds_used = geo.lds_bytes; nseg = 1; pc_tile = geo.tile;
-        flavour |= MSDR_FLAVOUR_BLOCK | MSDR_FLAVOUR_TAPS_PC | (c->opc_active ? (uint32_t)MSDR_FLAVOUR_OSC_PC : 0u) | (c->n_inputs ? (uint32_t)MSDR_FLAVOUR_SHARED_IF : 0u);
-    }
-    else if (use_pcf) {
-        PcfParams q;
-        memset(&q, 0, sizeof q);
-        q.x = d_if; q.out = (float *)fout; q.hist_in = c->d_hist[c->cur]; q.n = (long long)n_samples; q.channels = (int)c->channels;
-        q.hist_len = (int)c->hist_len; q.np = c->pc_np; q.taps = c->d_pcf_taps; q.chan_mode = c->d_mode; q.mixer = c->mixer; q.osc = c->d_osc;
-        q.osc_len = (int)c->osc_len; q.phase0 = (int)c->phase; q.in_scale = c->in_scale; q.osc_hist = p.osc_hist;
-        q.in_row = c->n_inputs ? c->d_in_row : nullptr;
-        PcLaunch geo;
-        if (c->opc_active) {          // per-channel oscillator tables: the bank in place of the shared table
-            q.osc = c->d_osc_bank;
-            if (launch_chain_f32pco(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, q, &geo) != hipSuccess)
-                return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pco_kernel launch failed");
-            kname = kPcfoKernelName; flavour |= MSDR_FLAVOUR_OSC_PC;
-        } else {
-            if (launch_chain_f32pc(c->ctx->stream, false, c->ctx->num_cus, (int)c->time_segments, q, &geo) != hipSuccess)
-                return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pc_kernel launch failed");
-            kname = kPcfKernelName;
-        }
-        grid = geo.grid; block = geo.block; lds_used = geo.lds_bytes; nseg = geo.nseg; pc_tile = geo.tile;
-        flavour |= MSDR_FLAVOUR_TAPS_PC | (geo.nseg > 1 ? MSDR_FLAVOUR_SEGMENTED : 0u) | (c->n_inputs ? (uint32_t)MSDR_FLAVOUR_SHARED_IF : 0u);
-    }
-    else if (f32) { (void)launch_chain_generic(c->ctx->stream, false, grid, lds, p); if (nseg > 1) flavour |= MSDR_FLAVOUR_SEGMENTED; }
-    else if (use_qb) {
-        grid = 0;
-        // the two biquad nodes as the kernel's second phase: the reference's configuration (one stage per node, nothing between the
-        // demodulator and the nodes), one 128-sample block, and every launch of this call with one tile per wave on three or more waves
-        // (small batches: up to 16 384 channels of one flavour on this part); MSDR_Q15_NO_FUSE=1 at create time: the node kernel behind it as before
-        nodes_fused = c->nnodes == 2 && c->nodes[0]->max_stage == 0 && c->nodes[1]->max_stage == 0 && n_samples == 128 && !pll_active &&
-                      !(c->anr && (c->d_anr_on || c->anr_all > 0)) && !c->no_fuse && !chain_nodes_per_channel(c);
-        for (int part = 0; part < 2 && nodes_fused; part++) {
-            const msdr_chain::BlockPart &bp = c->bpart[part];
-            if (bp.wgs && (bp.tpw != 1 || bp.nw < 3 || qb_nodes_lds_bytes(c->qm_halo, 128, c->qm_bsteps, (int)bp.nw) > 160 * 1024)) nodes_fused = false;
-        }
-        for (int part = 0; part < 2; part++) {
-            const msdr_chain::BlockPart &bp = c->bpart[part];
-            if (bp.wgs == 0) continue;
-            ChainParams q = p;
-            q.mf_tab = c->d_qm_tab; q.mf_stride = c->qm_stride; q.mf_halo = c->qm_halo; q.mf_bsteps = c->qm_bsteps;
-            q.mf_units = c->d_btiles + bp.offset; q.mf_nw = (int)bp.nw; q.nseg = (int)bp.tpw;
-            lds_used = nodes_fused ? qb_nodes_lds_bytes(c->qm_halo, 128, c->qm_bsteps, (int)bp.nw) : qb_lds_bytes(c->qm_halo, (int)n_samples, c->qm_bsteps, (int)bp.nw, (int)bp.tpw);
-            if (nodes_fused) { q.bq_state = reinterpret_cast<float *>(c->nodes[0]->d_defs); q.bq_state_out = reinterpret_cast<float *>(c->nodes[1]->d_defs); }
-            const int flavour = part == 0 ? 0 : (c->sqrt_kind == 1 ? 2 : 1);
-            if (launch_chain_q15mb(c->ctx->stream, flavour, nodes_fused, bp.wgs, bp.nw * 64, lds_used, q) != hipSuccess)
-                return fail(MSDR_STATUS_HIP_ERROR, "chain_q15mb_kernel launch failed");
-            grid += bp.wgs; block = bp.nw * 64;
-        }
-        kname = nodes_fused ? "chain_q15mb_kernel (block tiles) + both biquad nodes" : "chain_q15mb_kernel (channel-batched block tiles)";
-        if (nodes_fused) node_kname = "chain_q15mb_kernel";
-    }
-    else if (use_qm) {
-        // channels grouped by (tap set, flavour): a workgroup's waves share one table; one launch per group in use
-        const int env_flavour = (c->sqrt_kind == 1) ? 2 : 1;
-        auto flavour_of = [&](uint32_t ch) { const int m = c->h_mode[ch]; return (m == MSDR_MODE_LSB || m == MSDR_MODE_USB) ? 0 : env_flavour; };
-        if (c->qm_order_gen != c->mode_gen) {
-            std::vector<int> order;
-            c->qm_group_start.assign((size_t)c->tapsets * 3, 0); c->qm_group_count.assign((size_t)c->tapsets * 3, 0);
-            for (uint32_t s = 0; s < c->tapsets; s++)
-                for (int fl = 0; fl < 3; fl++) {
-                    const size_t gi = (size_t)s * 3 + fl;
-                    c->qm_group_start[gi] = (uint32_t)order.size();
-                    for (uint32_t ch = 0; ch < c->channels; ch++)
-                        if ((uint32_t)c->h_tapset[ch] == s && flavour_of(ch) == fl) order.push_back((int)ch);
-                    c->qm_group_count[gi] = (uint32_t)order.size() - c->qm_group_start[gi];
-                }
-            if (!c->d_qm_order) HIP_TRY(hipMalloc((void **)&c->d_qm_order, (size_t)c->channels * sizeof(int)));
-            HIP_TRY(hipMemcpyAsync(c->d_qm_order, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice, c->ctx->stream));
-            HIP_TRY(hipStreamSynchronize(c->ctx->stream));
-            c->qm_order_gen = c->mode_gen;
-        }
-        const long long qtiles = ((long long)n_samples + kQmTile - 1) / kQmTile;
-        ChainParams q = p;
-        q.mf_tab = c->d_qm_tab; q.mf_stride = c->qm_stride; q.mf_halo = c->qm_halo; q.mf_bsteps = c->qm_bsteps; q.warm = 0; q.mf_units = c->d_qm_order;
-        int nw = 8;
-        long long qseg = 1;
-        for (size_t gi = 0; gi < c->qm_group_count.size(); gi++) {
-            const long long cnt = c->qm_group_count[gi];
-            if (!cnt) continue;
-            // every launch fills the GPU on its own: aim at two rounds of 16 waves per CU, at least two tiles per segment
-            qseg = (8192 + cnt - 1) / cnt;
-            qseg = std::max<long long>(1, std::min<long long>(qseg, std::max<long long>(1, qtiles / 2)));
-            if (c->time_segments > 0) qseg = std::max<long long>(1, std::min<long long>(c->time_segments, qtiles));
-            const long long qseg_len = ((qtiles + qseg - 1) / qseg) * kQmTile;
-            qseg = ((long long)n_samples + qseg_len - 1) / qseg_len;
-            nw = 8;
-            while (nw > 1 && cnt * qseg < 256LL * nw) nw >>= 1;
-            while (nw > 1 && qm_lds_bytes(c->qm_halo, c->qm_bsteps, nw, c->qm_fr) > 80 * 1024) nw >>= 1;     // two workgroups per CU
-            const size_t qlds = qm_lds_bytes(c->qm_halo, c->qm_bsteps, nw, c->qm_fr);
-            q.mf_nw = nw; q.nseg = (int)qseg; q.seg_len = qseg_len;
-            q.fold_period = (int)c->qm_group_start[gi]; q.fold_rot = (int)cnt; q.mf_waves = (int)(gi / 3);
-            grid = (unsigned)((cnt * qseg + nw - 1) / nw);
-            (void)launch_chain_q15mf(c->ctx->stream, (int)(gi % 3), c->qm_fr, grid, (unsigned)nw * 64, qlds, q);
-            if (int rc = launch_check("chain_q15mf_kernel")) return rc;
-        }
-        kname = c->qm_fr ? "chain_q15mf_kernel full-rate NCO streams" : "chain_q15mf_kernel"; block = (unsigned)nw * 64; nseg = qseg;
-    }
-    else if (use_qpcb) {
-        QpcbParams q;
-        memset(&q, 0, sizeof q);
-        q.x = d_if; q.out = (short *)d_audio; q.hist_in = c->d_hist[c->cur]; q.hist_out = c->d_hist[c->cur ^ 1]; q.n = (int)n_samples; q.channels = (int)c->channels;
-        q.hist_len = (int)c->hist_len; q.np = c->pc_np; q.taps = c->d_pc_taps; q.chan_mode = c->d_mode;
-        q.osc = c->opc_active ? c->d_osc_bank : (const void *)c->d_osc; q.osc_len = (int)c->osc_len; q.osc_stride = c->opc_active ? (int)c->osc_len : 0;
-        q.phase0 = (int)c->phase; q.sqrt_kind = c->sqrt_kind; q.in_row = c->n_inputs ? c->d_in_row : nullptr;
-        q.nnodes = (int)c->nnodes; q.defs0 = c->nnodes > 0 ? c->nodes[0]->d_defs : nullptr; q.defs1 = c->nnodes > 1 ? c->nodes[1]->d_defs : nullptr;
-        PcLaunch geo;
-        if (launch_chain_q15pcb(c->ctx->stream, c->mixer == kMixerFs4, q, &geo) != hipSuccess)
-            return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pcb_kernel launch failed");
-        kname = c->opc_active ? kQpcboKernelName : kQpcbKernelName;
-        if (c->nnodes) node_kname = "chain_q15pcb_kernel";
-        grid = geo.grid; block = geo.block; lds_used = geo.lds_bytes; nseg = 1; pc_tile = geo.tile;
-    }
-    else if (use_pc) {
-        PcParams q;
-        memset(&q, 0, sizeof q);
-        q.x = d_if; q.out = (short *)d_audio; q.hist_in = c->d_hist[c->cur]; q.n = (long long)n_samples; q.channels = (int)c->channels;
-        q.hist_len = (int)c->hist_len; q.np = c->pc_np; q.taps = c->d_pc_taps; q.chan_mode = c->d_mode; q.mixer = c->mixer; q.osc = c->d_osc;
-        q.osc_len = (int)c->osc_len; q.phase0 = (int)c->phase; q.sqrt_kind = c->sqrt_kind; q.syncam_q = p.syncam_q; q.osc_hist = p.osc_hist;
-        q.in_row = c->n_inputs ? c->d_in_row : nullptr;
-        PcLaunch geo;
-        if (c->opc_active) {          // per-channel oscillator tables: the bank in place of the shared table
-            q.osc = c->d_osc_bank;
-            if (launch_chain_q15pco(c->ctx->stream, c->ctx->num_cus, q, &geo) != hipSuccess)
-                return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pco_kernel launch failed");
-            kname = "chain_q15pco_kernel (per-channel taps and oscillator tables)";
-        } else {
-            if (launch_chain_q15pc(c->ctx->stream, false, c->ctx->num_cus, q, &geo) != hipSuccess)
-                return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pc_kernel launch failed");
-            kname = "chain_q15pc_kernel (per-channel taps)";
-        }
-        grid = geo.grid; block = geo.block; lds_used = geo.lds_bytes; nseg = geo.nseg; pc_tile = geo.tile;
-    }
-    else     (void)launch_chain_generic(c->ctx->stream, true, grid, lds, p);
-    if (int rc = launch_check("chain_kernel")) return rc;
+    if (rc) return rc;
+    if (int rc2 = launch_check("chain_kernel")) return rc2;
     if (e0) { HIP_TRY(hipEventRecord(e1, c->ctx->stream)); c->events.emplace_back(e0, e1); }
 
-    if (c->seq_bq && !use_pcb) // F32, ill-conditioned cascade: arm_biquad_cascade_df1_f32 in CMSIS order, in place on the audio (chain_f32pcb_kernel ran it itself)
-        { if (int rc = msdr_biquad_df1_f32_process(c->seq_bq, (const float *)fout, (float *)fout, (uint32_t)n_samples)) return rc; flavour |= MSDR_FLAVOUR_SEQ_CASCADE | (c->seq_bq->per_channel ? (uint32_t)MSDR_FLAVOUR_CASCADE_PC : 0u); }
+    // ---- the passes behind it
+    if (c->seq_bq && d.path != kPathF32Pcb) // F32, ill-conditioned cascade: arm_biquad_cascade_df1_f32 in CMSIS order, in place on the audio (chain_f32pcb_kernel ran it itself)
+        { if (int rc2 = msdr_biquad_df1_f32_process(c->seq_bq, (const float *)fout, (float *)fout, (uint32_t)n_samples)) return rc2; r.flavour |= MSDR_FLAVOUR_SEQ_CASCADE | (c->seq_bq->per_channel ? (uint32_t)MSDR_FLAVOUR_CASCADE_PC : 0u); }
 
-    if (pll_active)            // SYNCAM channels: I (in d_audio) and Q (scratch) -> PLL demodulator -> audio, before the biquad nodes
-        if (int rc = msdr_syncam_q15(c->pll, c->d_mode, (const q15_t *)d_audio, c->d_pll_q, (q15_t *)d_audio, (uint32_t)n_samples)) return rc;
+    if (d.pll_active)          // SYNCAM channels: I (in d_audio) and Q (scratch) -> PLL demodulator -> audio, before the biquad nodes
+        if (int rc2 = msdr_syncam_q15(c->pll, c->d_mode, (const q15_t *)d_audio, c->d_pll_q, (q15_t *)d_audio, (uint32_t)n_samples)) return rc2;
 
-    if (c->anr && (c->d_anr_on || c->anr_all > 0))      // LMS notch / noise reduction (.ino:702-770), then the biquad nodes
-        if (int rc = msdr_anr_q15(c->anr, c->d_anr_on, c->anr_all, (q15_t *)d_audio, (uint32_t)n_samples)) return rc;
+    if (d.anr_active)          // LMS notch / noise reduction (.ino:702-770), then the biquad nodes
+        if (int rc2 = msdr_anr_q15(c->anr, c->d_anr_on, c->anr_all, (q15_t *)d_audio, (uint32_t)n_samples)) return rc2;
 
-    if (use_qpcb) { /* (chain_q15pcb_kernel ran the nodes as its third phase, on the same records) */ }
-    else if (c->nnodes == 2 && !nodes_fused) {      // biquad1_dac -> biquad2_dac in one pass over the audio
-        const bool slabs = (c->channels & 63u) == 0 && (n_samples & 127u) == 0 && (reinterpret_cast<uintptr_t>(d_audio) & 15) == 0;
-        const int per_group = c->nodes[0]->pipe_ch;
-        // one 128-sample block, the reference's cadence, one stage per node: the pipeline over sub-slabs inside the block (biquad_teensy_blk_kernel),
-        // ANY channel count -- the reference's own single receiver included (1 channel: 27 -> 12 us per tick; its rows past the end idle) --
-        // while its 16-channel workgroups find a CU each (4096 channels: 15.1 -> 13.2 us per tick; at 8192 the slab kernel is ahead again,
-        // 16.6 vs 17.3, tools/r05_nodes_x.sh); MSDR_BIQUAD_BLK=0 / 1 at create time overrides
-        const uint32_t blk_wgs = (c->channels + kTqbCh - 1) / kTqbCh;
-        if (chain_nodes_per_channel(c)) {      // every channel its own records: one lane = one channel with its own coefficients, any shape
-            node_kname = "biquad_teensy_pc_kernel<2>";
-            if (launch_biquad_teensy_pc(c->ctx->stream, 2, (short *)d_audio, c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels, (long long)n_samples) != hipSuccess)
-                return fail(MSDR_STATUS_HIP_ERROR, "biquad_teensy_pc_kernel<2> launch failed");
-        } else
-        if (n_samples == 128 && (reinterpret_cast<uintptr_t>(d_audio) & 15) == 0 && c->nodes[0]->max_stage == 0 && c->nodes[1]->max_stage == 0 &&
-            (c->blk_force >= 1 || (c->blk_force < 0 && blk_wgs <= (uint32_t)c->ctx->num_cus))) {
-            node_kname = "biquad_teensy_blk_kernel";
-            hipLaunchKernelGGL(biquad_teensy_blk_kernel, dim3(blk_wgs), dim3(kTqbThreads), tqb_lds_bytes(), c->ctx->stream, (short *)d_audio,
-                               c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels);
-        } else
-        if ((n_samples & 127u) == 0 && (reinterpret_cast<uintptr_t>(d_audio) & 15) == 0 && c->channels % (unsigned)per_group == 0 &&
-            c->nodes[0]->max_stage == 0 && c->nodes[1]->max_stage == 0) {
-            // one stage per node (the reference's configuration): the recursions alone on two waves, the input products element-wise on the others
-            if (per_group == 64) {
-                node_kname = "biquad_teensy_pipe4_kernel<2,64>";
-                hipLaunchKernelGGL((biquad_teensy_pipe4_kernel<2, 64>), dim3(c->channels / 64), dim3(tq4_threads(64)), tq4_lds_bytes(64), c->ctx->stream, (short *)d_audio,
-                                   c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels, (long long)n_samples);
-            } else if (per_group == 32) {
-                node_kname = "biquad_teensy_pipe4_kernel<2,32>";
-                hipLaunchKernelGGL((biquad_teensy_pipe4_kernel<2, 32>), dim3(c->channels / 32), dim3(tq4_threads(32)), tq4_lds_bytes(32), c->ctx->stream, (short *)d_audio,
-                                   c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels, (long long)n_samples);
-            } else {
-                node_kname = "biquad_teensy_pipe4_kernel<2,16>";
-                hipLaunchKernelGGL((biquad_teensy_pipe4_kernel<2, 16>), dim3(c->channels / 16), dim3(tq4_threads(16)), tq4_lds_bytes(16), c->ctx->stream, (short *)d_audio,
-                                   c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels, (long long)n_samples);
-            }
-        }
-        else if (slabs) {
-            node_kname = "biquad_teensy_pipe_kernel";
-            hipLaunchKernelGGL(biquad_teensy_pipe_kernel, dim3(c->channels / 64), dim3(128), 0, c->ctx->stream, (short *)d_audio,
-                               c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels, (long long)n_samples);     // node per wave, slab pipeline
-        } else {
-            node_kname = "biquad_teensy_kernel<2>";
-            hipLaunchKernelGGL((biquad_teensy_kernel<2>), dim3((c->channels + 63) / 64), dim3(64), 0, c->ctx->stream, (short *)d_audio,
-                               c->nodes[0]->d_defs, c->nodes[1]->d_defs, (int)c->channels, (long long)n_samples);
-        }
-        if (int rc = launch_check(node_kname)) return rc;
+    if (d.path == kPathQ15Pcb) { /* (chain_q15pcb_kernel ran the nodes as its third phase, on the same records) */ }
+    else if (c->nnodes == 2 && !d.nodes_fused) {
+        if (int rc2 = chain_two_nodes(c, d_audio, n_samples, &r.node_kname)) return rc2;
     } else if (c->nnodes == 1) {
-        if (int rc = msdr_biquad_q15_update(c->nodes[0], (q15_t *)d_audio, (uint32_t)n_samples)) return rc;
-        node_kname = c->nodes[0]->last_kernel;
+        if (int rc2 = msdr_biquad_q15_update(c->nodes[0], (q15_t *)d_audio, (uint32_t)n_samples)) return rc2;
+        r.node_kname = c->nodes[0]->last_kernel;
     }
-    c->node_kernel = node_kname;
+    c->node_kernel = r.node_kname;
 
     // rows f2 / f3 inside the fp32 chain: PLL / LMS channels are redone behind the main kernel (before the history moves on: a rebuilt
     // auxiliary chain takes over the history and table position this call started from)
-    if (f32) if (int rc = chain_post_run(c, d_if, (float *)fout, n_samples)) return rc;
-    if (i16_via_scratch) {
+    if (f32) if (int rc2 = chain_post_run(c, d_if, (float *)fout, n_samples)) return rc2;
+    if (d.i16 == kI16ViaScratch) {
         const long long total = (long long)c->channels * (long long)n_samples;
         hipLaunchKernelGGL(f32_to_q15_kernel, dim3(grid_1d((total + 3) / 4)), dim3(256), 0, c->ctx->stream, (const float *)fout, (short *)d_audio, total);
-        if (int rc = launch_check("f32_to_q15_kernel")) return rc;
+        if (int rc2 = launch_check("f32_to_q15_kernel")) return rc2;
     }
 
-    if (!use_mfb && !use_qb && !use_pcb && !use_qpcb && c->n_inputs) {          // msdr_chain_set_input_rows: each channel's history from the row it heard
+    // ---- history and bookkeeping (the block kernels write the next history themselves)
+    if (path_block(d.path)) { }
+    else if (c->n_inputs) {          // msdr_chain_set_input_rows: each channel's history from the row it heard
         hipLaunchKernelGGL((history_rows_kernel<int16_t>), dim3(grid_1d((long long)c->channels * c->hist_len)), dim3(256), 0, c->ctx->stream,
                            d_if, (const int16_t *)c->d_hist[c->cur], c->d_hist[c->cur ^ 1], (long long)n_samples, (int)c->hist_len,
                            (int)c->channels, (const int *)c->d_in_row);
-        if (int rc = launch_check("history_rows_kernel")) return rc;
-    } else
-    if (!use_mfb && !use_qb && !use_pcb && !use_qpcb) {            // (the block kernels write the next history themselves)
+        if (int rc2 = launch_check("history_rows_kernel")) return rc2;
+    } else {
         hipLaunchKernelGGL((history_kernel<int16_t>), dim3(grid_1d((long long)c->channels * c->hist_len)), dim3(256), 0, c->ctx->stream,
                            d_if, (const int16_t *)c->d_hist[c->cur], c->d_hist[c->cur ^ 1], (long long)n_samples, (int)c->hist_len,
                            (int)c->channels);
-        if (int rc = launch_check("history_kernel")) return rc;
+        if (int rc2 = launch_check("history_kernel")) return rc2;
     }
     c->cur ^= 1; c->gen++;
     c->phase = (c->phase + (long long)(n_samples % c->osc_len)) % c->osc_len;
     if (c->force_generic) {
         for (auto &o : c->osc_pending) o.elapsed += (long long)n_samples;
         if (c->osc_pending.empty() || c->osc_pending.back().elapsed >= (long long)c->hist_len)
-            if (int rc = chain_leave_generic(c)) return rc;
+            if (int rc2 = chain_leave_generic(c)) return rc2;
     }
 
+    // ---- info
     // (the cascade's kernel is always named in full: a main kernel's name that leaves no room for it in info.kernel is cut short instead;
     //  behind chain_f32pcb_kernel it names the cascade that ran as that kernel's second phase)
     const char *bq_name = !c->seq_bq ? "" : c->seq_bq->per_channel ? " + biquad_df1_seq_pc_kernel" : c->seq_bq->sequential ? " + biquad_df1_seq_kernel" : " + biquad_df1_kernel";
-    snprintf(c->info.kernel, sizeof c->info.kernel, "%.*s%s", (int)(sizeof c->info.kernel - 1 - strlen(bq_name)), kname, bq_name);
-    c->info.grid = grid; c->info.block = block; c->info.lds_bytes = (uint32_t)lds_used;
-    c->info.env_scan = env_scan; c->info.flavour = f32 ? flavour : 0u;
-    c->info.time_segments = (uint32_t)nseg; c->info.warmup = (uint32_t)p.warm; c->info.tile = (uint32_t)((use_pc || use_pcf) ? pc_tile : kTile);
-    c->info.taps_padded = (use_pc || use_pcf) ? (uint32_t)c->pc_np : c->ntaps_pad;
-    c->info.mfma_ksteps = use_mf ? (uint32_t)(c->mf_bsteps - std::max(merged_steps, 0)) : use_qm ? (uint32_t)c->qm_bsteps : 0u;
+    snprintf(c->info.kernel, sizeof c->info.kernel, "%.*s%s", (int)(sizeof c->info.kernel - 1 - strlen(bq_name)), r.kname, bq_name);
+    c->info.grid = r.grid; c->info.block = r.block; c->info.lds_bytes = (uint32_t)r.lds_bytes;
+    c->info.env_scan = r.env_scan; c->info.flavour = f32 ? r.flavour : 0u;
+    c->info.time_segments = (uint32_t)r.nseg; c->info.warmup = (uint32_t)p.warm; c->info.tile = (uint32_t)r.tile;
+    c->info.taps_padded = path_per_channel(d.path) ? (uint32_t)c->pc_np : c->ntaps_pad;
+    c->info.mfma_ksteps = d.mf ? (uint32_t)(c->mf_bsteps - std::max(r.merged_steps, 0)) : path_qm(d.path) ? (uint32_t)c->qm_bsteps : 0u;
     return 0;
 }
 

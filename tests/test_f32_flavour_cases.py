@@ -36,8 +36,14 @@ def test_signatures_are_distinct():
 
 def test_kernel_names_equal_those_of_msdr_chain_process():
     src = open(os.path.join(ROOT, "minimal-sdr_amd", "csrc", "msdr_api.hip")).read()
-    body = src[src.index('extern "C" int msdr_chain_process('):]
-    body = body[:body.index("\n}\n")]
+    # the names are reported by the per-path functions msdr_chain_process switches over (static int chain_launch_<path>(...)): the region
+    # from the first of them to the end of msdr_chain_process, and every one of them lies inside it
+    launchers = [m.start() for m in re.finditer(r"^static int chain_launch_\w+\(", src, re.M)]
+    entry = src.index('extern "C" int msdr_chain_process(')
+    end = entry + src[entry:].index("\n}\n")
+    assert len(launchers) >= 10 and launchers[-1] < entry, launchers
+    body = src[launchers[0]:end]
+    assert len(re.findall(r"\bchain_launch_\w+\(c, d,", src[entry:end])) == 11       # one per path, all called from msdr_chain_process
     body = re.sub(r'launch_check\("[^"]*"\)', "", body)
     lits = {m for m in re.findall(r'"(chain_[^"]*)"', body) if "q15" not in m.lower() and not m.endswith("launch failed")}
     assert len(lits) >= 19, sorted(lits)

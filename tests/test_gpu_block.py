@@ -602,3 +602,98 @@ def test_chain_graph_refuses_what_it_cannot_hold(ctx, orc):
     g.close()
     # a chain left untouched by the refusals: a direct call still works from the state the one replay left
     chain.process(dx[0], dy[0], 128)
+
+
+def test_chain_graph_refusal_says_which_pass_is_in_the_way(ctx, orc):
+    """msdr_chain_graph_create on block-cadence calls whose demodulator kernel is capturable and something behind it is not: one chain per clause."""
+    lp = _lowpass(102)
+    c30 = lambda kind, f, q: (lambda c: [c[0], c[1], c[2], -c[3], -c[4]])(orc.biquad_design(kind, np.float32(f * orclib.AUDIO_SAMPLE_RATE_EXACT / 24000.0), q).astype(np.float64) / 2 ** 30)
+    bad = np.array([c30(orclib.BQ_HIGHPASS, 300.0, 0.7)] * 2, np.float32)          # (runs in CMSIS order: tests/test_gpu_out_i16.py)
+    modes = np.array([orclib.SYNCAM, orclib.AM, orclib.AM], np.int32)
+    nodes = [[n] for n in _ref_nodes(orc)]
+    q15 = lambda: msdr.Chain(ctx, msdr.ARITH_Q15, 3, np.round(lp * 32767).astype(np.int16), np.round(lp * 32767).astype(np.int16), mode=orclib.AM, biquad_nodes=nodes)
+    f32 = lambda **kw: msdr.Chain(ctx, msdr.ARITH_F32, 3, lp, lp, mixer=msdr.MIXER_FS4, **kw)
+
+    def lms():
+        c = q15()
+        c.set_anr(None, 1)
+        return c
+    t = np.arange(128)
+    oi, oq = np.sin(2 * np.pi * t / 4).round().astype(np.float32), np.cos(2 * np.pi * t / 4).round().astype(np.float32)
+    for make, n, dtype, text in (
+            (lambda: f32(mode=orclib.LSB, biquad_coeffs=bad), 128, np.float32, "the cascade runs in CMSIS order behind the kernel"),
+            (lambda: f32(modes=modes, flags=msdr.CHAIN_SYNCAM_PLL | msdr.CHAIN_OUT_I16), 128, np.int16, "int16 audio through the scratch batch"),
+            (lambda: f32(modes=modes, flags=msdr.CHAIN_SYNCAM_PLL), 128, np.float32, "PLL / LMS channels run behind the kernel through an auxiliary chain"),
+            (lms, 128, np.int16, "the LMS filter runs behind the kernel"),
+            (lambda: msdr.Chain(ctx, msdr.ARITH_F32, 3, lp, lp, mixer=msdr.MIXER_NCO, mode=orclib.AM, osc_i=oi, osc_q=oq), 32, np.float32,
+             "the oscillator's position changes from call to call at this block length")):
+        chain = make()
+        dx, dy = [ctx.array((3, n), np.int16).fill(0) for _ in range(2)], [ctx.array((3, n), dtype) for _ in range(2)]
+        with pytest.raises(msdr.MsdrError, match=text + ".*not capturable"):
+            chain.graph(dx, dy, n)
+        chain.process(dx[0], dy[0], n)                             # the refusal left the chain as it was: a direct call runs
+        chain.close()
+
+
+def test_block_call_corners_fall_to_the_streaming_kernels(ctx, orc, monkeypatch):
+    """What takes a 128-sample call off the block kernels, or keeps the nodes out of chain_q15mb_kernel, changes no sample: (1) a d_if or
+    d_audio that is not 16-byte aligned, (2) SYNCAM channels under the PLL, (3) the LMS filter between demodulator and nodes -- the tile
+    table is still laid out for the node phase (three waves or more per workgroup)."""
+    rng = np.random.default_rng(41)
+    ch, ticks = 16, 4
+    lpq = np.round(_lowpass(102) * 32767).astype(np.int16)
+    nodes = [[n] for n in _ref_nodes(orc)]
+    x = rng.integers(-12000, 12001, (ticks, ch * 128)).astype(np.int16)
+
+    def stream(chain, off_in=0, off_out=0, dtype=np.int16):
+        out, names = [], set()
+        for t in range(ticks):
+            buf = np.zeros(ch * 128 + 16, np.int16)
+            buf[off_in // 2:off_in // 2 + ch * 128] = x[t]
+            dx, dy = ctx.to_device(buf), ctx.array((ch * 128 + 16,), dtype).fill(0)
+            chain.process(dx.offset(off_in), dy.offset(off_out), 128)
+            o = dy.download()
+            k = off_out // o.itemsize
+            assert not o[:k].any() and not o[k + ch * 128:].any()
+            out.append(o[k:k + ch * 128])
+            names.add((chain.info()["kernel"], chain.node_kernel(), chain.info()["block"]))
+        return np.stack(out), names
+
+    q15 = lambda **kw: msdr.Chain(ctx, msdr.ARITH_Q15, ch, lpq, lpq, biquad_nodes=nodes, **{"mode": orclib.AM, **kw})
+    want, names = stream(q15())
+    assert {n[:2] for n in names} == {("chain_q15mb_kernel (block tiles) + both biquad nodes", "chain_q15mb_kernel")}, names
+    for off_in, off_out in ((2, 0), (0, 2)):
+        got, names = stream(q15(), off_in, off_out)
+        assert {n[0] for n in names} == {"chain_q15mf_kernel"}, names
+        assert np.array_equal(got, want), (off_in, off_out)
+    # (2) SYNCAM under the PLL: the streaming kernel hands I and Q to the PLL kernel; the same with the block kernels switched off altogether
+    modes = (np.arange(ch) % 2).astype(np.int32)                   # SYNCAM, AM, ...
+    got, names = stream(q15(modes=modes, flags=msdr.CHAIN_SYNCAM_PLL))
+    assert {n[0] for n in names} == {"chain_q15mf_kernel"}, names
+    monkeypatch.setenv("MSDR_NO_BLOCK", "1")
+    ref, _ = stream(q15(modes=modes, flags=msdr.CHAIN_SYNCAM_PLL))
+    monkeypatch.delenv("MSDR_NO_BLOCK")
+    assert np.array_equal(got, ref)
+    # (3) the LMS filter on: block tiles, the node kernel behind the filter, on a table with three or more waves per workgroup; the same
+    # samples as from a chain that never lays its table out for the node phase (MSDR_Q15_NO_FUSE=1: one wave does for 16 channels)
+    lms = q15()
+    lms.set_anr(None, 1)
+    got, names = stream(lms)
+    assert {n[:2] for n in names} == {("chain_q15mb_kernel (channel-batched block tiles)", "biquad_teensy_blk_kernel")}, names
+    assert all(n[2] >= 192 for n in names), names
+    monkeypatch.setenv("MSDR_Q15_NO_FUSE", "1")
+    plain = q15()
+    monkeypatch.delenv("MSDR_Q15_NO_FUSE")
+    plain.set_anr(None, 1)
+    ref, names = stream(plain)
+    assert {n[:2] for n in names} == {("chain_q15mb_kernel (channel-batched block tiles)", "biquad_teensy_blk_kernel")} and all(n[2] == 64 for n in names), names
+    assert np.array_equal(got, ref)
+    # fp32: a misaligned buffer takes the wave-stream kernel, which agrees with the block kernel to the module's tolerance
+    lp = _lowpass(102)
+    f32 = lambda: msdr.Chain(ctx, msdr.ARITH_F32, ch, lp, lp, mixer=msdr.MIXER_FS4, mode=orclib.AM, biquad_coeffs=_f32_biquads(orc, 2))
+    want, names = stream(f32(), dtype=np.float32)
+    assert all(n[0].startswith("chain_mfb_kernel") for n in names), names
+    for off_in, off_out in ((2, 0), (0, 4)):
+        got, names = stream(f32(), off_in, off_out, np.float32)
+        assert all(n[0].startswith("chain_mfw_kernel") or n[0].startswith("chain_amtr_kernel") for n in names), names
+        assert rel_rms(got.ravel(), want.ravel()) < TOL, (off_in, off_out)

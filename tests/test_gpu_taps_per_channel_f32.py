@@ -519,3 +519,24 @@ def test_fir_stage_per_channel(ctx, orc, ntaps):
         for c in range(ch):
             assert rel_rms(y[c], orc.fir_f32_blocks(rows[2], x[c, :B], B)) <= 1e-6, c
         fir.close()
+
+
+def test_per_channel_rows_take_a_chain_off_the_folded_kernel(ctx, orc):
+    """Per-channel coefficients come before the oscillator fold in msdr_chain_process: a chain on chain_fold_kernel<4> (Fs/4, MSDR_CHAIN_NO_MFMA)
+    runs chain_f32pc_kernel from the first call after the rows arrive -- the same samples as from a chain that never folded (no cascade: the
+    raw history is all the state there is)."""
+    rng = np.random.default_rng(77)
+    ch = 5
+    taps = bank_taps(ch)
+    x = signal(rng, ch, 3 * B + 40)
+    outs = []
+    for flags in (msdr.CHAIN_NO_MFMA, 0):
+        chain = msdr.Chain(ctx, msdr.ARITH_F32, ch, taps[0], taps[0], mode=LSB, flags=flags)
+        run(ctx, chain, x[:, :B])
+        if flags:
+            assert chain.info()["kernel"] == "chain_fold_kernel<4>", chain.info()
+        chain.set_taps_channels_f32(0, taps)
+        outs.append(run(ctx, chain, x[:, B:]))
+        assert chain.info()["kernel"].startswith(PC) and chain.info()["flavour"] & msdr.FLAVOUR_TAPS_PC, chain.info()
+        chain.close()
+    assert np.array_equal(outs[0], outs[1])
