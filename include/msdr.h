@@ -193,12 +193,29 @@ const char *msdr_fir_f32_kernel_name(msdr_fir_f32 *S);      /* the kernel msdr_f
  * one scale for samples below that magnitude (saves the per-tile maximum; samples above it would overflow); 0 = automatic again.
  * No counterpart in CMSIS (arm_fir_f32 is plain fp32).
  * Guaranteed precision (arm_fir_f32 has none that depends on the input; this does, and here is the bound).  Let Mw be the largest
- * magnitude among the samples a tile's outputs can meet (its 1024 samples and the numTaps - 1 before them).  Every sample x of that
- * window enters the products with an error of at most max(2^-21 |x|, 2^-39 Mw), every tap h with at most max(2^-21 |h|, 2^-38 hmax),
- * the sums are fp32.  So a sample keeps its full 22 bits down to 2^-18 of Mw; below that it keeps 22 - (R - 18) bits at 2^-R of Mw
- * (19 bits one part in a million below the tile's peak).  An isolated spike therefore costs the quiet outputs of ITS OWN tile window a
- * relative 2^-19 ... 2^-15 for spikes 10^6 ... 10^7 times the quiet level, never the stretches before or after that window
- * (tests/test_gpu_stages.py: test_fir_f32_isolated_spike, test_fir_f32_matrix_core_input_ranges). */
+ * magnitude in the SCALE WINDOW of a tile (tiles are the 1024-output pieces of one call, counted from its first sample; the numTaps - 1
+ * samples before a call are the carried history):
+ *   16 .. 289 taps (fir_f32tq_kernel): the tile's 1024 samples and the numTaps - 1 before them, rounded up to a multiple of 32;
+ *   290 .. 513 taps (fir_f32mf_kernel): the tile's 1024 samples and the whole tile before it (at most: the first tile of one of the
+ *     kernel's time segments looks back as far as the line above says);
+ *   a pinned range: max_abs rounded up to a power of two, for every tile.
+ * Every sample x of a tile's outputs enters the products with an error of at most max(2^-21 |x|, 2^-39 Mw), every tap h with at most
+ * max(2^-21 |h|, 2^-38 hmax), the sums are fp32.  (290 .. 513 taps: a sample of the numTaps - 1 before the tile keeps the pieces it was
+ * given under the previous tile's scale while the scale grows finer by at most 2^12 -- then read 2^-27 Mw for it -- or coarser by at
+ * most 2^24 -- its two pieces are each rounded once more, to the new scale: read 2^-37 Mw --; past either it is converted again.)
+ * So a sample keeps its full 22 bits down to 2^-18 of Mw; below that it keeps 22 - (R - 18) bits at 2^-R of Mw (19 bits one part in a million below the window's peak).  An isolated spike therefore costs the quiet
+ * outputs of ITS OWN scale windows a relative 2^-19 ... 2^-15 for spikes 10^6 ... 10^7 times the quiet level, never the stretches before
+ * or after those windows; a level step costs the quiet side the windows that hold loud samples and nothing behind them.
+ * Magnitude range: the scale exponent is limited to +-100, so the bound holds for windows whose Mw lies between 2^-86 and 2^115 (filters
+ * whose largest tap lies between 2^-13 and 2^40; the outputs must fit fp32).  A window with a finite sample of 2^116 or more is lost
+ * (fp16 infinities), one whose Mw is below 2^-86 keeps fewer bits: in both cases the damage stays in the scale windows that hold such
+ * samples, of that channel.
+ * Non-finite samples: a NaN or an infinity costs its own channel the outputs of the scale windows that hold it -- more than the numTaps
+ * outputs arm_fir_f32 loses: the matrix products spread 0 x NaN, and the window's scale is spent on it --, no other channel, no other
+ * window, and not the next call once the history has passed it.  The numTaps outputs that arm_fir_f32 would make non-finite are
+ * non-finite here: a NaN is never turned into a number.
+ * (tests/fir_f32_edges.py is this paragraph as code; tests/test_gpu_fir_f32_edges.py holds every kernel of the stage to it,
+ * tests/test_gpu_stages.py: test_fir_f32_isolated_spike, test_fir_f32_matrix_core_input_ranges.) */
 int msdr_fir_f32_set_input_range(msdr_fir_f32 *S, float max_abs);
 int msdr_fir_f32_destroy(msdr_fir_f32 *S);
 
