@@ -666,7 +666,50 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   of per-channel taps / oscillator tables; F32: only with msdr_chain_set_block_kernel on), its d_if[k] are [n_inputs][n_samples], and it
  *   replays bit-exactly.
  *   Out of scope: the uniform (matrix-core) kernels, the msdr_fir_* stage instances, fp32 chains with PLL / LMS channels, and sharing one
- *   history per input row (the histories cost channels x hist_len x 2 bytes as before). */
+ *   history per input row (the histories cost channels x hist_len x 2 bytes as before).
+ * msdr_chain_set_nco_channels: a PHASE-ACCUMULATOR oscillator per channel -- tune() of receiver rx sets that receiver's local oscillator to
+ *   ANY frequency (Minimal-SDR.ino:328-368), where an oscillator table sits on multiples of fs / osc_len.  A receiver keeps one 32-bit
+ *   phase and one 32-bit step (resolution fs / 2^32); the oscillator of a sample is {osc_q ("cos"), osc_i ("sin")} = {cosq, sinq} of the
+ *   phase at that sample, as msdr_nco_q15 computes them (below), and the mixing is the table chains': Q15 ssat16((x * osc) >> 15), F32
+ *   x * in_scale * (osc / 32768).  step / phase: HOST arrays of `count` entries for channels first_channel .. first_channel + count - 1,
+ *   read during the call; phase may be NULL.  The named channels get step[k] from their next sample on.  With phase == NULL the phase
+ *   carries on (a phase-continuous retune); otherwise the next sample has phase[k].  Every filter state is kept; the samples already in the
+ *   FIR history stay mixed with the oscillator of their own time.  For step = k * 2^25 the oscillator equals the 128-entry table
+ *   round(32767 sin / cos(2 pi k n / 128)): such a chain is bit-identical to the table chain.
+ *   Generations: one call is ONE generation for the whole chain, whatever `count`; two calls with no msdr_chain_process between them count
+ *   once; up to 16 are kept, a 17th inside one history length drops the oldest.  A generation is channels x 8 bytes, freed once the history
+ *   has turned over.
+ *   The first call puts the chain, for the rest of its life, into the per-channel kernel family with this oscillator: chain_q15pcn_kernel
+ *   (Q15; PLL, LMS and node kernels behind it as before) or chain_f32pcn_kernel (F32; the cascade moves behind the kernel in CMSIS order
+ *   with its state, with that move's one refusal; MSDR_CHAIN_OUT_I16 converts last).  The tap table is filled from the shared tap sets as
+ *   the other per-channel setters fill it.  The first call must name every channel (first_channel == 0, count == channels) and is accepted
+ *   only while the FIR history is clear -- before the first msdr_chain_process, or directly after msdr_chain_reset / msdr_chain_init_fir
+ *   (a cleared history needs no generation of the old tables); otherwise MSDR_STATUS_ARGUMENT_ERROR, nothing changed.
+ *   Refused (ARGUMENT_ERROR, nothing changed): a NULL chain, a NULL step, a range past `channels`, a chain created with MSDR_MIXER_FS4, a
+ *   chain holding per-channel oscillator tables (msdr_chain_set_osc_channels), an fp32 chain created with MSDR_CHAIN_SYNCAM_PLL or with an
+ *   LMS channel on, and a filter too long for 64 KB of LDS beside the 4 KB sine table (Q15: more than 4 776 taps, no chain; F32: more than
+ *   3 584).  count == 0 does nothing.
+ *   On a chain in this mode msdr_chain_set_osc and msdr_chain_set_osc_channels are refused; msdr_chain_graph_create is refused (the time
+ *   of a call's first sample is a launch operand: a replay would repeat one phase) and a graph made earlier is refused at launch;
+ *   msdr_chain_set_anr with any channel on is refused on fp32 chains; msdr_chain_set_block_kernel[_q15] is accepted and such calls run
+ *   the unfused launches.  The bank survives msdr_chain_set_taps[_channels][_f32], set_mode, the node and cascade setters,
+ *   msdr_chain_set_input_rows (in either order) and, on Q15 chains, set_anr.  msdr_chain_init_fir keeps phases and steps;
+ *   msdr_chain_reset sets the chain's time and every phase to 0, keeps the steps and drops the pending generations.
+ *   msdr_chain_get_info().kernel names the kernel; on fp32 chains flavour carries MSDR_FLAVOUR_NCO_PC beside MSDR_FLAVOUR_TAPS_PC (plus
+ *   SEQ_CASCADE, SEGMENTED, SHARED_IF where they apply).
+ * msdr_chain_get_nco: the channel's step and the phase of its NEXT sample (either pointer may be NULL); ARGUMENT_ERROR on a chain that is
+ *   not in this mode.
+ * msdr_nco_step (host only): llround(f_hz / fs_hz * 2^32) mod 2^32; a negative frequency wraps (-6000 at 24000: 0xC0000000).
+ * msdr_nco_table (host only): T[i] = (int16) lround(32767 sin(2 pi i / 1024)), i = 0 .. 1024, T[1024] = 0.
+ * msdr_nco_q15 (host only; what the kernels compute): for each uint32 phase, i = phase >> 22, f = (phase >> 6) & 0xFFFF,
+ *   sin = T[i] + (((T[i + 1] - T[i]) * f + 32768) >> 16) (arithmetic shift), cos = sin of phase + 0x40000000 (wrapping); within 1.154 LSB
+ *   of 32767 sin, range -32767 .. 32767.  Either output may be NULL. */
+uint32_t msdr_nco_step(double f_hz, double fs_hz);
+void msdr_nco_table(int16_t table[1025]);
+void msdr_nco_q15(const uint32_t *phase, size_t count, int16_t *sin_out, int16_t *cos_out);
+int msdr_chain_set_nco_channels(msdr_chain *chain, uint32_t first_channel, uint32_t count,
+                                const uint32_t *step, const uint32_t *phase);
+int msdr_chain_get_nco(msdr_chain *chain, uint32_t channel, uint32_t *step, uint32_t *phase);
 int msdr_chain_set_taps(msdr_chain *chain, uint32_t tapset, const void *coeffs_i, const void *coeffs_q);
 int msdr_chain_set_taps_channels(msdr_chain *chain, uint32_t first_channel, uint32_t count,
                                  const q15_t *coeffs_i, const q15_t *coeffs_q);
@@ -733,6 +776,9 @@ enum { MSDR_FLAVOUR_OSC_PC = 0x20000u };
 /* And another: the demodulator kernel read its IF samples through an input map -- msdr_chain_set_input_rows with n_inputs > 0, d_if
  * [n_inputs][n_samples] (always beside MSDR_FLAVOUR_TAPS_PC). */
 enum { MSDR_FLAVOUR_SHARED_IF = 0x40000u };
+/* And another: the demodulator kernel computed every channel's oscillator from its phase accumulator -- chain_f32pcn_kernel,
+ * msdr_chain_set_nco_channels (always beside MSDR_FLAVOUR_TAPS_PC). */
+enum { MSDR_FLAVOUR_NCO_PC = 0x80000u };
 int msdr_chain_get_info(msdr_chain *chain, msdr_chain_info *info);
 /* Which kernel ran the serial recurrences (introspection for tests: tests/q15_ladder_cases.py is the table of every branch below, and
  * tests/test_gpu_q15_ladders.py holds each of them to the oracle bit for bit).  Each getter returns a static string -- the kernel's name

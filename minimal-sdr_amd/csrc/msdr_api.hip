@@ -22,6 +22,7 @@
 #include "msdr_chain_f32pc.hiph"
 #include "msdr_chain_oscpc.hiph"
 #include "msdr_block.h"
+#include "msdr_nco.h"
 #include "msdr_design.h"
 #include "msdr_cascade_state.h"
 #include "msdr_kstack.h"
@@ -2484,6 +2485,16 @@ struct msdr_chain {
     bool opc_active = false;
     void *d_osc_bank = nullptr;           // [channels][osc_len] pairs {osc_q ("cos"), osc_i ("sin")}: int2 (Q15) / float2 (F32)
     uint64_t osc_gen = 0;                 // bumped by every change of the bank: part of a HIP graph's key
+    // phase-accumulator oscillator (msdr_chain_set_nco_channels): from the first such call on, for the chain's life, the demodulator kernel is
+    // chain_q15pcn_kernel / chain_f32pcn_kernel (msdr_chain_ncopc.hiph), which read per-channel tap rows as above (pc_active is set with it) and
+    // compute channel ch's oscillator from pair ch of this bank at the chain time of each sample.  A pending generation (osc_pending, stride 1)
+    // is a copy of the whole bank.  d_osc stays what the stored shared tables say; nothing reads it in this mode.
+    bool nco_active = false;
+    uint32_t *d_nco_bank = nullptr;       // [channels] pairs {base0, step}
+    uint32_t *d_nco_tab = nullptr;        // [1024] packed sine table (msdr_nco.h)
+    std::vector<uint32_t> h_nco_base, h_nco_step;
+    uint64_t nco_T = 0;                   // samples processed since creation / msdr_chain_reset (every chain counts them)
+    bool hist_clear = true;               // no sample has entered the FIR history since creation / msdr_chain_reset / msdr_chain_init_fir
     // msdr_chain_set_block_kernel (F32): a block-cadence call of the chain in per-channel mode runs chain_f32pcb_kernel (msdr_chain_f32pcb.hiph) --
     // demodulator, CMSIS-order cascade, int16 conversion and the next history in ONE launch -- where msdr_chain_process finds the conditions met;
     // every other call runs the unfused launches over the same history, table position and cascade state.  Off by default.
@@ -2534,6 +2545,9 @@ static const char kPcboKernelName[] = "chain_f32pcb_kernel (per-channel taps and
 // ... and of a Q15 chain on its block kernel (msdr_chain_set_block_kernel_q15)
 static const char kQpcbKernelName[] = "chain_q15pcb_kernel (per-channel taps, one launch per block)";
 static const char kQpcboKernelName[] = "chain_q15pcb_kernel (per-channel taps and oscillator tables, one launch per block)";
+// ... and of the chains with the phase-accumulator oscillator (msdr_chain_set_nco_channels)
+static const char kPcnKernelName[] = "chain_q15pcn_kernel (per-channel taps, phase oscillator)";
+static const char kPcfnKernelName[] = "chain_f32pcn_kernel (per-channel taps, phase oscillator)";
 static void chain_pcf_row_from(msdr_chain *c, uint32_t ch, const float *ci, const float *cq)
 {
     float *row = c->h_pcf_taps.data() + (size_t)ch * 2 * c->pc_np;
@@ -2559,6 +2573,16 @@ static int chain_pc_upload(msdr_chain *c, uint32_t first, uint32_t count)
         return 0;
     }
     HIP_TRY(hipMemcpy(c->d_pc_taps + first * row, c->h_pc_taps.data() + first * row, count * row * sizeof(int16_t), hipMemcpyHostToDevice));
+    return 0;
+}
+
+// pairs first .. first + count - 1 of the phase-accumulator oscillator's bank to the device; the stream is drained first (a kernel in flight reads it)
+static int chain_nco_upload(msdr_chain *c, uint32_t first, uint32_t count)
+{
+    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+    std::vector<uint32_t> pairs((size_t)2 * count);
+    for (uint32_t k = 0; k < count; k++) { pairs[2 * k] = c->h_nco_base[first + k]; pairs[2 * k + 1] = c->h_nco_step[first + k]; }
+    HIP_TRY(hipMemcpy(c->d_nco_bank + (size_t)2 * first, pairs.data(), pairs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -2591,6 +2615,7 @@ static void chain_free(msdr_chain *c)
     for (auto &e : c->events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (auto &o : c->osc_pending) hipFree(o.d_tab);
     hipFree(c->d_f32_scratch); hipFree(c->d_osc_hist); hipFree(c->d_btiles); hipFree(c->d_pc_taps); hipFree(c->d_pcf_taps); hipFree(c->d_osc_bank); hipFree(c->d_in_row);
+    hipFree(c->d_nco_bank); hipFree(c->d_nco_tab);
     delete c;
 }
 
@@ -3743,7 +3768,7 @@ static ChainDecision chain_decide(msdr_chain *c, const int16_t *d_if, const void
         const bool mfw_out_aligned = (want_i16 && !mfw_i16_direct) || out_aligned;
         // msdr_chain_set_block_kernel: the whole block-cadence call of a per-channel chain in one launch (msdr_chain_f32pcb.hiph) -- where no
         // oscillator generation is pending, nothing runs behind the kernel but a CMSIS-order cascade, and one wave's LDS fits
-        if (c->pc_active && c->block_pc && block_n && !osc_pending && !d.post_active &&
+        if (c->pc_active && c->block_pc && !c->nco_active && block_n && !osc_pending && !d.post_active &&
             (!c->seq_bq || c->seq_bq->stages == 0 || c->seq_bq->sequential) && chain_f32pcb_lds((int)n_samples, c->pc_np, pc_osc_len, nullptr))
             d.path = kPathF32Pcb;
         else if (c->pc_active) d.path = kPathF32Pc;                  // per-channel taps: chain_f32pc_kernel in place of every uniform demodulator kernel
@@ -3769,7 +3794,7 @@ static ChainDecision chain_decide(msdr_chain *c, const int16_t *d_if, const void
         else if (qm) d.path = kPathQ15Mf;
         // msdr_chain_set_block_kernel_q15: the whole call of a per-channel chain in one launch (msdr_chain_q15pcb.hiph) -- where no oscillator
         // generation is pending, neither the PLL demodulator nor the LMS filter runs between the demodulator and the nodes, and one wave's LDS fits
-        else if (c->pc_active && c->block_q15 && block_n && !osc_pending && !d.pll_active && !d.anr_active &&
+        else if (c->pc_active && c->block_q15 && !c->nco_active && block_n && !osc_pending && !d.pll_active && !d.anr_active &&
                  chain_q15pcb_lds((int)n_samples, c->pc_np, pc_osc_len, nullptr))
             d.path = kPathQ15Pcb;
         else if (c->pc_active) d.path = kPathQ15Pc;                  // per-channel taps: chain_q15pc_kernel in place of every uniform demodulator kernel
@@ -4035,6 +4060,7 @@ static void pc_params(Q &q, const msdr_chain *c, const ChainParams &p)
     memset(&q, 0, sizeof q);
     q.x = p.x; q.hist_in = p.hist_in; q.n = (decltype(q.n))p.n; q.channels = p.channels; q.hist_len = p.hist_len; q.np = c->pc_np; q.chan_mode = c->d_mode;
     q.osc = c->opc_active ? c->d_osc_bank : (const void *)c->d_osc;        // per-channel oscillator tables: the bank in place of the shared table
+    if (c->nco_active) q.osc = c->d_nco_bank;                              // ... phase-accumulator oscillator: the bank of {base0, step}
     q.osc_len = p.osc_len; q.phase0 = p.phase0; q.in_row = c->n_inputs ? c->d_in_row : nullptr;
 }
 static void pc_geometry_of(const PcLaunch &geo, ChainLaunch &r)
@@ -4065,11 +4091,16 @@ static int chain_launch_f32pcb(msdr_chain *c, const ChainDecision &, const Chain
 
 static int chain_launch_f32pc(msdr_chain *c, const ChainDecision &, const ChainParams &p, ChainLaunch &r)
 {
-    PcfParams q;
+    PcfnParams q;          // (PcfParams and the phase-accumulator oscillator's two operands)
     pc_params(q, c, p);
     q.out = (float *)p.out; q.taps = c->d_pcf_taps; q.mixer = c->mixer; q.in_scale = c->in_scale; q.osc_hist = p.osc_hist;
     PcLaunch geo;
-    if (c->opc_active) {
+    if (c->nco_active) {
+        q.sin_tab = c->d_nco_tab; q.t0 = (unsigned)c->nco_T;
+        if (launch_chain_f32pcn(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, q, &geo) != hipSuccess)
+            return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pcn_kernel launch failed");
+        r.kname = kPcfnKernelName; r.flavour |= MSDR_FLAVOUR_NCO_PC;
+    } else if (c->opc_active) {
         if (launch_chain_f32pco(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, q, &geo) != hipSuccess)
             return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pco_kernel launch failed");
         r.kname = kPcfoKernelName; r.flavour |= MSDR_FLAVOUR_OSC_PC;
@@ -4245,11 +4276,16 @@ static int chain_launch_q15pcb(msdr_chain *c, const ChainDecision &, const Chain
 
 static int chain_launch_q15pc(msdr_chain *c, const ChainDecision &, const ChainParams &p, ChainLaunch &r)
 {
-    PcParams q;
+    PcnParams q;          // (PcParams and the phase-accumulator oscillator's two operands)
     pc_params(q, c, p);
     q.out = (short *)p.out; q.taps = c->d_pc_taps; q.mixer = c->mixer; q.sqrt_kind = c->sqrt_kind; q.syncam_q = p.syncam_q; q.osc_hist = p.osc_hist;
     PcLaunch geo;
-    if (c->opc_active) {
+    if (c->nco_active) {
+        q.sin_tab = c->d_nco_tab; q.t0 = (unsigned)c->nco_T;
+        if (launch_chain_q15pcn(c->ctx->stream, c->ctx->num_cus, q, &geo) != hipSuccess)
+            return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pcn_kernel launch failed");
+        r.kname = kPcnKernelName;
+    } else if (c->opc_active) {
         if (launch_chain_q15pco(c->ctx->stream, c->ctx->num_cus, q, &geo) != hipSuccess)
             return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pco_kernel launch failed");
         r.kname = "chain_q15pco_kernel (per-channel taps and oscillator tables)";
@@ -4405,6 +4441,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     }
     c->cur ^= 1; c->gen++;
     c->phase = (c->phase + (long long)(n_samples % c->osc_len)) % c->osc_len;
+    c->nco_T += n_samples; c->hist_clear = false;
     if (c->force_generic) {
         for (auto &o : c->osc_pending) o.elapsed += (long long)n_samples;
         if (c->osc_pending.empty() || c->osc_pending.back().elapsed >= (long long)c->hist_len)
@@ -4478,6 +4515,7 @@ extern "C" int msdr_chain_graph_create(msdr_chain *c, uint32_t ticks, const int1
     *out = nullptr;
     if (!c || !d_if || !d_audio) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
     if (int rc = bind(c->ctx)) return rc;
+    if (c->nco_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "a chain with the phase-accumulator oscillator is not capturable (the time of a call's first sample is a launch operand: a replay would repeat one phase)");
     if (ticks < 2 || (ticks & 1u) || ticks > 1024) return fail(MSDR_STATUS_ARGUMENT_ERROR, "a chain graph holds an even number of calls, 2 .. 1024 (the state buffers alternate from call to call)");
     for (uint32_t k = 0; k < ticks; k++) if (!d_if[k] || !d_audio[k]) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null buffer for call %u", k);
     // 1. preparation: every table / cache a call of this shape needs, built outside the capture (uploads and synchronisations are not
@@ -4490,7 +4528,7 @@ extern "C" int msdr_chain_graph_create(msdr_chain *c, uint32_t ticks, const int1
     if (rc) { c->timing = timing; return rc; }
     HIP_TRY(hipStreamSynchronize(c->ctx->stream));
     // 2. capture: the launches of `ticks` calls.  The host's bookkeeping runs with them (an even number of flips: back where it was).
-    const int cur0 = c->cur; const uint64_t gen0 = c->gen; const long long phase0 = c->phase;
+    const int cur0 = c->cur; const uint64_t gen0 = c->gen, T0 = c->nco_T; const long long phase0 = c->phase; const bool clear0 = c->hist_clear;
     float *const st0 = c->d_bq_state, *const st1 = c->d_bq_state_alt;
     msdr_chain_graph *g = new (std::nothrow) msdr_chain_graph();
     if (!g) { c->timing = timing; return fail(MSDR_STATUS_OUT_OF_MEMORY, "host allocation failed"); }
@@ -4502,6 +4540,7 @@ extern "C" int msdr_chain_graph_create(msdr_chain *c, uint32_t ticks, const int1
     const hipError_t ee = hipStreamEndCapture(c->ctx->stream, &g->graph);
     c->timing = timing;
     c->cur = cur0; c->gen = gen0; c->phase = phase0; c->d_bq_state = st0; c->d_bq_state_alt = st1;        // (nothing ran: the stream is where it was)
+    c->nco_T = T0; c->hist_clear = clear0;
     if (rc || ee != hipSuccess || !g->graph) {
         if (g->graph) hipGraphDestroy(g->graph);
         delete g;
@@ -4521,6 +4560,7 @@ extern "C" int msdr_chain_graph_launch(msdr_chain_graph *g)
     if (!g || !g->c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null graph");
     msdr_chain *c = g->c;
     if (int rc = bind(c->ctx)) return rc;
+    if (c->nco_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the chain got a phase-accumulator oscillator since this graph was made (its captured launches mix with tables): graphs are not for such chains");
     msdr_chain_graph now;
     chain_graph_key(c, &now);
     if (now.k_hist != g->k_hist || now.k_state != g->k_state || now.k_tab != g->k_tab || now.k_tiles != g->k_tiles || now.k_cur != g->k_cur || now.k_mode_gen != g->k_mode_gen ||
@@ -4551,6 +4591,7 @@ extern "C" int msdr_chain_graph_launch(msdr_chain_graph *g)
     }
     HIP_TRY(hipGraphLaunch(g->exec, c->ctx->stream));
     c->gen += g->ticks;                                     // (an even number of calls: buffers, table position and caches stay as they are)
+    c->nco_T += (uint64_t)g->ticks * g->n; c->hist_clear = false;
     return 0;
 }
 
@@ -4591,6 +4632,11 @@ extern "C" int msdr_chain_reset(msdr_chain *c)
         c->osc_pending.clear(); c->force_generic = false;
     }
     c->phase = 0; c->gen++; c->rebuild_gen++;
+    c->nco_T = 0; c->hist_clear = true;
+    if (c->nco_active) {          // time and every phase to 0; the steps stay
+        std::fill(c->h_nco_base.begin(), c->h_nco_base.end(), 0u);
+        if (int rc = chain_nco_upload(c, 0, c->channels)) return rc;
+    }
     return 0;
 }
 
@@ -4669,6 +4715,7 @@ extern "C" int msdr_chain_init_fir(msdr_chain *c)
     const size_t hb = (size_t)c->channels * c->hist_len * sizeof(int16_t);
     HIP_TRY(hipMemsetAsync(c->d_hist[0], 0, hb, c->ctx->stream));
     HIP_TRY(hipMemsetAsync(c->d_hist[1], 0, hb, c->ctx->stream));
+    c->hist_clear = true;
     return 0;
 }
 
@@ -4792,6 +4839,9 @@ static int chain_rebuild(msdr_chain *c, const ChainCfgStore &edited, void **stea
     n->block_pc = c->block_pc; n->block_epoch = c->block_epoch;          // (msdr_chain_set_block_kernel holds for the chain's life)
     n->block_q15 = c->block_q15; n->block_q15_epoch = c->block_q15_epoch;          // (and so does msdr_chain_set_block_kernel_q15)
     n->n_inputs = c->n_inputs; std::swap(n->d_in_row, c->d_in_row); n->in_row_epoch = c->in_row_epoch;       // (the input map too)
+    // ... the phase-accumulator oscillator's bank (its pending generations went over with osc_pending above) and the chain's time
+    n->nco_active = c->nco_active; std::swap(n->d_nco_bank, c->d_nco_bank); std::swap(n->d_nco_tab, c->d_nco_tab);
+    n->h_nco_base.swap(c->h_nco_base); n->h_nco_step.swap(c->h_nco_step); n->nco_T = c->nco_T; n->hist_clear = c->hist_clear;
     std::swap(*c, *n);
     if (steal_osc) { *steal_osc = n->d_osc; n->d_osc = nullptr; }
     chain_free(n);
@@ -5089,6 +5139,7 @@ extern "C" int msdr_chain_set_osc_channels(msdr_chain *c, uint32_t first_channel
     if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
     if (int rc = bind(c->ctx)) return rc;
     if (c->mixer != MSDR_MIXER_NCO) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has the Fs/4 mixer: no oscillator tables (Minimal-SDR.ino:546-558)");
+    if (c->nco_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has the phase-accumulator oscillator (msdr_chain_set_nco_channels): no oscillator tables; nothing changed");
     if (count == 0) return 0;
     if (!osc_i || !osc_q) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null oscillator array");
     if (first_channel >= c->channels || count > c->channels - first_channel)
@@ -5116,6 +5167,7 @@ extern "C" int msdr_chain_set_osc(msdr_chain *c, const void *osc_i, const void *
     if (!c || !osc_i || !osc_q) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
     if (int rc = bind(c->ctx)) return rc;
     if (c->mixer != MSDR_MIXER_NCO) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has the Fs/4 mixer: no oscillator tables (Minimal-SDR.ino:546-558)");
+    if (c->nco_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has the phase-accumulator oscillator (msdr_chain_set_nco_channels): no oscillator tables; nothing changed");
     if (c->opc_active) {          // per-channel oscillator tables: EVERY channel's row, one generation; the stored shared tables follow
         if (int rc = chain_osc_rows(c, 0, c->channels, osc_i, osc_q, 0)) return rc;
         const size_t nb = c->store.osc_i.size();
@@ -5128,6 +5180,108 @@ extern "C" int msdr_chain_set_osc(msdr_chain *c, const void *osc_i, const void *
     ed.osc_i.assign((const char *)osc_i, (const char *)osc_i + bytes);
     ed.osc_q.assign((const char *)osc_q, (const char *)osc_q + bytes);
     return chain_rebuild_keep_folded(c, ed, [](uint32_t) { return true; }, true);
+}
+
+// ---- phase-accumulator oscillator (msdr_nco.h) ----
+static const int16_t *nco_host_table()
+{
+    static const struct Tab { int16_t t[kNcoTabLen + 1]; Tab() { nco_table_build(t); } } tab;
+    return tab.t;
+}
+extern "C" uint32_t msdr_nco_step(double f_hz, double fs_hz) { return nco_step_of(f_hz, fs_hz); }
+extern "C" void msdr_nco_table(int16_t table[1025])
+{
+    if (table) memcpy(table, nco_host_table(), (kNcoTabLen + 1) * sizeof(int16_t));
+}
+extern "C" void msdr_nco_q15(const uint32_t *phase, size_t count, int16_t *sin_out, int16_t *cos_out)
+{
+    if (!phase) return;
+    const int16_t *T = nco_host_table();
+    for (size_t k = 0; k < count; k++) {
+        if (sin_out) sin_out[k] = (int16_t)nco_sinq(T, phase[k]);
+        if (cos_out) cos_out[k] = (int16_t)nco_cosq(T, phase[k]);
+    }
+}
+
+// tune() of ONE receiver of the bank to ANY frequency (Minimal-SDR.ino:328-368): pairs {base0, step} of the bank rewritten under the running
+// stream, ONE generation for the whole chain (a device copy of the bank, channels x 8 bytes).  The first call of a chain's life enters the
+// per-channel kernel family (chain_pc_activate) over a clear history.  Everything that can fail happens before anything changes.
+extern "C" int msdr_chain_set_nco_channels(msdr_chain *c, uint32_t first_channel, uint32_t count, const uint32_t *step, const uint32_t *phase)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (int rc = bind(c->ctx)) return rc;
+    if (c->mixer != MSDR_MIXER_NCO) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has the Fs/4 mixer: no oscillator to tune (Minimal-SDR.ino:546-558)");
+    if (c->opc_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has per-channel oscillator tables (msdr_chain_set_osc_channels): no phase-accumulator oscillator; nothing changed");
+    if (count == 0) return 0;
+    if (!step) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null step array");
+    if (first_channel >= c->channels || count > c->channels - first_channel)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "channels %u .. %llu of %u", first_channel, (unsigned long long)first_channel + count - 1, c->channels);
+    const bool f32 = c->arith == MSDR_ARITH_F32;
+    if (f32) {          // PLL / LMS channels of an fp32 chain run through an auxiliary chain that is built from the shared tables
+        if (c->f32_pll) return fail(MSDR_STATUS_ARGUMENT_ERROR, "phase-accumulator oscillator: not on an fp32 chain created with MSDR_CHAIN_SYNCAM_PLL (its PLL channels run through an auxiliary chain with the shared tables); nothing changed");
+        for (int v : c->h_anr) if (v > 0) return fail(MSDR_STATUS_ARGUMENT_ERROR, "phase-accumulator oscillator: not while an LMS channel of an fp32 chain is on (such channels run through an auxiliary chain with the shared tables); nothing changed");
+    }
+    const bool first_call = !c->nco_active;
+    if (first_call) {
+        if (first_channel != 0 || count != c->channels)
+            return fail(MSDR_STATUS_ARGUMENT_ERROR, "phase-accumulator oscillator: the first call names every channel (first_channel 0, count %u); nothing changed", c->channels);
+        if (!c->hist_clear)
+            return fail(MSDR_STATUS_ARGUMENT_ERROR, "phase-accumulator oscillator: the first call needs a clear FIR history (before the first msdr_chain_process, or directly after msdr_chain_reset / msdr_chain_init_fir); nothing changed");
+        const int np = f32 ? f32pc_np((int)c->ntaps) : pc_np((int)c->ntaps), cap = chain_pcn_max_taps(f32);
+        if (np > cap)          // (one wave's windows and tap rows must fit the kernel's LDS beside the sine table)
+            return fail(MSDR_STATUS_ARGUMENT_ERROR, "phase-accumulator oscillator: beside the sine table the kernel holds filters of up to %d taps (this chain has %u); nothing changed", cap, c->ntaps);
+    }
+    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+    const size_t bank_bytes = (size_t)c->channels * 2 * sizeof(uint32_t);
+    uint32_t *bank = nullptr, *tab = nullptr;
+    void *snap = nullptr;
+    if (first_call) {
+        uint32_t packed[kNcoTabLen];
+        nco_pack(nco_host_table(), packed);
+        if (hipMalloc((void **)&bank, bank_bytes) != hipSuccess || hipMalloc((void **)&tab, sizeof packed) != hipSuccess ||
+            hipMemcpy(tab, packed, sizeof packed, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipGetLastError(); hipFree(bank); hipFree(tab);
+            return fail(MSDR_STATUS_OUT_OF_MEMORY, "device allocation of the oscillator bank failed");
+        }
+    }
+    // a bank that was replaced before any sample arrived under it mixed nothing: it is not a generation; nor does a clear history hold a sample of it
+    const bool new_gen = !first_call && !c->hist_clear && (c->osc_pending.empty() || c->osc_pending.back().elapsed != 0);
+    if (new_gen && (hipMalloc(&snap, bank_bytes) != hipSuccess || hipMemcpy(snap, c->d_nco_bank, bank_bytes, hipMemcpyDeviceToDevice) != hipSuccess)) {
+        (void)hipGetLastError(); hipFree(snap);
+        return fail(MSDR_STATUS_OUT_OF_MEMORY, "device copy of the oscillator bank in force (one pending generation: channels x 8 bytes) failed");
+    }
+    if (first_call) {
+        const bool taps_first = !c->pc_active;
+        if (int rc = chain_pc_activate(c)) { hipFree(bank); hipFree(tab); return rc; }
+        if (taps_first) if (int rc = chain_pc_upload(c, 0, c->channels)) { hipFree(bank); hipFree(tab); return rc; }
+        // generations of the shared tables (msdr_chain_set_osc): the cleared history holds no sample of theirs
+        if (!c->osc_pending.empty() || c->force_generic) if (int rc = chain_leave_generic(c)) { hipFree(bank); hipFree(tab); return rc; }
+        c->d_nco_bank = bank; c->d_nco_tab = tab;
+        c->h_nco_base.assign(c->channels, 0u); c->h_nco_step.assign(c->channels, 0u);
+        c->nco_active = true;
+    }
+    for (uint32_t k = 0; k < count; k++) {
+        const uint32_t ch = first_channel + k;
+        c->h_nco_base[ch] = phase ? nco_base_for(phase[k], step[k], c->nco_T) : nco_rebase(c->h_nco_base[ch], c->nco_T, c->h_nco_step[ch], step[k]);
+        c->h_nco_step[ch] = step[k];
+    }
+    if (int rc = chain_nco_upload(c, first_channel, count)) { hipFree(snap); return rc; }
+    if (new_gen) {
+        if (c->osc_pending.size() >= (size_t)kOscHistMax) { hipFree(c->osc_pending.front().d_tab); c->osc_pending.erase(c->osc_pending.begin()); }
+        c->osc_pending.push_back(msdr_chain::OscPending{snap, 0, 1});
+    }
+    if (!c->osc_pending.empty()) c->force_generic = true;          // (generations are pending: msdr_chain_process counts them down and frees them, chain_leave_generic)
+    return 0;
+}
+
+extern "C" int msdr_chain_get_nco(msdr_chain *c, uint32_t channel, uint32_t *step, uint32_t *phase)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (!c->nco_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has no phase-accumulator oscillator (msdr_chain_set_nco_channels)");
+    if (channel >= c->channels) return fail(MSDR_STATUS_ARGUMENT_ERROR, "channel %u of %u", channel, c->channels);
+    if (step) *step = c->h_nco_step[channel];
+    if (phase) *phase = nco_phase(c->h_nco_base[channel], c->h_nco_step[channel], (uint32_t)c->nco_T);
+    return 0;
 }
 
 extern "C" int msdr_chain_set_node_coefficients(msdr_chain *c, uint32_t node, uint32_t stage, const int32_t coef[5])
@@ -5290,11 +5444,12 @@ extern "C" int msdr_chain_set_anr(msdr_chain *c, const int32_t *anr_on, int32_t 
     if (c->arith != MSDR_ARITH_Q15) {
         // fp32 chain: the float flavour of the filter, between demodulator and cascade (chain_post_run)
         if (c->seq_bq && !c->h_bq_stages) return fail(MSDR_STATUS_ARGUMENT_ERROR, "internal: cascade coefficients not kept");
-        if ((c->seq_bq && c->seq_bq->per_channel) || c->opc_active || c->n_inputs) {      // (LMS channels run a post cascade with the chain's uniform coefficients, behind an auxiliary chain with the shared oscillator tables)
+        if ((c->seq_bq && c->seq_bq->per_channel) || c->opc_active || c->nco_active || c->n_inputs) {      // (LMS channels run a post cascade with the chain's uniform coefficients, behind an auxiliary chain with the shared oscillator tables)
             bool any = anr_on ? false : anr_on_all > 0;
             if (anr_on) for (uint32_t ch = 0; ch < c->channels; ch++) any = any || anr_on[ch] > 0;
             if (any && c->n_inputs) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has an input map (msdr_chain_set_input_rows): no LMS channels (they run through an auxiliary chain that gathers its rows from d_if by channel); nothing changed");
             if (any && c->opc_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has per-channel oscillator tables: no LMS channels (they run through an auxiliary chain with the shared tables); nothing changed");
+            if (any && c->nco_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has the phase-accumulator oscillator: no LMS channels (they run through an auxiliary chain with the shared tables); nothing changed");
             if (any) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has per-channel cascade coefficients: no LMS channels (they run a post cascade of their own); nothing changed");
         }
         c->h_anr.assign(c->channels, anr_on ? 0 : (int)anr_on_all);

@@ -9,6 +9,7 @@
 //   msdr_chain_f32pc.hip   the fp32 chain / the arm_fir_f32 stage with per-channel FIR coefficients: chain_f32pc_kernel
 //   msdr_biquad_df1_pc.hip arm_biquad_cascade_df1_f32 in CMSIS order with per-channel coefficients: biquad_df1_seq_pc_kernel
 //   msdr_chain_oscpc.hip   the two chains above with per-channel oscillator tables: chain_q15pco_kernel, chain_f32pco_kernel
+//   msdr_chain_ncopc.hip   the same two with a per-channel phase-accumulator oscillator: chain_q15pcn_kernel, chain_f32pcn_kernel
 //   msdr_chain_f32pcb.hip  the fp32 chain with per-channel settings at block cadence, one launch per call: chain_f32pcb_kernel
 //   msdr_chain_q15pcb.hip  the Q15 chain with per-channel settings at block cadence, one launch per call: chain_q15pcb_kernel
 // Host-side geometry helpers (LDS sizes, table formats) live with the kernels' headers; the launch geometry of the per-receiver chain kernels
@@ -61,6 +62,14 @@ hipError_t launch_chain_f32pc(hipStream_t stream, bool fir_only, int num_cus, in
 // p.osc is the bank [channels][osc_len] of pairs, p.mixer MSDR_MIXER_NCO; geometry chosen as above, with the row's LDS counted in.
 hipError_t launch_chain_q15pco(hipStream_t stream, int num_cus, PcParams p, PcLaunch *geo);
 hipError_t launch_chain_f32pco(hipStream_t stream, int num_cus, int time_segments, PcfParams p, PcLaunch *geo);
+// ---- msdr_chain_ncopc.hip ----
+// chain_q15pcn_kernel<CPW> / chain_f32pcn_kernel<CPW> (msdr_chain_ncopc.hiph): the two chain kernels above with a phase-accumulator oscillator.
+// p.osc is the bank [channels] of pairs {base0, step}, p.sin_tab the packed sine table (msdr_nco.h), p.t0 the chain time of the call's first
+// sample, p.mixer MSDR_MIXER_NCO; geometry chosen as above, with the table's LDS (once per workgroup) counted in.  chain_pcn_max_taps: the
+// longest filter (taps padded as the kernel pads them) one wave with one channel holds beside the table.
+int chain_pcn_max_taps(bool f32);
+hipError_t launch_chain_q15pcn(hipStream_t stream, int num_cus, PcnParams p, PcLaunch *geo);
+hipError_t launch_chain_f32pcn(hipStream_t stream, int num_cus, int time_segments, PcfnParams p, PcLaunch *geo);
 // ---- msdr_biquad_df1_pc.hip ----
 // biquad_df1_seq_pc_kernel<S, SEG> (msdr_biquad_df1_pc.hiph): stages = S = 1 .. 4 sections in CMSIS order on data [channels][n] (y may be x), every
 // channel with the 5 S coefficients of its own row of tab ([channels][20] floats).  nseg = 1: state_in may be state_out, seg_len / warm / scratch

@@ -162,6 +162,18 @@ struct PcfParams {
                                // (chains only: the FIR stage leaves it null)
 };
 
+// chain_q15pcn_kernel / chain_f32pcn_kernel (msdr_chain_ncopc.hiph): the two blocks above with the phase-accumulator oscillator's operands.
+// `osc` is the bank [channels] of pairs {base0, step} (uint2), osc_len and phase0 are not read; a pending generation (osc_hist) is a copy
+// of the whole bank, stride 1.
+struct PcnParams : PcParams {
+    const unsigned *sin_tab;   // [1024] packed sine table (msdr_nco.h: nco_pack), copied to LDS once per workgroup
+    unsigned t0;               // chain time of sample 0 of this call: the low 32 bits of the sample count since msdr_chain_reset
+};
+struct PcfnParams : PcfParams {
+    const unsigned *sin_tab;
+    unsigned t0;
+};
+
 // chain_f32pcb_kernel (msdr_chain_f32pcb.hiph): a whole block-cadence call of the fp32 chain with per-channel settings in one launch
 struct PcbParams {
     const int16_t *x;          // [channels][n] IF samples

@@ -345,6 +345,19 @@ public:
     {
         return chain ? msdr_chain_set_osc_channels(chain, channel, 1, osc_i, osc_q) : MSDR_STATUS_ARGUMENT_ERROR;
     }
+    // phase-accumulator oscillators for the whole bank (msdr_chain_set_nco_channels): step[c] = msdr_nco_step(f, fs) of receiver c, phase[c] the
+    // phase of its next sample (nullptr: the phases carry on).  The first call of the node's life, before the first tick or directly after init_FIR()
+    int setNco(const uint32_t *step, const uint32_t *phase = nullptr)
+    {
+        return chain ? msdr_chain_set_nco_channels(chain, 0, AudioGPU.channels(), step, phase) : MSDR_STATUS_ARGUMENT_ERROR;
+    }
+    // tune() of receiver `channel` (Minimal-SDR.ino:328-368) to ANY frequency: that receiver's step and nobody else's, phase-continuous (after setNco)
+    int tuneChannel(uint32_t channel, double f_hz, double fs_hz = 24000.0)
+    {
+        if (!chain || !(fs_hz > 0.0) || !(f_hz == f_hz)) return MSDR_STATUS_ARGUMENT_ERROR;
+        const uint32_t step = msdr_nco_step(f_hz, fs_hz);
+        return msdr_chain_set_nco_channels(chain, channel, 1, &step, nullptr);
+    }
     // one queue_adc feeds the bank (msdr_chain_set_input_rows): receiver c hears row rows[c] of the incoming block.  The block stays
     // [AudioGPU.channels()][AUDIO_BLOCK_SAMPLES]; with a map in force the node reads only its first n_inputs rows (so n_inputs <= channels()).
     // n_inputs == 0: every receiver hears its own row again

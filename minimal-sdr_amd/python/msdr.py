@@ -32,6 +32,7 @@ FLAVOUR_TAPS_PC = 0x8000
 FLAVOUR_CASCADE_PC = 0x10000
 FLAVOUR_OSC_PC = 0x20000
 FLAVOUR_SHARED_IF = 0x40000
+FLAVOUR_NCO_PC = 0x80000
 FE_DCBLOCK, FE_AMP, FE_AGC, FE_ALL = 1, 2, 4, 7
 
 STATUS_ARGUMENT_ERROR, STATUS_LENGTH_ERROR, STATUS_NO_DEVICE = -1, -2, -100
@@ -105,10 +106,19 @@ def load_library(path=None):
                        ("msdr_chain_set_block_kernel", [_p, C.c_int]),
                        ("msdr_chain_set_block_kernel_q15", [_p, C.c_int]),
                        ("msdr_chain_set_input_rows", [_p, C.c_uint32, _p]),
+                       ("msdr_chain_set_nco_channels", [_p, C.c_uint32, C.c_uint32, _p, _p]),
+                       ("msdr_chain_get_nco", [_p, C.c_uint32, _p, _p]),
+                       ("msdr_nco_step", [C.c_double, C.c_double]),
+                       ("msdr_nco_table", [_p]),
+                       ("msdr_nco_q15", [_p, C.c_size_t, _p, _p]),
                        ("msdr_chain_get_fir_history", [_p, C.c_uint32, _p, C.c_uint32, _p]),
                        ("msdr_chain_get_cmsis_state", [_p, C.c_uint32, _p])):
             if hasattr(_lib, n):
                 getattr(_lib, n).argtypes = sig
+        if hasattr(_lib, "msdr_nco_step"):
+            _lib.msdr_nco_step.restype = C.c_uint32
+            _lib.msdr_nco_table.restype = None
+            _lib.msdr_nco_q15.restype = None
         _lib.msdr_chain_set_biquad_coeffs.argtypes = [_p, _p]
         _lib.msdr_malloc.argtypes = [_p, C.c_size_t, _p]
         _lib.msdr_free.argtypes = [_p, _p]
@@ -524,6 +534,40 @@ def _input_rows(what, rows, channels, n_inputs):
     return np.ascontiguousarray(r, np.uint32), int(n_inputs)
 
 
+def _nco_words(what, a, count):
+    """a one-dimensional array of uint32 words (steps, phases); count: the length it must have, or None"""
+    t = np.asarray(a)
+    if t.dtype.kind not in "iu":
+        raise ValueError("%s: steps and phases are unsigned 32-bit integers, dtype %s given" % (what, t.dtype))
+    if t.ndim != 1 or t.size == 0:
+        raise ValueError("%s: one word per channel, shape %s given" % (what, (t.shape,)))
+    if count is not None and t.size != count:
+        raise ValueError("%s: %d phases for %d steps" % (what, t.size, count))
+    if t.min() < 0 or t.max() > 0xFFFFFFFF:
+        raise ValueError("%s: a word outside uint32" % what)
+    return np.ascontiguousarray(t, np.uint32)
+
+
+def nco_step(f_hz, fs_hz=24000.0):
+    """msdr_nco_step: llround(f / fs * 2^32) mod 2^32 -- the step of a phase-accumulator oscillator at f_hz (negative wraps).  Host only."""
+    return int(load_library().msdr_nco_step(float(f_hz), float(fs_hz)))
+
+
+def nco_table():
+    """msdr_nco_table: the 1025-entry sine table T[i] = lround(32767 sin(2 pi i / 1024)) the oscillator interpolates in.  Host only."""
+    t = np.zeros(1025, np.int16)
+    load_library().msdr_nco_table(_hp(t))
+    return t
+
+
+def nco_q15(phases):
+    """msdr_nco_q15: (sin, cos) as int16 arrays for uint32 phases, exactly what the kernels compute.  Host only."""
+    ph = np.ascontiguousarray(_nco_words("nco_q15", np.asarray(phases).reshape(-1), None))
+    s, c = np.zeros(ph.size, np.int16), np.zeros(ph.size, np.int16)
+    load_library().msdr_nco_q15(_hp(ph), C.c_size_t(ph.size), _hp(s), _hp(c))
+    return s, c
+
+
 def _kernel_name(f, h):
     f.restype = C.c_char_p
     f.argtypes = [_p]
@@ -841,6 +885,21 @@ class Chain(_Instance):
         if oi.shape != oq.shape:
             raise ValueError("set_osc_channels: osc_i %s and osc_q %s differ in shape" % ((oi.shape,), (oq.shape,)))
         _ck(self.ctx.lib.msdr_chain_set_osc_channels(self.h, C.c_uint32(first_channel), C.c_uint32(oi.shape[0]), _hp(oi), _hp(oq)))
+
+    def set_nco_channels(self, first_channel, steps, phases=None):
+        """channel first_channel + i gets a phase-accumulator oscillator with step steps[i] (uint32 [count]; nco_step(f, fs)) from its next
+        sample on: tune() of ONE receiver to ANY frequency.  phases = None: the phase carries on (a phase-continuous retune); otherwise the next
+        sample has phase phases[i] (uint32 [count]).  Every state kept; chain_q15pcn_kernel / chain_f32pcn_kernel from the first call on, which
+        names every channel over a clear history."""
+        st = _nco_words("set_nco_channels", steps, None)
+        ph = None if phases is None else _nco_words("set_nco_channels", phases, st.size)
+        _ck(self.ctx.lib.msdr_chain_set_nco_channels(self.h, C.c_uint32(first_channel), C.c_uint32(st.size), _hp(st), _hp(ph)))
+
+    def nco(self, channel):
+        """(step, phase of the NEXT sample) of `channel`'s phase-accumulator oscillator (msdr_chain_get_nco)"""
+        st, ph = C.c_uint32(0), C.c_uint32(0)
+        _ck(self.ctx.lib.msdr_chain_get_nco(self.h, C.c_uint32(channel), C.byref(st), C.byref(ph)))
+        return st.value, ph.value
 
     def set_block_kernel(self, on):
         """F32: a block-cadence call of a chain in per-channel mode as ONE launch (chain_f32pcb_kernel: demodulator, CMSIS-order cascade, int16
