@@ -699,6 +699,35 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   SEQ_CASCADE, SEGMENTED, SHARED_IF where they apply).
  * msdr_chain_get_nco: the channel's step and the phase of its NEXT sample (either pointer may be NULL); ARGUMENT_ERROR on a chain that is
  *   not in this mode.
+ * msdr_chain_set_decimation: the third piece of a digital down-converter behind oscillator and FIR -- arm_fir_decimate_q15 /
+ *   arm_fir_decimate_fast_q15 / arm_fir_decimate_f32's convention: D new samples into the state, one output ending at the newest.  With
+ *   decimation D, output sample m of a call is exactly what the undecimated chain's demodulator would have produced at input sample
+ *   m * D + D - 1 of that call, and the passes behind the demodulator run on that decimated stream as if it were the stream.  Mixer, FIR
+ *   history and oscillator generations still see every input sample; the FIR pair, the demodulator, the store and every recurrence behind
+ *   the kernel shrink by D.  D = 1 (the default) is off.
+ *   msdr_chain_process with D > 1: d_if is unchanged ([channels or n_inputs][n_samples]); d_audio is [channels][n_samples / D].
+ *   n_samples % D != 0 is MSDR_STATUS_LENGTH_ERROR, nothing enqueued, no state moved (the decimation phase is therefore 0 at every call
+ *   boundary); a Q15 chain with biquad nodes needs n_samples / D even, same error.  The chain's time, the history and the generations
+ *   advance by n_samples.  The Q15 nodes (shared or per-channel records), the F32 CMSIS-order cascade (shared or per-channel rows) and
+ *   MSDR_CHAIN_OUT_I16 with its scratch get n_samples / D samples per channel.
+ *   A switch of the host's: stream-ordered, may be called at any time, keeps every state.  The FIR history is raw IF at the full rate and
+ *   does not care; node and cascade states simply CONTINUE AT THE NEW RATE -- the caller designs those filters for fs / D
+ *   (msdr_biquad_design takes the sample rate).
+ *   Scope: chains in phase-accumulator mode only (msdr_chain_set_nco_channels has been called), Q15 and F32; every other chain is
+ *   MSDR_STATUS_ARGUMENT_ERROR, nothing changed.  Also refused: a Q15 chain created with MSDR_CHAIN_SYNCAM_PLL, a Q15 chain with an LMS
+ *   channel on (and, while D > 1, msdr_chain_set_anr with any channel on); fp32 chains in this mode refuse both already.
+ *   Values: 1 .. MSDR_MAX_DECIMATION_Q15 (60) / MSDR_MAX_DECIMATION_F32 (59).  The kernel's window of one wave with one channel --
+ *   128 D + np mixed samples per stream (np = num_taps rounded up to 8 (Q15) / 4 (F32)), twice for odd D on Q15 chains -- must fit 64 KB of
+ *   LDS beside the tap rows and the 4 KB sine table:
+ *     Q15, even D:  512 D +  8 np <= 61 440      Q15, odd D:  1024 D + 12 np <= 61 440      F32:  1024 D + 16 np <= 61 440
+ *   The maxima are the largest D such that every factor up to it holds an 8- (4-) tap filter; a D whose window does not fit beside THIS
+ *   chain's filter is ARGUMENT_ERROR, nothing changed.  At 102 taps every factor up to 58 is accepted; at D = 8 filters of up to 7 168
+ *   (Q15: every chain) / 3 328 (F32) taps, at D = 32 up to 5 632 / 1 792.
+ *   Reporting: msdr_chain_get_info().kernel begins chain_q15pcnd_kernel / chain_f32pcnd_kernel, `tile` is the launch's tile in OUTPUTS,
+ *   and on fp32 chains flavour carries MSDR_FLAVOUR_DECIMATED beside NCO_PC and TAPS_PC.  Graphs stay refused, as on every chain in this
+ *   mode; msdr_chain_set_block_kernel[_q15] is accepted and such calls run the unfused launches.  The setting survives everything the
+ *   oscillator bank survives: msdr_chain_reset and init_fir, the tap, node, cascade and NCO setters, msdr_chain_set_input_rows.
+ * msdr_chain_get_decimation: the factor in force (1 on every chain that never set one).
  * msdr_nco_step (host only): llround(f_hz / fs_hz * 2^32) mod 2^32; a negative frequency wraps (-6000 at 24000: 0xC0000000).
  * msdr_nco_table (host only): T[i] = (int16) lround(32767 sin(2 pi i / 1024)), i = 0 .. 1024, T[1024] = 0.
  * msdr_nco_q15 (host only; what the kernels compute): for each uint32 phase, i = phase >> 22, f = (phase >> 6) & 0xFFFF,
@@ -710,6 +739,9 @@ void msdr_nco_q15(const uint32_t *phase, size_t count, int16_t *sin_out, int16_t
 int msdr_chain_set_nco_channels(msdr_chain *chain, uint32_t first_channel, uint32_t count,
                                 const uint32_t *step, const uint32_t *phase);
 int msdr_chain_get_nco(msdr_chain *chain, uint32_t channel, uint32_t *step, uint32_t *phase);
+enum { MSDR_MAX_DECIMATION_Q15 = 60, MSDR_MAX_DECIMATION_F32 = 59 };
+int msdr_chain_set_decimation(msdr_chain *chain, uint32_t D);   /* 1 = off (default) */
+int msdr_chain_get_decimation(msdr_chain *chain, uint32_t *D);
 int msdr_chain_set_taps(msdr_chain *chain, uint32_t tapset, const void *coeffs_i, const void *coeffs_q);
 int msdr_chain_set_taps_channels(msdr_chain *chain, uint32_t first_channel, uint32_t count,
                                  const q15_t *coeffs_i, const q15_t *coeffs_q);
@@ -779,6 +811,9 @@ enum { MSDR_FLAVOUR_SHARED_IF = 0x40000u };
 /* And another: the demodulator kernel computed every channel's oscillator from its phase accumulator -- chain_f32pcn_kernel,
  * msdr_chain_set_nco_channels (always beside MSDR_FLAVOUR_TAPS_PC). */
 enum { MSDR_FLAVOUR_NCO_PC = 0x80000u };
+/* And another: the demodulator kernel decimated -- chain_f32pcnd_kernel, msdr_chain_set_decimation with D > 1 (always beside
+ * MSDR_FLAVOUR_NCO_PC and MSDR_FLAVOUR_TAPS_PC). */
+enum { MSDR_FLAVOUR_DECIMATED = 0x100000u };
 int msdr_chain_get_info(msdr_chain *chain, msdr_chain_info *info);
 /* Which kernel ran the serial recurrences (introspection for tests: tests/q15_ladder_cases.py is the table of every branch below, and
  * tests/test_gpu_q15_ladders.py holds each of them to the oracle bit for bit).  Each getter returns a static string -- the kernel's name

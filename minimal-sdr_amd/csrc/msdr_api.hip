@@ -2495,6 +2495,10 @@ struct msdr_chain {
     std::vector<uint32_t> h_nco_base, h_nco_step;
     uint64_t nco_T = 0;                   // samples processed since creation / msdr_chain_reset (every chain counts them)
     bool hist_clear = true;               // no sample has entered the FIR history since creation / msdr_chain_reset / msdr_chain_init_fir
+    // msdr_chain_set_decimation (chains with the phase-accumulator oscillator only): D > 1 runs chain_q15pcnd_kernel / chain_f32pcnd_kernel
+    // (msdr_chain_decpc.hiph) -- d_audio is [channels][n_samples / D] and every pass behind the demodulator sees n_samples / D samples.  Host
+    // state alone: the history is raw IF at the full rate, node and cascade states carry on at the new rate.
+    uint32_t decim = 1;
     // msdr_chain_set_block_kernel (F32): a block-cadence call of the chain in per-channel mode runs chain_f32pcb_kernel (msdr_chain_f32pcb.hiph) --
     // demodulator, CMSIS-order cascade, int16 conversion and the next history in ONE launch -- where msdr_chain_process finds the conditions met;
     // every other call runs the unfused launches over the same history, table position and cascade state.  Off by default.
@@ -2548,6 +2552,9 @@ static const char kQpcboKernelName[] = "chain_q15pcb_kernel (per-channel taps an
 // ... and of the chains with the phase-accumulator oscillator (msdr_chain_set_nco_channels)
 static const char kPcnKernelName[] = "chain_q15pcn_kernel (per-channel taps, phase oscillator)";
 static const char kPcfnKernelName[] = "chain_f32pcn_kernel (per-channel taps, phase oscillator)";
+// ... and of the same chains under msdr_chain_set_decimation
+static const char kPcndKernelName[] = "chain_q15pcnd_kernel (per-channel taps, NCO, decimator)";
+static const char kPcfndKernelName[] = "chain_f32pcnd_kernel (per-channel taps, NCO, decimator)";
 static void chain_pcf_row_from(msdr_chain *c, uint32_t ch, const float *ci, const float *cq)
 {
     float *row = c->h_pcf_taps.data() + (size_t)ch * 2 * c->pc_np;
@@ -3992,7 +3999,7 @@ static int chain_prepare(msdr_chain *c, ChainDecision &d, const ChainTiles &t, c
     }
     if (d.i16 == kI16InKernel && path_mfw(d.path)) p.dbg |= kChainOutI16;       // (chain_f32pcb_kernel: PcbParams.out_i16)
     if (d.i16 == kI16ViaScratch) {
-        if (int rc = grow_device(c->ctx, &c->d_f32_scratch, &c->f32_scratch_floats, (size_t)c->channels * n_samples)) return rc;
+        if (int rc = grow_device(c->ctx, &c->d_f32_scratch, &c->f32_scratch_floats, (size_t)c->channels * (n_samples / c->decim))) return rc;      // (the audio: n / D per channel)
         p.out = c->d_f32_scratch;                                    // where the fp32 passes of this call read and write the audio
     }
     p.mf_tab = c->d_mf_tab; p.mf_stride = c->mf_stride; p.mf_halo = c->mf_halo; p.mf_bsteps = c->mf_bsteps; p.mf_xsteps = c->mf_xsteps; p.bq_mf = c->d_bq_mf; p.bq_mf32 = c->d_bq_mf32;
@@ -4095,7 +4102,14 @@ static int chain_launch_f32pc(msdr_chain *c, const ChainDecision &, const ChainP
     pc_params(q, c, p);
     q.out = (float *)p.out; q.taps = c->d_pcf_taps; q.mixer = c->mixer; q.in_scale = c->in_scale; q.osc_hist = p.osc_hist;
     PcLaunch geo;
-    if (c->nco_active) {
+    if (c->nco_active && c->decim > 1) {          // msdr_chain_set_decimation: p.out is [channels][n / D]
+        PcfndParams qd;
+        static_cast<PcfnParams &>(qd) = q;
+        qd.sin_tab = c->d_nco_tab; qd.t0 = (unsigned)c->nco_T; qd.dec = (int)c->decim; qd.opl = 0; qd.nout = 0;
+        if (launch_chain_f32pcnd(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, qd, &geo) != hipSuccess)
+            return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pcnd_kernel launch failed");
+        r.kname = kPcfndKernelName; r.flavour |= MSDR_FLAVOUR_NCO_PC | MSDR_FLAVOUR_DECIMATED;
+    } else if (c->nco_active) {
         q.sin_tab = c->d_nco_tab; q.t0 = (unsigned)c->nco_T;
         if (launch_chain_f32pcn(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, q, &geo) != hipSuccess)
             return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pcn_kernel launch failed");
@@ -4280,7 +4294,14 @@ static int chain_launch_q15pc(msdr_chain *c, const ChainDecision &, const ChainP
     pc_params(q, c, p);
     q.out = (short *)p.out; q.taps = c->d_pc_taps; q.mixer = c->mixer; q.sqrt_kind = c->sqrt_kind; q.syncam_q = p.syncam_q; q.osc_hist = p.osc_hist;
     PcLaunch geo;
-    if (c->nco_active) {
+    if (c->nco_active && c->decim > 1) {          // msdr_chain_set_decimation: p.out is [channels][n / D]
+        PcndParams qd;
+        static_cast<PcnParams &>(qd) = q;
+        qd.sin_tab = c->d_nco_tab; qd.t0 = (unsigned)c->nco_T; qd.dec = (int)c->decim; qd.opl = 0; qd.nout = 0;
+        if (launch_chain_q15pcnd(c->ctx->stream, c->ctx->num_cus, qd, &geo) != hipSuccess)
+            return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pcnd_kernel launch failed");
+        r.kname = kPcndKernelName;
+    } else if (c->nco_active) {
         q.sin_tab = c->d_nco_tab; q.t0 = (unsigned)c->nco_T;
         if (launch_chain_q15pcn(c->ctx->stream, c->ctx->num_cus, q, &geo) != hipSuccess)
             return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pcn_kernel launch failed");
@@ -4361,6 +4382,13 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     const bool f32 = (c->arith == MSDR_ARITH_F32);
     if (!f32 && c->nnodes && (n_samples & 1u))
         return fail(MSDR_STATUS_LENGTH_ERROR, "AudioFilterBiquad processes sample pairs: n_samples must be even");
+    // msdr_chain_set_decimation: whole groups of D samples per call (the decimation phase is 0 at every call boundary); everything behind the
+    // demodulator kernel sees n_out samples
+    if (n_samples % c->decim)
+        return fail(MSDR_STATUS_LENGTH_ERROR, "decimation %u: n_samples (%llu) must be a multiple of it; nothing enqueued", c->decim, (unsigned long long)n_samples);
+    const uint64_t n_out = n_samples / c->decim;
+    if (!f32 && c->nnodes && (n_out & 1u))
+        return fail(MSDR_STATUS_LENGTH_ERROR, "AudioFilterBiquad processes sample pairs: n_samples / decimation (%llu) must be even; nothing enqueued", (unsigned long long)n_out);
 
     // ---- decide, prepare
     ChainDecision d = chain_decide(c, d_if, d_audio, n_samples);
@@ -4398,30 +4426,31 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     if (int rc2 = launch_check("chain_kernel")) return rc2;
     if (e0) { HIP_TRY(hipEventRecord(e1, c->ctx->stream)); c->events.emplace_back(e0, e1); }
 
-    // ---- the passes behind it
+    // ---- the passes behind it: n_out samples per channel (n_samples / decimation; the two are equal without msdr_chain_set_decimation)
     if (c->seq_bq && d.path != kPathF32Pcb) // F32, ill-conditioned cascade: arm_biquad_cascade_df1_f32 in CMSIS order, in place on the audio (chain_f32pcb_kernel ran it itself)
-        { if (int rc2 = msdr_biquad_df1_f32_process(c->seq_bq, (const float *)fout, (float *)fout, (uint32_t)n_samples)) return rc2; r.flavour |= MSDR_FLAVOUR_SEQ_CASCADE | (c->seq_bq->per_channel ? (uint32_t)MSDR_FLAVOUR_CASCADE_PC : 0u); }
+        { if (int rc2 = msdr_biquad_df1_f32_process(c->seq_bq, (const float *)fout, (float *)fout, (uint32_t)n_out)) return rc2; r.flavour |= MSDR_FLAVOUR_SEQ_CASCADE | (c->seq_bq->per_channel ? (uint32_t)MSDR_FLAVOUR_CASCADE_PC : 0u); }
 
     if (d.pll_active)          // SYNCAM channels: I (in d_audio) and Q (scratch) -> PLL demodulator -> audio, before the biquad nodes
-        if (int rc2 = msdr_syncam_q15(c->pll, c->d_mode, (const q15_t *)d_audio, c->d_pll_q, (q15_t *)d_audio, (uint32_t)n_samples)) return rc2;
+        if (int rc2 = msdr_syncam_q15(c->pll, c->d_mode, (const q15_t *)d_audio, c->d_pll_q, (q15_t *)d_audio, (uint32_t)n_out)) return rc2;
 
     if (d.anr_active)          // LMS notch / noise reduction (.ino:702-770), then the biquad nodes
-        if (int rc2 = msdr_anr_q15(c->anr, c->d_anr_on, c->anr_all, (q15_t *)d_audio, (uint32_t)n_samples)) return rc2;
+        if (int rc2 = msdr_anr_q15(c->anr, c->d_anr_on, c->anr_all, (q15_t *)d_audio, (uint32_t)n_out)) return rc2;
 
     if (d.path == kPathQ15Pcb) { /* (chain_q15pcb_kernel ran the nodes as its third phase, on the same records) */ }
     else if (c->nnodes == 2 && !d.nodes_fused) {
-        if (int rc2 = chain_two_nodes(c, d_audio, n_samples, &r.node_kname)) return rc2;
+        if (int rc2 = chain_two_nodes(c, d_audio, n_out, &r.node_kname)) return rc2;
     } else if (c->nnodes == 1) {
-        if (int rc2 = msdr_biquad_q15_update(c->nodes[0], (q15_t *)d_audio, (uint32_t)n_samples)) return rc2;
+        if (int rc2 = msdr_biquad_q15_update(c->nodes[0], (q15_t *)d_audio, (uint32_t)n_out)) return rc2;
         r.node_kname = c->nodes[0]->last_kernel;
     }
     c->node_kernel = r.node_kname;
 
     // rows f2 / f3 inside the fp32 chain: PLL / LMS channels are redone behind the main kernel (before the history moves on: a rebuilt
     // auxiliary chain takes over the history and table position this call started from)
+    // (no chain with a decimator has such channels: msdr_chain_set_nco_channels and msdr_chain_set_anr refuse them)
     if (f32) if (int rc2 = chain_post_run(c, d_if, (float *)fout, n_samples)) return rc2;
     if (d.i16 == kI16ViaScratch) {
-        const long long total = (long long)c->channels * (long long)n_samples;
+        const long long total = (long long)c->channels * (long long)n_out;
         hipLaunchKernelGGL(f32_to_q15_kernel, dim3(grid_1d((total + 3) / 4)), dim3(256), 0, c->ctx->stream, (const float *)fout, (short *)d_audio, total);
         if (int rc2 = launch_check("f32_to_q15_kernel")) return rc2;
     }
@@ -4842,6 +4871,7 @@ static int chain_rebuild(msdr_chain *c, const ChainCfgStore &edited, void **stea
     // ... the phase-accumulator oscillator's bank (its pending generations went over with osc_pending above) and the chain's time
     n->nco_active = c->nco_active; std::swap(n->d_nco_bank, c->d_nco_bank); std::swap(n->d_nco_tab, c->d_nco_tab);
     n->h_nco_base.swap(c->h_nco_base); n->h_nco_step.swap(c->h_nco_step); n->nco_T = c->nco_T; n->hist_clear = c->hist_clear;
+    n->decim = c->decim;          // (msdr_chain_set_decimation holds through every rebuild)
     std::swap(*c, *n);
     if (steal_osc) { *steal_osc = n->d_osc; n->d_osc = nullptr; }
     chain_free(n);
@@ -5284,6 +5314,32 @@ extern "C" int msdr_chain_get_nco(msdr_chain *c, uint32_t channel, uint32_t *ste
     return 0;
 }
 
+// The third piece of a digital down-converter behind oscillator and FIR (arm_fir_decimate_*'s convention): a switch of the host's, read by
+// the next msdr_chain_process.  Everything that can fail happens before anything changes.
+extern "C" int msdr_chain_set_decimation(msdr_chain *c, uint32_t D)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (!c->nco_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "decimation: only on a chain with the phase-accumulator oscillator (msdr_chain_set_nco_channels); nothing changed");
+    const bool f32 = c->arith == MSDR_ARITH_F32;
+    if (D == 0 || D > (uint32_t)chain_dec_max(f32))
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "decimation %u: 1 .. %d (the window of one wave with one channel must fit 64 KB of LDS beside the sine table); nothing changed", D, chain_dec_max(f32));
+    if (D > 1 && !chain_dec_fits(f32, c->pc_np, (int)D))
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "decimation %u: beside its window the kernel holds filters of up to %d taps (this chain has %u); nothing changed", D, chain_dec_max_taps(f32, (int)D), c->ntaps);
+    if (!f32 && D > 1) {          // (fp32 chains with the phase-accumulator oscillator have neither)
+        if (c->pll) return fail(MSDR_STATUS_ARGUMENT_ERROR, "decimation: not on a chain created with MSDR_CHAIN_SYNCAM_PLL (the PLL demodulator runs at the full rate); nothing changed");
+        if (chain_anr_active(c)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "decimation: not while an LMS channel is on (msdr_chain_set_anr); nothing changed");
+    }
+    c->decim = D;
+    return 0;
+}
+
+extern "C" int msdr_chain_get_decimation(msdr_chain *c, uint32_t *D)
+{
+    if (!c || !D) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
+    *D = c->decim;
+    return 0;
+}
+
 extern "C" int msdr_chain_set_node_coefficients(msdr_chain *c, uint32_t node, uint32_t stage, const int32_t coef[5])
 {
     if (!c || !coef) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
@@ -5457,6 +5513,11 @@ extern "C" int msdr_chain_set_anr(msdr_chain *c, const int32_t *anr_on, int32_t 
         for (int &v : c->h_anr) if (v < 0) v = 0;
         c->anr_gen++;
         return 0;
+    }
+    if (c->decim > 1) {          // msdr_chain_set_decimation: the LMS filter belongs to the full rate
+        bool any = anr_on ? false : anr_on_all > 0;
+        if (anr_on) for (uint32_t ch = 0; ch < c->channels; ch++) any = any || anr_on[ch] > 0;
+        if (any) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain decimates (msdr_chain_set_decimation): no LMS channels; nothing changed");
     }
     if (!c->anr) if (int rc = msdr_anr_create(c->ctx, c->channels, &c->anr)) return rc;
     HIP_TRY(hipStreamSynchronize(c->ctx->stream));

@@ -70,6 +70,15 @@ hipError_t launch_chain_f32pco(hipStream_t stream, int num_cus, int time_segment
 int chain_pcn_max_taps(bool f32);
 hipError_t launch_chain_q15pcn(hipStream_t stream, int num_cus, PcnParams p, PcLaunch *geo);
 hipError_t launch_chain_f32pcn(hipStream_t stream, int num_cus, int time_segments, PcfnParams p, PcLaunch *geo);
+// ---- msdr_chain_decpc.hip ----
+// chain_q15pcnd_kernel<CPW, AL> / chain_f32pcnd_kernel<CPW, AL> (msdr_chain_decpc.hiph): the two kernels above with decimation p.dec >= 2
+// (p.n a multiple of it).  The launcher fills p.nout, p.opl, p.nseg, p.seg_len and p.nw from dec_geometry (msdr_decpc_geometry.h); geo->tile
+// is in outputs.  chain_dec_fits: whether factor D fits beside filters of np padded taps at all; chain_dec_max: the setter's largest factor.
+bool chain_dec_fits(bool f32, int np, int D);
+int chain_dec_max(bool f32);
+int chain_dec_max_taps(bool f32, int D);
+hipError_t launch_chain_q15pcnd(hipStream_t stream, int num_cus, PcndParams p, PcLaunch *geo);
+hipError_t launch_chain_f32pcnd(hipStream_t stream, int num_cus, int time_segments, PcfndParams p, PcLaunch *geo);
 // ---- msdr_biquad_df1_pc.hip ----
 // biquad_df1_seq_pc_kernel<S, SEG> (msdr_biquad_df1_pc.hiph): stages = S = 1 .. 4 sections in CMSIS order on data [channels][n] (y may be x), every
 // channel with the 5 S coefficients of its own row of tab ([channels][20] floats).  nseg = 1: state_in may be state_out, seg_len / warm / scratch

@@ -174,6 +174,20 @@ struct PcfnParams : PcfParams {
     unsigned t0;
 };
 
+// chain_q15pcnd_kernel / chain_f32pcnd_kernel (msdr_chain_decpc.hiph): the two blocks above with a decimator behind the FIR pair.  x, n, t0
+// and the history are the INPUT's (full rate); `out` is [channels][nout], nseg / seg_len count outputs (seg_len a multiple of the tile
+// opl * 64 / channels per wave).
+struct PcndParams : PcnParams {
+    int dec;                   // decimation D >= 2: output m is the demodulator's value at input sample m * D + D - 1
+    int opl;                   // outputs per lane (msdr_decpc_geometry.h)
+    long long nout;            // n / D
+};
+struct PcfndParams : PcfnParams {
+    int dec;
+    int opl;
+    long long nout;
+};
+
 // chain_f32pcb_kernel (msdr_chain_f32pcb.hiph): a whole block-cadence call of the fp32 chain with per-channel settings in one launch
 struct PcbParams {
     const int16_t *x;          // [channels][n] IF samples

@@ -33,6 +33,8 @@ FLAVOUR_CASCADE_PC = 0x10000
 FLAVOUR_OSC_PC = 0x20000
 FLAVOUR_SHARED_IF = 0x40000
 FLAVOUR_NCO_PC = 0x80000
+FLAVOUR_DECIMATED = 0x100000
+MAX_DECIMATION_Q15, MAX_DECIMATION_F32 = 60, 59
 FE_DCBLOCK, FE_AMP, FE_AGC, FE_ALL = 1, 2, 4, 7
 
 STATUS_ARGUMENT_ERROR, STATUS_LENGTH_ERROR, STATUS_NO_DEVICE = -1, -2, -100
@@ -108,6 +110,8 @@ def load_library(path=None):
                        ("msdr_chain_set_input_rows", [_p, C.c_uint32, _p]),
                        ("msdr_chain_set_nco_channels", [_p, C.c_uint32, C.c_uint32, _p, _p]),
                        ("msdr_chain_get_nco", [_p, C.c_uint32, _p, _p]),
+                       ("msdr_chain_set_decimation", [_p, C.c_uint32]),
+                       ("msdr_chain_get_decimation", [_p, _p]),
                        ("msdr_nco_step", [C.c_double, C.c_double]),
                        ("msdr_nco_table", [_p]),
                        ("msdr_nco_q15", [_p, C.c_size_t, _p, _p]),
@@ -900,6 +904,18 @@ class Chain(_Instance):
         st, ph = C.c_uint32(0), C.c_uint32(0)
         _ck(self.ctx.lib.msdr_chain_get_nco(self.h, C.c_uint32(channel), C.byref(st), C.byref(ph)))
         return st.value, ph.value
+
+    def set_decimation(self, D):
+        """a chain in phase-accumulator mode becomes a bank of digital down-converters: output m of a call is the demodulator's value at input
+        sample m * D + D - 1, d_audio is [channels, n // D] and the nodes / the cascade behind the kernel run at fs / D.  1 = off; every state
+        kept (msdr_chain_set_decimation)."""
+        _ck(self.ctx.lib.msdr_chain_set_decimation(self.h, C.c_uint32(D)))
+
+    def decimation(self):
+        """the decimation in force (msdr_chain_get_decimation)"""
+        d = C.c_uint32(0)
+        _ck(self.ctx.lib.msdr_chain_get_decimation(self.h, C.byref(d)))
+        return d.value
 
     def set_block_kernel(self, on):
         """F32: a block-cadence call of a chain in per-channel mode as ONE launch (chain_f32pcb_kernel: demodulator, CMSIS-order cascade, int16
