@@ -8,12 +8,14 @@
 //   msdr_chain_q15pc.hip   the Q15 chain / the arm_fir_fast_q15 stage with per-channel FIR coefficients: chain_q15pc_kernel
 //   msdr_chain_f32pc.hip   the fp32 chain / the arm_fir_f32 stage with per-channel FIR coefficients: chain_f32pc_kernel
 //   msdr_biquad_df1_pc.hip arm_biquad_cascade_df1_f32 in CMSIS order with per-channel coefficients: biquad_df1_seq_pc_kernel
-//   msdr_chain_oscpc.hip   the two chains above with per-channel oscillator tables: chain_q15pco_kernel, chain_f32pco_kernel
-//   msdr_chain_ncopc.hip   the same two with a per-channel phase-accumulator oscillator: chain_q15pcn_kernel, chain_f32pcn_kernel
+//   msdr_chain_oscpc.hip   the frames of the two chains above with the oscillator policy "a row of a bank per channel": chain_q15pco_kernel, chain_f32pco_kernel
+//   msdr_chain_ncopc.hip   the same frames with the policy "a phase accumulator per channel": chain_q15pcn_kernel, chain_f32pcn_kernel
+//   msdr_chain_decpc.hip   that policy under a decimating tile loop: chain_q15pcnd_kernel, chain_f32pcnd_kernel
 //   msdr_chain_f32pcb.hip  the fp32 chain with per-channel settings at block cadence, one launch per call: chain_f32pcb_kernel
 //   msdr_chain_q15pcb.hip  the Q15 chain with per-channel settings at block cadence, one launch per call: chain_q15pcb_kernel
 // Host-side geometry helpers (LDS sizes, table formats) live with the kernels' headers; the launch geometry of the per-receiver chain kernels
-// (PcLaunch, pc_geometry, kPcLdsCap) is msdr_pc_geometry.h, plain C++.  Every launcher returns the HIP error of its launch.
+// (PcLaunch, pc_geometry, kPcLdsCap) is msdr_pc_geometry.h, plain C++; the eight launchers of those kernels are calls of one body, pc_launch
+// (msdr_pc_launch.h).  Every launcher returns the HIP error of its launch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "msdr_shared.h"
@@ -58,12 +60,13 @@ hipError_t launch_chain_q15pc(hipStream_t stream, bool fir_only, int num_cus, Pc
 // choice, 1 = never split, > 1 = that many (as far as the call has tiles).
 hipError_t launch_chain_f32pc(hipStream_t stream, bool fir_only, int num_cus, int time_segments, PcfParams p, PcLaunch *geo);
 // ---- msdr_chain_oscpc.hip ----
-// chain_q15pco_kernel<CPW> / chain_f32pco_kernel<CPW> (msdr_chain_oscpc.hiph): the two chain kernels above with per-channel oscillator tables.
+// chain_q15pco_kernel<CPW> / chain_f32pco_kernel<CPW> (msdr_chain_oscpc.hiph): the frames of the two chain kernels above, the oscillator row of
+// each channel in LDS.
 // p.osc is the bank [channels][osc_len] of pairs, p.mixer MSDR_MIXER_NCO; geometry chosen as above, with the row's LDS counted in.
 hipError_t launch_chain_q15pco(hipStream_t stream, int num_cus, PcParams p, PcLaunch *geo);
 hipError_t launch_chain_f32pco(hipStream_t stream, int num_cus, int time_segments, PcfParams p, PcLaunch *geo);
 // ---- msdr_chain_ncopc.hip ----
-// chain_q15pcn_kernel<CPW> / chain_f32pcn_kernel<CPW> (msdr_chain_ncopc.hiph): the two chain kernels above with a phase-accumulator oscillator.
+// chain_q15pcn_kernel<CPW> / chain_f32pcn_kernel<CPW> (msdr_chain_ncopc.hiph): the same frames with a phase-accumulator oscillator per channel.
 // p.osc is the bank [channels] of pairs {base0, step}, p.sin_tab the packed sine table (msdr_nco.h), p.t0 the chain time of the call's first
 // sample, p.mixer MSDR_MIXER_NCO; geometry chosen as above, with the table's LDS (once per workgroup) counted in.  chain_pcn_max_taps: the
 // longest filter (taps padded as the kernel pads them) one wave with one channel holds beside the table.
@@ -71,7 +74,7 @@ int chain_pcn_max_taps(bool f32);
 hipError_t launch_chain_q15pcn(hipStream_t stream, int num_cus, PcnParams p, PcLaunch *geo);
 hipError_t launch_chain_f32pcn(hipStream_t stream, int num_cus, int time_segments, PcfnParams p, PcLaunch *geo);
 // ---- msdr_chain_decpc.hip ----
-// chain_q15pcnd_kernel<CPW, AL> / chain_f32pcnd_kernel<CPW, AL> (msdr_chain_decpc.hiph): the two kernels above with decimation p.dec >= 2
+// chain_q15pcnd_kernel<CPW, AL> / chain_f32pcnd_kernel<CPW, AL> (msdr_chain_decpc.hiph): the phase-accumulator oscillator with decimation p.dec >= 2
 // (p.n a multiple of it).  The launcher fills p.nout, p.opl, p.nseg, p.seg_len and p.nw from dec_geometry (msdr_decpc_geometry.h); geo->tile
 // is in outputs.  chain_dec_fits: whether factor D fits beside filters of np padded taps at all; chain_dec_max: the setter's largest factor.
 bool chain_dec_fits(bool f32, int np, int D);

@@ -1,6 +1,7 @@
 // msdr_chain_decpc.hip -- the decimating chain kernels with a per-channel phase-accumulator oscillator and their launchers (a translation unit of its own).
 #include "msdr_chain_decpc.hiph"
 #include "msdr_block.h"
+#include "msdr_pc_launch.h"
 
 namespace msdr {
 
@@ -10,58 +11,43 @@ int chain_dec_max_taps(bool f32, int D) { return dec_max_taps(f32, D); }
 
 // f(std::integral_constant<int, AL>) for the kernels' read widths
 template <typename F>
-static void dec_dispatch_al(int al, F f)
+static auto dec_dispatch_al(int al, F f)
 {
     switch (al) {
-    case 4: f(std::integral_constant<int, 4>()); break;
-    case 2: f(std::integral_constant<int, 2>()); break;
-    case 1: f(std::integral_constant<int, 1>()); break;
-    default: f(std::integral_constant<int, 0>()); break;
+    case 4: return f(std::integral_constant<int, 4>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 1: return f(std::integral_constant<int, 1>());
+    default: return f(std::integral_constant<int, 0>());
     }
 }
 
-// launch geometry from dec_geometry (msdr_decpc_geometry.h): everything in outputs
+// pc_launch for the decimating pair: launch geometry from dec_geometry (msdr_decpc_geometry.h), everything in outputs; p.nout and p.opl
+// beside the fields every parameter block carries.  kernel_of(CPW, AL): the instantiation for the read width al.
+template <typename P, typename KernelOf>
+static hipError_t dec_launch(hipStream_t stream, P &p, bool valid, bool f32, int num_cus, int time_segments, int al, KernelOf kernel_of, PcLaunch *geo)
+{
+    if (!valid || p.dec < 2 || p.n % p.dec) return hipErrorInvalidValue;
+    p.nout = p.n / p.dec;
+    DecGeometry g;
+    const bool ok = dec_geometry(p.nout, p.channels, num_cus, time_segments, kPcLdsCap, [&](int cpw, int nw, int opl) { return dec_lds_bytes(f32, p.np, p.dec, cpw, nw, opl); }, &g);
+    if (ok) p.opl = g.opl;
+    return pc_launch_geometry(stream, p, ok, g, [&](auto cpw) { return dec_dispatch_al(al, [&](auto a) { return kernel_of(cpw, a); }); }, geo);
+}
+
 hipError_t launch_chain_q15pcnd(hipStream_t stream, int num_cus, PcndParams p, PcLaunch *geo)
 {
-    if (p.np <= 0 || (p.np & 7) || p.channels <= 0 || p.n <= 0 || p.mixer != kMixerNco || !p.osc || !p.sin_tab || p.syncam_q) return hipErrorInvalidValue;
-    if (p.dec < 2 || p.n % p.dec) return hipErrorInvalidValue;
-    p.nout = p.n / p.dec;
-    const int D = p.dec;
-    DecGeometry g;          // (time_segments = 0: the Q15 chains do not look at the configuration's value)
-    if (!dec_geometry(p.nout, p.channels, num_cus, 0, kPcLdsCap, [&](int cpw, int nw, int opl) { return dec_q15_lds_bytes(p.np, D, cpw, nw, opl); }, &g))
-        return hipErrorInvalidValue;
-    p.nseg = g.launch.nseg; p.seg_len = g.seg_len; p.nw = g.nw; p.opl = g.opl;
-    const PcLaunch &l = g.launch;
-    const int al = (D & 1) ? 0 : (D % 8 == 0) ? 4 : (D % 4 == 0) ? 2 : 1;
-    pc_dispatch_cpw(l.cpw, [&](auto cpw) {
-        dec_dispatch_al(al, [&](auto a) {
-            hipLaunchKernelGGL((chain_q15pcnd_kernel<decltype(cpw)::value, decltype(a)::value>), dim3(l.grid), dim3(l.block), l.lds_bytes, stream, p);
-        });
-    });
-    if (geo) *geo = l;
-    return hipGetLastError();
+    const int D = p.dec;          // (time_segments = 0: the Q15 chains do not look at the configuration's value)
+    return dec_launch(stream, p, p.np > 0 && !(p.np & 7) && p.channels > 0 && p.n > 0 && p.mixer == kMixerNco && p.osc && p.sin_tab && !p.syncam_q, false, num_cus, 0,
+                      (D & 1) ? 0 : (D % 8 == 0) ? 4 : (D % 4 == 0) ? 2 : 1,
+                      [](auto cpw, auto a) { return chain_q15pcnd_kernel<decltype(cpw)::value, decltype(a)::value>; }, geo);
 }
 
 hipError_t launch_chain_f32pcnd(hipStream_t stream, int num_cus, int time_segments, PcfndParams p, PcLaunch *geo)
 {
-    if (p.np <= 0 || (p.np & 3) || p.channels <= 0 || p.n <= 0 || p.mixer != kMixerNco || !p.osc || !p.sin_tab) return hipErrorInvalidValue;
-    if (p.dec < 2 || p.n % p.dec) return hipErrorInvalidValue;
-    p.nout = p.n / p.dec;
     const int D = p.dec;
-    DecGeometry g;
-    if (!dec_geometry(p.nout, p.channels, num_cus, time_segments, kPcLdsCap, [&](int cpw, int nw, int opl) { return dec_f32_lds_bytes(p.np, D, cpw, nw, opl); }, &g))
-        return hipErrorInvalidValue;
-    p.nseg = g.launch.nseg; p.seg_len = g.seg_len; p.nw = g.nw; p.opl = g.opl;
-    const PcLaunch &l = g.launch;
-    const int al = (D % 4 == 0) ? 4 : (D % 2 == 0) ? 2 : 1;
-    pc_dispatch_cpw(l.cpw, [&](auto cpw) {
-        dec_dispatch_al(al, [&](auto a) {
-            if constexpr (decltype(a)::value != 0)
-                hipLaunchKernelGGL((chain_f32pcnd_kernel<decltype(cpw)::value, decltype(a)::value>), dim3(l.grid), dim3(l.block), l.lds_bytes, stream, p);
-        });
-    });
-    if (geo) *geo = l;
-    return hipGetLastError();
+    return dec_launch(stream, p, p.np > 0 && !(p.np & 3) && p.channels > 0 && p.n > 0 && p.mixer == kMixerNco && p.osc && p.sin_tab, true, num_cus, time_segments,
+                      (D % 4 == 0) ? 4 : (D % 2 == 0) ? 2 : 1,
+                      [](auto cpw, auto a) { return chain_f32pcnd_kernel<decltype(cpw)::value, decltype(a)::value == 0 ? 1 : decltype(a)::value>; }, geo);          // (AL = 0 is Q15's)
 }
 
 }  // namespace msdr

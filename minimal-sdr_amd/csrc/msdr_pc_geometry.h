@@ -1,5 +1,5 @@
 // msdr_pc_geometry.h -- launch geometry of the per-receiver chain kernels (chain_q15pc / chain_f32pc / chain_q15pco / chain_f32pco /
-// chain_f32pcb): plain host C++, no HIP, so that the rule is testable on its own (tests/test_pc_geometry.py).
+// chain_q15pcn / chain_f32pcn; its LDS-fitting step also of chain_f32pcb / chain_q15pcb): plain host C++, no HIP, so that the rule is testable on its own (tests/test_pc_geometry.py).
 //
 //   channels per wave   CPW = 4 for calls of up to 128 samples (the reference's block), 2 up to 256, else 1; a lane owns R consecutive outputs,
 //                       so a channel's tile is R * 64 / CPW outputs

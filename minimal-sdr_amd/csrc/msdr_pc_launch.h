@@ -1,0 +1,31 @@
+// msdr_pc_launch.h -- the one body of the per-receiver chain launchers (launch_chain_q15pc ... launch_chain_f32pcnd, msdr_block.h): what follows
+// a launcher's own validation.  Host code of the translation units that hold the kernels; the geometry rule itself is msdr_pc_geometry.h.
+#pragma once
+#include <hip/hip_runtime.h>
+#include "msdr_pc_geometry.h"
+
+namespace msdr {
+
+// ok: the launcher's validation and its geometry routine both held (g is read only then).  Copies what the kernels' parameter blocks carry
+// of the geometry, launches kernel_of(std::integral_constant<int, CPW>) -- the instantiation for the chosen channels per wave -- and reports.
+template <typename P, typename G, typename KernelOf>
+inline hipError_t pc_launch_geometry(hipStream_t stream, P &p, bool ok, const G &g, KernelOf kernel_of, PcLaunch *geo)
+{
+    if (!ok) return hipErrorInvalidValue;
+    const PcLaunch &l = g.launch;
+    p.nseg = l.nseg; p.seg_len = g.seg_len; p.nw = g.nw;
+    pc_dispatch_cpw(l.cpw, [&](auto cpw) { hipLaunchKernelGGL(kernel_of(cpw), dim3(l.grid), dim3(l.block), l.lds_bytes, stream, p); });
+    if (geo) *geo = l;
+    return hipGetLastError();
+}
+
+// The sliding-window kernels: pc_geometry with outs_per_lane outputs per lane and lds_bytes(cpw, nw).  time_segments as
+// msdr_chain_config.time_segments; the Q15 launchers pass 0 (they do not look at the configuration's value).
+template <typename P, typename LdsBytes, typename KernelOf>
+inline hipError_t pc_launch(hipStream_t stream, P &p, bool valid, int num_cus, int time_segments, int outs_per_lane, LdsBytes lds_bytes, KernelOf kernel_of, PcLaunch *geo)
+{
+    PcGeometry g;
+    return pc_launch_geometry(stream, p, valid && pc_geometry(p.n, p.channels, num_cus, time_segments, outs_per_lane, kPcLdsCap, lds_bytes, &g), g, kernel_of, geo);
+}
+
+}  // namespace msdr

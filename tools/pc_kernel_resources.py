@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Resource table of the per-receiver chain kernels, without a GPU: compiles the four translation units to gfx950 assembly with the
+"""Resource table of the per-receiver chain kernels, without a GPU: compiles their seven translation units to gfx950 assembly with the
 Makefile's flags and prints, per instantiation, the code-object metadata and the instruction count of the body as a markdown table.
 
     python tools/pc_kernel_resources.py [--csrc DIR] [--against DIR]
@@ -14,7 +14,7 @@ import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")          # as the Makefile's HIPCC ?=
-UNITS = ["msdr_chain_q15pc", "msdr_chain_f32pc", "msdr_chain_oscpc", "msdr_chain_f32pcb"]
+UNITS = ["msdr_chain_q15pc", "msdr_chain_f32pc", "msdr_chain_oscpc", "msdr_chain_ncopc", "msdr_chain_decpc", "msdr_chain_f32pcb", "msdr_chain_q15pcb"]
 FIELDS = ["vgpr_count", "sgpr_count", "agpr_count", "group_segment_fixed_size", "private_segment_fixed_size", "vgpr_spill_count"]
 
 

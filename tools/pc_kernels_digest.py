@@ -2,21 +2,27 @@
 """tools/pc_kernels_digest.py -- what the per-receiver chain kernels compute and how they are launched, as digests (not collected by pytest).
 
 Runs against the library MSDR_LIB names (default: this tree's build).  Run it once against a build of one commit and once against a build of
-another: the two JSON files are byte-identical exactly when every case gives the same output bits from the same launches.
+another: the two JSON files are byte-identical exactly when every case gives the same output bits from the same launches.  --out holds
+one line per case (the SHA-256 over the case's records); --records FILE keeps the records themselves, to find the shape that differs.
 
-Cases reach every instantiation and every mixer policy of chain_q15pc / chain_f32pc / chain_q15pco / chain_f32pco / chain_f32pcb:
+Cases reach every instantiation and every oscillator policy of chain_q15pc / chain_f32pc / chain_q15pco / chain_f32pco / chain_q15pcn /
+chain_f32pcn / chain_q15pcnd / chain_f32pcnd and the block kernels chain_f32pcb / chain_q15pcb:
 per-channel taps (Fs/4, the shared NCO table, the table with a pending generation; LSB / USB / AM, both square roots and a SYNCAM channel
-under the PLL on Q15), per-channel oscillator rows with and without a pending generation, a set_input_rows map (on the taps, the rows and
-the block kernels), the two FIR stages with per-channel coefficients, block-kernel ticks (Fs/4, shared table, bank; 0 and 2 cascade stages, shared and per-channel rows; fp32 and int16),
-and one long call with time segments.  7 channels; n in {128, 256, 1003} (block kernel: 128, 256, 512); 13, 21 and 30 taps (padded rows of 16,
+under the PLL on Q15), per-channel oscillator rows with and without a pending generation, a set_input_rows map (on the taps, the rows, the
+phase accumulator and the block kernels), the phase-accumulator oscillator (*_nco_steps: set_nco_channels with steps off the 128 grid;
+*_nco_pending: some channels retuned between the priming call and the calls that count; *_nco_map: behind a set_input_rows map; the table
+mixer's cases have the names *_nco and *_pending), decimation by 2, 3, 4 and 8 (*_dec: every read width AL of both kernels),
+the two FIR stages with per-channel coefficients, block-kernel ticks (Fs/4, shared table, bank; 0 and 2 cascade stages, shared and per-channel rows; fp32 and int16),
+and one long call with time segments.  7 channels; n in {128, 256, 1003} (block kernel: 128, 256, 512; decimation: 64, 250 and 1003 OUTPUTS,
+n = outputs x factor, so that every factor meets 4, 2 and 1 channels per wave); 13, 21 and 30 taps (padded rows of 16,
 24 and 32; Q15: 14, 22 and 30 taps, the same rows -- arm_fir_init_q15 takes even counts only); osc_len 24.
 
 Every shape of a case: a priming call of 37 samples (36 with 21 taps: the calls that count start with a full history at a non-zero phase, odd
 and even, so that both arrangements of the Fs/4 flavour's rows and accumulators run at every n), the
-case's pending change if it has one, then TWO calls of n samples; the record holds the SHA-256 of the two outputs' bytes and what
+case's pending change if it has one (decimation is set here: the priming call runs undecimated), then TWO calls of n samples; the record holds the SHA-256 of the two outputs' bytes and what
 msdr_chain_get_info reports behind the second.  Each case runs in a child process under its own time limit; the run stops at the first failure.
 
-usage: python tools/pc_kernels_digest.py [--out FILE.json] [--cases a,b,...]"""
+usage: python tools/pc_kernels_digest.py [--out FILE.json] [--records FILE.json] [--cases a,b,...]"""
 import argparse
 import hashlib
 import json
@@ -30,6 +36,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LIMIT_S = 120
 CH, L = 7, 24
 NS, NTS = (128, 256, 1003), (13, 21, 30)
+NOUTS = (64, 250, 1003)          # outputs of a decimated call
 INFO = ("kernel", "grid", "block", "lds_bytes", "time_segments", "tile")
 MAP = [0, 1, 0, 2, 1, 0, 2]          # set_input_rows: 7 receivers on 3 input rows
 
@@ -53,6 +60,14 @@ def taps(rng, rows, nt, f32):
     return (rng.standard_normal((rows, nt)) * 0.08).astype(np.float32) if f32 else rng.integers(-2500, 2501, (rows, nt)).astype(np.int16)
 
 
+def set_map(chain):
+    """The map, set twice.  The first msdr_chain_set_input_rows of a chain allocates the table and clears it on the chain's stream, then uploads
+    the rows with a blocking copy that does not wait for that clear: on the first chain of a process the clear has been seen to land after
+    the upload (rows read as 0).  The second call waits for the stream before it uploads."""
+    for _ in range(2):
+        chain.set_input_rows(np.array(MAP))
+
+
 def record(obj, channels, calls, out_dtype, in_dtype=np.int16):
     """calls: the inputs of the priming call and of the two calls that count, in order; a callable among them runs between two calls"""
     h, k = hashlib.sha256(), 0
@@ -60,7 +75,7 @@ def record(obj, channels, calls, out_dtype, in_dtype=np.int16):
         if callable(c):
             c()
             continue
-        dx, dy = ctx.to_device(np.ascontiguousarray(c, in_dtype)), ctx.array((channels, c.shape[1]), out_dtype)
+        dx, dy = ctx.to_device(np.ascontiguousarray(c, in_dtype)), ctx.array((channels, c.shape[1] // getattr(obj, "decimation", lambda: 1)()), out_dtype)
         obj.process(dx, dy, c.shape[1])
         if k:
             h.update(dy.download().tobytes())
@@ -93,13 +108,45 @@ def chain_case(name):
             if what == "rows_pending":
                 change = lambda: chain.set_osc_channels(2, ni[:4], nq[:4])          # noqa: E731
             if what in ("map", "rows_map"):
-                chain.set_input_rows(np.array(MAP))
+                set_map(chain)
                 rows = max(MAP) + 1
             x = [rng.integers(-20000, 20001, (rows, m)).astype(np.int16) for m in (prime(nt), n, n)]
             sha = record(chain, CH, [x[0]] + ([change] if change else []) + x[1:], np.float32 if f32 else np.int16)
             info = chain.info()
             out.append(dict(n=n, taps=nt, sha256=sha, **{k: info[k] for k in INFO}))
             chain.close()
+    return out
+
+
+def nco_case(name):
+    """the phase-accumulator oscillator: name = <arith>_<nco_steps | nco_pending | nco_map | dec>"""
+    arith, what = name.split("_", 1)
+    f32 = arith == "f32"
+    out = []
+    for D in ((2, 3, 4, 8) if what == "dec" else (1,)):
+        for n in (NOUTS if what == "dec" else NS):
+            for nt in NTS:
+                rng = np.random.default_rng([D, n, nt, len(name)])
+                ci, cq = taps(rng, CH, ntaps(nt, f32), f32), taps(rng, CH, ntaps(nt, f32), f32)
+                oi, oq = osc(rng, 1, f32)
+                steps, phases = [(rng.integers(1, 1 << 32, CH, dtype=np.uint64) | np.uint64(1)).astype(np.uint32) for _ in range(2)], [rng.integers(0, 1 << 32, CH, dtype=np.uint64).astype(np.uint32) for _ in range(2)]
+                modes = np.array([msdr.MODE_LSB, msdr.MODE_USB, msdr.MODE_AM, msdr.MODE_CW, msdr.MODE_AM, msdr.MODE_LSB, msdr.MODE_USB], np.int32)
+                chain = msdr.Chain(ctx, msdr.ARITH_F32 if f32 else msdr.ARITH_Q15, CH, ci[0], cq[0], mixer=msdr.MIXER_NCO, modes=modes, osc_i=oi[0], osc_q=oq[0])
+                (chain.set_taps_channels_f32 if f32 else chain.set_taps_channels)(0, ci, cq)
+                chain.set_nco_channels(0, steps[0], phases[0])
+                change, rows = None, CH
+                if what == "nco_pending":
+                    change = lambda: chain.set_nco_channels(2, steps[1][:4], phases[1][:4])          # noqa: E731
+                if what == "dec":
+                    change = lambda: chain.set_decimation(D)          # noqa: E731
+                if what == "nco_map":
+                    set_map(chain)
+                    rows = max(MAP) + 1
+                x = [rng.integers(-20000, 20001, (rows, m)).astype(np.int16) for m in (prime(nt), n * D, n * D)]
+                sha = record(chain, CH, [x[0]] + ([change] if change else []) + x[1:], np.float32 if f32 else np.int16)
+                info = chain.info()
+                out.append(dict(n=n * D, taps=nt, sha256=sha, **({"decimation": D} if what == "dec" else {}), **{k: info[k] for k in INFO}))
+                chain.close()
     return out
 
 
@@ -144,7 +191,7 @@ def block_case(name):
                     if what in ("bank", "map"):
                         chain.set_osc_channels(0, oi, oq)
                     if what == "map":
-                        chain.set_input_rows(np.array(MAP))
+                        set_map(chain)
                     chain.set_block_kernel(1)
                     x = [rng.integers(-20000, 20001, (max(MAP) + 1 if what == "map" else CH, m)).astype(np.int16) for m in (prime(nt), n, n)]
                     sha = record(chain, CH, x, np.int16 if i16 else np.float32)
@@ -180,13 +227,16 @@ CASES = {}
 for _a in ("q15", "f32"):
     for _w in ("fs4", "nco", "pending", "rows", "rows_pending", "map", "rows_map"):
         CASES["%s_%s" % (_a, _w)] = chain_case
+    for _w in ("nco_steps", "nco_pending", "nco_map", "dec"):
+        CASES["%s_%s" % (_a, _w)] = nco_case
     CASES["%s_fir" % _a] = fir_case
 CASES.update({"q15_nco_q31": chain_case, "q15_pll": chain_case, "block_fs4": block_case, "block_shared": block_case, "block_bank": block_case, "block_map": block_case, "long": long_case})
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out")
+    ap.add_argument("--out", help="one line per case: its records folded into one SHA-256 (default: to stdout)")
+    ap.add_argument("--records", help="every record of every case, to see which shape differs when two runs do")
     ap.add_argument("--cases", default=",".join(CASES))
     ap.add_argument("--case", help="run this one case in this process")
     args = ap.parse_args()
@@ -212,7 +262,13 @@ def main():
             break
         res[name] = json.loads(p.stdout.strip().splitlines()[-1])
         print("%s: %d records" % (name, len(res[name])), file=sys.stderr, flush=True)
-    text = json.dumps(res, indent=1, sort_keys=True) + "\n"
+    if args.records:
+        with open(args.records, "w") as f:
+            f.write(json.dumps(res, indent=1, sort_keys=True) + "\n")
+    # one line per case: the SHA-256 over its records (each: shape, output digest, launch), so that two runs compare at a glance
+    text = "{\n" + ",\n".join(' "%s": %s' % (name, json.dumps({"records": len(recs), "kernels": sorted({r["kernel"] for r in recs if "kernel" in r}),
+                                                             "sha256": hashlib.sha256(json.dumps(recs, sort_keys=True).encode()).hexdigest()}, sort_keys=True))
+                             for name, recs in sorted(res.items())) + "\n}\n"
     if args.out:
         with open(args.out, "w") as f:
             f.write(text)
