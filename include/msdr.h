@@ -728,6 +728,36 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   mode; msdr_chain_set_block_kernel[_q15] is accepted and such calls run the unfused launches.  The setting survives everything the
  *   oscillator bank survives: msdr_chain_reset and init_fir, the tap, node, cascade and NCO setters, msdr_chain_set_input_rows.
  * msdr_chain_get_decimation: the factor in force (1 on every chain that never set one).
+ * msdr_chain_set_meter: the S-meter of the bank (the reference's to-do list begins with it, Minimal-SDR.ino:48-50) -- the power of every
+ *   channel behind its channel filter and before its demodulator, measured inside the per-receiver kernels at no extra pass over memory.
+ *   For a call of msdr_chain_process with n_out = n_samples / D outputs per channel
+ *       meter[c] = sum over m < n_out of I_c[m]^2 + Q_c[m]^2
+ *   with I_c[m], Q_c[m] the two FIR outputs the demodulator of output m receives, whatever the channel's mode (AM, SYNCAM -- under
+ *   MSDR_CHAIN_SYNCAM_PLL too -- LSB, USB, CW); no node, cascade, LMS filter or int16 conversion is in it.
+ *     Q15   I, Q = the saturated (acc >> 15) of arm_fir_fast_q15; the entry is a uint64_t, an exact integer whatever the launch geometry
+ *           (a pair of squares is at most 2^31, 2^31 outputs of that fit)
+ *     F32   the two fp32 sums in in_scale units; a lane's 8 outputs are added in fp32, everything beyond in double, in an order that the
+ *           launch geometry fixes (no atomics): the entry is a double, bit-identical from run to run
+ *   d_meter: device memory of the caller, [channels] entries of 8 bytes, 8-byte aligned; NULL = off (the default).  From the next
+ *   msdr_chain_process on every successful call OVERWRITES all `channels` entries, on the chain's stream, without synchronising; a call
+ *   that returns an error (MSDR_STATUS_LENGTH_ERROR included) writes nothing.  Integration over calls is the caller's business.  A
+ *   misaligned pointer or a NULL chain is MSDR_STATUS_ARGUMENT_ERROR, nothing changed.
+ *   The first non-NULL call enters the per-channel kernel family exactly as msdr_chain_set_input_rows does (tap table filled from the
+ *   shared tap sets, fp32 cascade behind the kernel in CMSIS order), with that call's refusals: an fp32 chain created with
+ *   MSDR_CHAIN_SYNCAM_PLL or with an LMS channel on (and, while a meter is set, msdr_chain_set_anr with a channel on), a filter beyond
+ *   the per-channel kernel's tap limit.  NULL leaves the chain in that family with the meter off.  The pointer survives everything the
+ *   input map survives: msdr_chain_reset and init_fir, every tap / oscillator / NCO / node / cascade / mode setter,
+ *   msdr_chain_set_input_rows, msdr_chain_set_decimation.
+ *   While a meter is set msdr_chain_set_block_kernel[_q15] stays accepted and calls run the unfused launches; msdr_chain_graph_create is
+ *   refused, and a graph made before a msdr_chain_set_meter call is refused at launch after it.
+ *   Reporting: msdr_chain_get_info().kernel keeps its names; on fp32 chains flavour carries MSDR_FLAVOUR_METER while a meter is set.
+ *   A call in more than one time segment (info.time_segments) writes per-segment partials of the chain's own and adds them in segment
+ *   order in a second small kernel (meter_reduce_kernel).
+ * msdr_chain_get_meter: the pointer in force (NULL on a chain that never set one).
+ * msdr_meter_dbfs (host only): 10 log10((sum_sq / n_out) / (full_scale^2 / 4)); full_scale = 32768 for Q15, 32768 * in_scale for F32;
+ *   -HUGE_VAL for sum_sq <= 0 or n_out == 0.  0 dBFS is a full-scale real carrier at the tuned frequency behind a unity-gain channel
+ *   filter (I^2 + Q^2 = A^2 / 4): round(32767 sin(2 pi 40 t / 128 + 0.3)) against bin 40 of 128 behind calc_FIR_coeffs(102, 2500 Hz)
+ *   reads -0.005 dBFS from the second block on.
  * msdr_nco_step (host only): llround(f_hz / fs_hz * 2^32) mod 2^32; a negative frequency wraps (-6000 at 24000: 0xC0000000).
  * msdr_nco_table (host only): T[i] = (int16) lround(32767 sin(2 pi i / 1024)), i = 0 .. 1024, T[1024] = 0.
  * msdr_nco_q15 (host only; what the kernels compute): for each uint32 phase, i = phase >> 22, f = (phase >> 6) & 0xFFFF,
@@ -742,6 +772,9 @@ int msdr_chain_get_nco(msdr_chain *chain, uint32_t channel, uint32_t *step, uint
 enum { MSDR_MAX_DECIMATION_Q15 = 60, MSDR_MAX_DECIMATION_F32 = 59 };
 int msdr_chain_set_decimation(msdr_chain *chain, uint32_t D);   /* 1 = off (default) */
 int msdr_chain_get_decimation(msdr_chain *chain, uint32_t *D);
+int msdr_chain_set_meter(msdr_chain *chain, void *d_meter);   /* NULL = off (default) */
+int msdr_chain_get_meter(msdr_chain *chain, void **d_meter);
+double msdr_meter_dbfs(double sum_sq, uint64_t n_out, double full_scale);
 int msdr_chain_set_taps(msdr_chain *chain, uint32_t tapset, const void *coeffs_i, const void *coeffs_q);
 int msdr_chain_set_taps_channels(msdr_chain *chain, uint32_t first_channel, uint32_t count,
                                  const q15_t *coeffs_i, const q15_t *coeffs_q);
@@ -814,6 +847,9 @@ enum { MSDR_FLAVOUR_NCO_PC = 0x80000u };
 /* And another: the demodulator kernel decimated -- chain_f32pcnd_kernel, msdr_chain_set_decimation with D > 1 (always beside
  * MSDR_FLAVOUR_NCO_PC and MSDR_FLAVOUR_TAPS_PC). */
 enum { MSDR_FLAVOUR_DECIMATED = 0x100000u };
+/* And another: the demodulator kernel measured the channels' power -- the metered flavour of a per-receiver kernel, msdr_chain_set_meter with
+ * a buffer (always beside MSDR_FLAVOUR_TAPS_PC). */
+enum { MSDR_FLAVOUR_METER = 0x200000u };
 int msdr_chain_get_info(msdr_chain *chain, msdr_chain_info *info);
 /* Which kernel ran the serial recurrences (introspection for tests: tests/q15_ladder_cases.py is the table of every branch below, and
  * tests/test_gpu_q15_ladders.py holds each of them to the oracle bit for bit).  Each getter returns a static string -- the kernel's name

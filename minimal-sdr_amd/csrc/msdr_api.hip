@@ -2514,6 +2514,12 @@ struct msdr_chain {
     uint32_t n_inputs = 0;
     int *d_in_row = nullptr;              // [channels], allocated by the first call; read by the kernels only while n_inputs > 0
     uint64_t in_row_epoch = 0;            // bumped by every msdr_chain_set_input_rows call: part of a HIP graph's key
+    // msdr_chain_set_meter: the caller's [channels] sums of I^2 + Q^2 (uint64_t for Q15, double for F32), written by the metered flavours of
+    // the per-receiver kernels (msdr_chain_meter.hiph) in every call while it is set; the block kernels and graphs step aside meanwhile
+    void *d_meter = nullptr;
+    void *d_meter_part = nullptr;         // partials [meter_part_cap] of calls in more than one time segment, the chain's own
+    size_t meter_part_cap = 0;
+    uint64_t meter_epoch = 0;             // bumped by every msdr_chain_set_meter call: part of a HIP graph's key
     msdr_chain_info info;
     // optional per-launch timing of the main kernel
     bool timing;
@@ -2621,7 +2627,7 @@ static void chain_free(msdr_chain *c)
     hipFree(c->d_anr_on);
     for (auto &e : c->events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (auto &o : c->osc_pending) hipFree(o.d_tab);
-    hipFree(c->d_f32_scratch); hipFree(c->d_osc_hist); hipFree(c->d_btiles); hipFree(c->d_pc_taps); hipFree(c->d_pcf_taps); hipFree(c->d_osc_bank); hipFree(c->d_in_row);
+    hipFree(c->d_f32_scratch); hipFree(c->d_osc_hist); hipFree(c->d_btiles); hipFree(c->d_pc_taps); hipFree(c->d_pcf_taps); hipFree(c->d_osc_bank); hipFree(c->d_in_row); hipFree(c->d_meter_part);
     hipFree(c->d_nco_bank); hipFree(c->d_nco_tab);
     delete c;
 }
@@ -3775,7 +3781,7 @@ static ChainDecision chain_decide(msdr_chain *c, const int16_t *d_if, const void
         const bool mfw_out_aligned = (want_i16 && !mfw_i16_direct) || out_aligned;
         // msdr_chain_set_block_kernel: the whole block-cadence call of a per-channel chain in one launch (msdr_chain_f32pcb.hiph) -- where no
         // oscillator generation is pending, nothing runs behind the kernel but a CMSIS-order cascade, and one wave's LDS fits
-        if (c->pc_active && c->block_pc && !c->nco_active && block_n && !osc_pending && !d.post_active &&
+        if (c->pc_active && c->block_pc && !c->nco_active && !c->d_meter && block_n && !osc_pending && !d.post_active &&
             (!c->seq_bq || c->seq_bq->stages == 0 || c->seq_bq->sequential) && chain_f32pcb_lds((int)n_samples, c->pc_np, pc_osc_len, nullptr))
             d.path = kPathF32Pcb;
         else if (c->pc_active) d.path = kPathF32Pc;                  // per-channel taps: chain_f32pc_kernel in place of every uniform demodulator kernel
@@ -3801,7 +3807,7 @@ static ChainDecision chain_decide(msdr_chain *c, const int16_t *d_if, const void
         else if (qm) d.path = kPathQ15Mf;
         // msdr_chain_set_block_kernel_q15: the whole call of a per-channel chain in one launch (msdr_chain_q15pcb.hiph) -- where no oscillator
         // generation is pending, neither the PLL demodulator nor the LMS filter runs between the demodulator and the nodes, and one wave's LDS fits
-        else if (c->pc_active && c->block_q15 && !c->nco_active && block_n && !osc_pending && !d.pll_active && !d.anr_active &&
+        else if (c->pc_active && c->block_q15 && !c->nco_active && !c->d_meter && block_n && !osc_pending && !d.pll_active && !d.anr_active &&
                  chain_q15pcb_lds((int)n_samples, c->pc_np, pc_osc_len, nullptr))
             d.path = kPathQ15Pcb;
         else if (c->pc_active) d.path = kPathQ15Pc;                  // per-channel taps: chain_q15pc_kernel in place of every uniform demodulator kernel
@@ -4070,6 +4076,12 @@ static void pc_params(Q &q, const msdr_chain *c, const ChainParams &p)
     if (c->nco_active) q.osc = c->d_nco_bank;                              // ... phase-accumulator oscillator: the bank of {base0, step}
     q.osc_len = p.osc_len; q.phase0 = p.phase0; q.in_row = c->n_inputs ? c->d_in_row : nullptr;
 }
+// msdr_chain_set_meter: the three fields of PcParams / PcfParams (the launchers pick the metered instantiations by q.meter)
+template <typename Q>
+static void pc_params_meter(Q &q, const msdr_chain *c)
+{
+    q.meter = (decltype(q.meter))c->d_meter; q.meter_part = (decltype(q.meter_part))c->d_meter_part; q.meter_cap = (long long)c->meter_part_cap;
+}
 static void pc_geometry_of(const PcLaunch &geo, ChainLaunch &r)
 {
     r.grid = geo.grid; r.block = geo.block; r.lds_bytes = geo.lds_bytes; r.nseg = geo.nseg; r.tile = geo.tile;
@@ -4101,6 +4113,7 @@ static int chain_launch_f32pc(msdr_chain *c, const ChainDecision &, const ChainP
     PcfnParams q;          // (PcfParams and the phase-accumulator oscillator's two operands)
     pc_params(q, c, p);
     q.out = (float *)p.out; q.taps = c->d_pcf_taps; q.mixer = c->mixer; q.in_scale = c->in_scale; q.osc_hist = p.osc_hist;
+    pc_params_meter(q, c);
     PcLaunch geo;
     if (c->nco_active && c->decim > 1) {          // msdr_chain_set_decimation: p.out is [channels][n / D]
         PcfndParams qd;
@@ -4124,7 +4137,8 @@ static int chain_launch_f32pc(msdr_chain *c, const ChainDecision &, const ChainP
         r.kname = kPcfKernelName;
     }
     pc_geometry_of(geo, r);
-    r.flavour |= MSDR_FLAVOUR_TAPS_PC | (geo.nseg > 1 ? MSDR_FLAVOUR_SEGMENTED : 0u) | (c->n_inputs ? (uint32_t)MSDR_FLAVOUR_SHARED_IF : 0u);
+    r.flavour |= MSDR_FLAVOUR_TAPS_PC | (geo.nseg > 1 ? MSDR_FLAVOUR_SEGMENTED : 0u) | (c->n_inputs ? (uint32_t)MSDR_FLAVOUR_SHARED_IF : 0u) |
+                 (c->d_meter ? (uint32_t)MSDR_FLAVOUR_METER : 0u);
     return 0;
 }
 
@@ -4293,6 +4307,7 @@ static int chain_launch_q15pc(msdr_chain *c, const ChainDecision &, const ChainP
     PcnParams q;          // (PcParams and the phase-accumulator oscillator's two operands)
     pc_params(q, c, p);
     q.out = (short *)p.out; q.taps = c->d_pc_taps; q.mixer = c->mixer; q.sqrt_kind = c->sqrt_kind; q.syncam_q = p.syncam_q; q.osc_hist = p.osc_hist;
+    pc_params_meter(q, c);
     PcLaunch geo;
     if (c->nco_active && c->decim > 1) {          // msdr_chain_set_decimation: p.out is [channels][n / D]
         PcndParams qd;
@@ -4520,6 +4535,7 @@ struct msdr_chain_graph {
     bool k_block_q15;      // chain_q15pcb_kernel (msdr_chain_set_block_kernel_q15): the captured ticks are one launch each, the switch as it was
     uint64_t k_block_q15_epoch;
     uint64_t k_in_row_epoch;   // msdr_chain_set_input_rows calls so far: each changes what the captured d_if pointers are taken to be
+    uint64_t k_meter_epoch;    // msdr_chain_set_meter calls so far (no graph is made while a meter is set; one made before knows nothing of it)
     const void *k_pcf_taps, *k_osc_bank, *k_bq_tab, *k_bq_state;
     size_t k_pcf_cap, k_osc_cap, k_bq_cap;
 };
@@ -4529,7 +4545,7 @@ static void chain_graph_key(const msdr_chain *c, msdr_chain_graph *g)
     g->k_tiles = c->d_btiles; g->k_cur = c->cur; g->k_mode_gen = c->mode_gen; g->k_nodes_pc = chain_nodes_per_channel(c); g->k_taps_pc = c->pc_active;
     g->k_rebuild_gen = c->rebuild_gen; g->k_mode = c->d_mode; g->k_osc = c->d_osc; g->k_osc_pc = c->opc_active; g->k_osc_gen = c->osc_gen;
     g->k_block_pc = c->arith == MSDR_ARITH_F32 && c->pc_active && c->block_pc; g->k_block_epoch = c->block_epoch; g->k_anr_gen = c->anr_gen;
-    g->k_in_row_epoch = c->in_row_epoch;
+    g->k_in_row_epoch = c->in_row_epoch; g->k_meter_epoch = c->meter_epoch;
     g->k_block_q15 = c->arith == MSDR_ARITH_Q15 && c->pc_active && c->block_q15; g->k_block_q15_epoch = c->block_q15_epoch;
     g->k_pcf_taps = c->d_pcf_taps; g->k_pcf_cap = c->pc_active ? (size_t)c->channels * 2 * (size_t)c->pc_np : 0;
     g->k_osc_bank = c->d_osc_bank; g->k_osc_cap = c->opc_active ? (size_t)c->channels * c->osc_len : 0;
@@ -4545,6 +4561,7 @@ extern "C" int msdr_chain_graph_create(msdr_chain *c, uint32_t ticks, const int1
     if (!c || !d_if || !d_audio) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
     if (int rc = bind(c->ctx)) return rc;
     if (c->nco_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "a chain with the phase-accumulator oscillator is not capturable (the time of a call's first sample is a launch operand: a replay would repeat one phase)");
+    if (c->d_meter) return fail(MSDR_STATUS_ARGUMENT_ERROR, "a chain with a meter set (msdr_chain_set_meter) is not capturable (a replay of `ticks` calls would leave the last call's sums alone): set the meter to NULL first");
     if (ticks < 2 || (ticks & 1u) || ticks > 1024) return fail(MSDR_STATUS_ARGUMENT_ERROR, "a chain graph holds an even number of calls, 2 .. 1024 (the state buffers alternate from call to call)");
     for (uint32_t k = 0; k < ticks; k++) if (!d_if[k] || !d_audio[k]) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null buffer for call %u", k);
     // 1. preparation: every table / cache a call of this shape needs, built outside the capture (uploads and synchronisations are not
@@ -4592,6 +4609,8 @@ extern "C" int msdr_chain_graph_launch(msdr_chain_graph *g)
     if (c->nco_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the chain got a phase-accumulator oscillator since this graph was made (its captured launches mix with tables): graphs are not for such chains");
     msdr_chain_graph now;
     chain_graph_key(c, &now);
+    if (c->d_meter || now.k_meter_epoch != g->k_meter_epoch)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "msdr_chain_set_meter ran since this graph was made (its captured launches measure nothing): make the graph again, with the meter set to NULL");
     if (now.k_hist != g->k_hist || now.k_state != g->k_state || now.k_tab != g->k_tab || now.k_tiles != g->k_tiles || now.k_cur != g->k_cur || now.k_mode_gen != g->k_mode_gen ||
         now.k_rebuild_gen != g->k_rebuild_gen || now.k_mode != g->k_mode || now.k_osc != g->k_osc)
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "the chain has changed since this graph was made (a live update, a reset, or an odd number of direct calls in between): make the graph again");
@@ -4868,6 +4887,7 @@ static int chain_rebuild(msdr_chain *c, const ChainCfgStore &edited, void **stea
     n->block_pc = c->block_pc; n->block_epoch = c->block_epoch;          // (msdr_chain_set_block_kernel holds for the chain's life)
     n->block_q15 = c->block_q15; n->block_q15_epoch = c->block_q15_epoch;          // (and so does msdr_chain_set_block_kernel_q15)
     n->n_inputs = c->n_inputs; std::swap(n->d_in_row, c->d_in_row); n->in_row_epoch = c->in_row_epoch;       // (the input map too)
+    n->d_meter = c->d_meter; std::swap(n->d_meter_part, c->d_meter_part); n->meter_part_cap = c->meter_part_cap; n->meter_epoch = c->meter_epoch;       // (and the meter)
     // ... the phase-accumulator oscillator's bank (its pending generations went over with osc_pending above) and the chain's time
     n->nco_active = c->nco_active; std::swap(n->d_nco_bank, c->d_nco_bank); std::swap(n->d_nco_tab, c->d_nco_tab);
     n->h_nco_base.swap(c->h_nco_base); n->h_nco_step.swap(c->h_nco_step); n->nco_T = c->nco_T; n->hist_clear = c->hist_clear;
@@ -5107,6 +5127,57 @@ extern "C" int msdr_chain_set_input_rows(msdr_chain *c, uint32_t n_inputs, const
     c->n_inputs = n_inputs;
     c->in_row_epoch++;
     return 0;
+}
+
+// The S-meter: from the next call on the per-receiver kernels' metered flavours (msdr_chain_meter.hiph) write every channel's sum of
+// I^2 + Q^2 over the call to d_meter, on the chain's stream.  The first non-NULL call enters the per-channel kernel family exactly as
+// msdr_chain_set_input_rows does, with its refusals; NULL switches the meter off and leaves the chain in that family.  Everything that can
+// fail happens before anything changes.
+extern "C" int msdr_chain_set_meter(msdr_chain *c, void *d_meter)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (int rc = bind(c->ctx)) return rc;
+    if (reinterpret_cast<uintptr_t>(d_meter) & 7) return fail(MSDR_STATUS_ARGUMENT_ERROR, "d_meter holds 8-byte entries: it must be 8-byte aligned; nothing changed");
+    if (d_meter) {
+        const bool f32 = c->arith == MSDR_ARITH_F32;
+        if (f32) {
+            // PLL / LMS channels of an fp32 chain are redone behind the main kernel through an auxiliary chain (chain_post_run): what the
+            // per-receiver kernel measured would not be what the audio came from
+            if (c->f32_pll) return fail(MSDR_STATUS_ARGUMENT_ERROR, "meter: not on an fp32 chain created with MSDR_CHAIN_SYNCAM_PLL (its PLL channels run through an auxiliary chain); nothing changed");
+            for (int v : c->h_anr) if (v > 0) return fail(MSDR_STATUS_ARGUMENT_ERROR, "meter: not while an LMS channel of an fp32 chain is on (such channels run through an auxiliary chain); nothing changed");
+            if (!c->pc_active && f32pc_np((int)c->ntaps) > f32pc_max_taps(false))
+                return fail(MSDR_STATUS_ARGUMENT_ERROR, "meter: the per-channel kernel holds filters of up to %d taps (this chain has %u); nothing changed", f32pc_max_taps(false), c->ntaps);
+        }
+        HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+        // the partials of calls in more than one time segment: the most entries the launch geometry can ask for (meter_partials)
+        const size_t cap = meter_partials((int)c->channels, c->ctx->num_cus, f32 ? (int)c->time_segments : 0);
+        if (cap > c->meter_part_cap) {
+            void *part = nullptr;
+            if (hipMalloc(&part, cap * 8) != hipSuccess) { (void)hipGetLastError(); return fail(MSDR_STATUS_OUT_OF_MEMORY, "meter: device allocation of %zu bytes failed; nothing changed", cap * 8); }
+            hipFree(c->d_meter_part);
+            c->d_meter_part = part; c->meter_part_cap = cap;
+        }
+        const bool taps_first = !c->pc_active;                  // the per-channel kernel family, entered as the other per-channel setters enter it
+        if (int rc = chain_pc_activate(c)) return rc;
+        if (taps_first) if (int rc = chain_pc_upload(c, 0, c->channels)) return rc;
+    }
+    c->d_meter = d_meter;
+    c->meter_epoch++;
+    return 0;
+}
+
+extern "C" int msdr_chain_get_meter(msdr_chain *c, void **d_meter)
+{
+    if (!c || !d_meter) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
+    *d_meter = c->d_meter;
+    return 0;
+}
+
+// 0 dBFS: a full-scale real carrier at the tuned frequency behind a unity-gain channel filter, I^2 + Q^2 = A^2 / 4
+extern "C" double msdr_meter_dbfs(double sum_sq, uint64_t n_out, double full_scale)
+{
+    if (!(sum_sq > 0.0) || n_out == 0) return -HUGE_VAL;
+    return 10.0 * std::log10((sum_sq / (double)n_out) / (full_scale * full_scale / 4.0));
 }
 
 // ---- per-channel oscillator tables ----
@@ -5500,10 +5571,11 @@ extern "C" int msdr_chain_set_anr(msdr_chain *c, const int32_t *anr_on, int32_t 
     if (c->arith != MSDR_ARITH_Q15) {
         // fp32 chain: the float flavour of the filter, between demodulator and cascade (chain_post_run)
         if (c->seq_bq && !c->h_bq_stages) return fail(MSDR_STATUS_ARGUMENT_ERROR, "internal: cascade coefficients not kept");
-        if ((c->seq_bq && c->seq_bq->per_channel) || c->opc_active || c->nco_active || c->n_inputs) {      // (LMS channels run a post cascade with the chain's uniform coefficients, behind an auxiliary chain with the shared oscillator tables)
+        if ((c->seq_bq && c->seq_bq->per_channel) || c->opc_active || c->nco_active || c->n_inputs || c->d_meter) {      // (LMS channels run a post cascade with the chain's uniform coefficients, behind an auxiliary chain with the shared oscillator tables)
             bool any = anr_on ? false : anr_on_all > 0;
             if (anr_on) for (uint32_t ch = 0; ch < c->channels; ch++) any = any || anr_on[ch] > 0;
             if (any && c->n_inputs) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has an input map (msdr_chain_set_input_rows): no LMS channels (they run through an auxiliary chain that gathers its rows from d_if by channel); nothing changed");
+            if (any && c->d_meter) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has a meter set (msdr_chain_set_meter): no LMS channels (they run through an auxiliary chain, which the meter does not see); nothing changed");
             if (any && c->opc_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has per-channel oscillator tables: no LMS channels (they run through an auxiliary chain with the shared tables); nothing changed");
             if (any && c->nco_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has the phase-accumulator oscillator: no LMS channels (they run through an auxiliary chain with the shared tables); nothing changed");
             if (any) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has per-channel cascade coefficients: no LMS channels (they run a post cascade of their own); nothing changed");

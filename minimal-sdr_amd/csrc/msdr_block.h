@@ -11,6 +11,7 @@
 //   msdr_chain_oscpc.hip   the frames of the two chains above with the oscillator policy "a row of a bank per channel": chain_q15pco_kernel, chain_f32pco_kernel
 //   msdr_chain_ncopc.hip   the same frames with the policy "a phase accumulator per channel": chain_q15pcn_kernel, chain_f32pcn_kernel
 //   msdr_chain_decpc.hip   that policy under a decimating tile loop: chain_q15pcnd_kernel, chain_f32pcnd_kernel
+//   msdr_chain_meter.hip   the S-meter's second step behind those kernels' metered flavours: meter_reduce_kernel
 //   msdr_chain_f32pcb.hip  the fp32 chain with per-channel settings at block cadence, one launch per call: chain_f32pcb_kernel
 //   msdr_chain_q15pcb.hip  the Q15 chain with per-channel settings at block cadence, one launch per call: chain_q15pcb_kernel
 // Host-side geometry helpers (LDS sizes, table formats) live with the kernels' headers; the launch geometry of the per-receiver chain kernels
@@ -82,6 +83,11 @@ int chain_dec_max(bool f32);
 int chain_dec_max_taps(bool f32, int D);
 hipError_t launch_chain_q15pcnd(hipStream_t stream, int num_cus, PcndParams p, PcLaunch *geo);
 hipError_t launch_chain_f32pcnd(hipStream_t stream, int num_cus, int time_segments, PcfndParams p, PcLaunch *geo);
+// ---- msdr_chain_meter.hip ----
+// meter_reduce_kernel<T> (msdr_chain_meter.hiph): d_meter[ch] = the sum of part[ch][0 .. nseg) in that order -- the S-meter of a call that the
+// per-receiver kernels above ran in nseg > 1 time segments (their launchers call it; uint64_t sums for Q15, double for F32)
+hipError_t launch_meter_reduce(hipStream_t stream, const unsigned long long *part, unsigned long long *d_meter, int channels, int nseg);
+hipError_t launch_meter_reduce(hipStream_t stream, const double *part, double *d_meter, int channels, int nseg);
 // ---- msdr_biquad_df1_pc.hip ----
 // biquad_df1_seq_pc_kernel<S, SEG> (msdr_biquad_df1_pc.hiph): stages = S = 1 .. 4 sections in CMSIS order on data [channels][n] (y may be x), every
 // channel with the 5 S coefficients of its own row of tab ([channels][20] floats).  nseg = 1: state_in may be state_out, seg_len / warm / scratch

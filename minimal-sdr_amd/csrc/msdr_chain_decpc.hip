@@ -39,7 +39,10 @@ hipError_t launch_chain_q15pcnd(hipStream_t stream, int num_cus, PcndParams p, P
     const int D = p.dec;          // (time_segments = 0: the Q15 chains do not look at the configuration's value)
     return dec_launch(stream, p, p.np > 0 && !(p.np & 7) && p.channels > 0 && p.n > 0 && p.mixer == kMixerNco && p.osc && p.sin_tab && !p.syncam_q, false, num_cus, 0,
                       (D & 1) ? 0 : (D % 8 == 0) ? 4 : (D % 4 == 0) ? 2 : 1,
-                      [](auto cpw, auto a) { return chain_q15pcnd_kernel<decltype(cpw)::value, decltype(a)::value>; }, geo);
+                      [&](auto cpw, auto a) {
+                          constexpr int CPW = decltype(cpw)::value, AL = decltype(a)::value;
+                          return p.meter ? chain_q15pcnd_meter_kernel<CPW, AL> : chain_q15pcnd_kernel<CPW, AL>;
+                      }, geo);
 }
 
 hipError_t launch_chain_f32pcnd(hipStream_t stream, int num_cus, int time_segments, PcfndParams p, PcLaunch *geo)
@@ -47,7 +50,10 @@ hipError_t launch_chain_f32pcnd(hipStream_t stream, int num_cus, int time_segmen
     const int D = p.dec;
     return dec_launch(stream, p, p.np > 0 && !(p.np & 3) && p.channels > 0 && p.n > 0 && p.mixer == kMixerNco && p.osc && p.sin_tab, true, num_cus, time_segments,
                       (D % 4 == 0) ? 4 : (D % 2 == 0) ? 2 : 1,
-                      [](auto cpw, auto a) { return chain_f32pcnd_kernel<decltype(cpw)::value, decltype(a)::value == 0 ? 1 : decltype(a)::value>; }, geo);          // (AL = 0 is Q15's)
+                      [&](auto cpw, auto a) {
+                          constexpr int CPW = decltype(cpw)::value, AL = decltype(a)::value == 0 ? 1 : decltype(a)::value;          // (AL = 0 is Q15's)
+                          return p.meter ? chain_f32pcnd_meter_kernel<CPW, AL> : chain_f32pcnd_kernel<CPW, AL>;
+                      }, geo);
 }
 
 }  // namespace msdr

@@ -12,14 +12,14 @@ hipError_t launch_chain_q15pcn(hipStream_t stream, int num_cus, PcnParams p, PcL
 {
     return pc_launch(stream, p, p.np > 0 && !(p.np & 7) && p.channels > 0 && p.n > 0 && p.mixer == kMixerNco && p.osc && p.sin_tab, num_cus, 0, kPcR,
                      [&](int cpw, int nw) { return pcn_lds_bytes(p.np, cpw, nw); },
-                     [](auto cpw) { return chain_q15pcn_kernel<decltype(cpw)::value>; }, geo);
+                     [&](auto cpw) { return p.meter ? chain_q15pcn_meter_kernel<decltype(cpw)::value> : chain_q15pcn_kernel<decltype(cpw)::value>; }, geo);
 }
 
 hipError_t launch_chain_f32pcn(hipStream_t stream, int num_cus, int time_segments, PcfnParams p, PcLaunch *geo)
 {
     return pc_launch(stream, p, p.np > 0 && !(p.np & 3) && p.channels > 0 && p.n > 0 && p.mixer == kMixerNco && p.osc && p.sin_tab, num_cus, time_segments, kPfR,
                      [&](int cpw, int nw) { return f32pcn_lds_bytes(p.np, cpw, nw); },
-                     [](auto cpw) { return chain_f32pcn_kernel<decltype(cpw)::value>; }, geo);
+                     [&](auto cpw) { return p.meter ? chain_f32pcn_meter_kernel<decltype(cpw)::value> : chain_f32pcn_kernel<decltype(cpw)::value>; }, geo);
 }
 
 }  // namespace msdr

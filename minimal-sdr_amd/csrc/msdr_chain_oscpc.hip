@@ -10,14 +10,14 @@ hipError_t launch_chain_q15pco(hipStream_t stream, int num_cus, PcParams p, PcLa
 {
     return pc_launch(stream, p, p.np > 0 && !(p.np & 7) && p.channels > 0 && p.n > 0 && p.osc_len > 0 && p.mixer == kMixerNco && p.osc, num_cus, 0, kPcR,
                      [&](int cpw, int nw) { return pco_lds_bytes(p.np, p.osc_len, cpw, nw); },
-                     [](auto cpw) { return chain_q15pco_kernel<decltype(cpw)::value>; }, geo);
+                     [&](auto cpw) { return p.meter ? chain_q15pco_meter_kernel<decltype(cpw)::value> : chain_q15pco_kernel<decltype(cpw)::value>; }, geo);
 }
 
 hipError_t launch_chain_f32pco(hipStream_t stream, int num_cus, int time_segments, PcfParams p, PcLaunch *geo)
 {
     return pc_launch(stream, p, p.np > 0 && !(p.np & 3) && p.channels > 0 && p.n > 0 && p.osc_len > 0 && p.mixer == kMixerNco && p.osc, num_cus, time_segments, kPfR,
                      [&](int cpw, int nw) { return f32pco_lds_bytes(p.np, p.osc_len, cpw, nw); },
-                     [](auto cpw) { return chain_f32pco_kernel<decltype(cpw)::value>; }, geo);
+                     [&](auto cpw) { return p.meter ? chain_f32pco_meter_kernel<decltype(cpw)::value> : chain_f32pco_kernel<decltype(cpw)::value>; }, geo);
 }
 
 }  // namespace msdr

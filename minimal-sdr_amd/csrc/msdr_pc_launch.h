@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "msdr_pc_geometry.h"
+#include "msdr_block.h"
 
 namespace msdr {
 
@@ -14,9 +15,18 @@ inline hipError_t pc_launch_geometry(hipStream_t stream, P &p, bool ok, const G 
     if (!ok) return hipErrorInvalidValue;
     const PcLaunch &l = g.launch;
     p.nseg = l.nseg; p.seg_len = g.seg_len; p.nw = g.nw;
+    // msdr_chain_set_meter (p.meter = d_meter; kernel_of picks the metered instantiation by it): one segment writes d_meter itself, more write
+    // the chain's partials [channels][nseg], which meter_reduce_kernel adds in segment order behind the kernel
+    auto *const d_meter = p.meter;
+    if (d_meter && l.nseg > 1) {
+        if (!p.meter_part || (long long)p.channels * l.nseg > p.meter_cap) return hipErrorInvalidValue;
+        p.meter = p.meter_part;
+    }
     pc_dispatch_cpw(l.cpw, [&](auto cpw) { hipLaunchKernelGGL(kernel_of(cpw), dim3(l.grid), dim3(l.block), l.lds_bytes, stream, p); });
     if (geo) *geo = l;
-    return hipGetLastError();
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !d_meter || l.nseg == 1) return e;
+    return launch_meter_reduce(stream, p.meter_part, d_meter, p.channels, l.nseg);
 }
 
 // The sliding-window kernels: pc_geometry with outs_per_lane outputs per lane and lds_bytes(cpw, nw).  time_segments as

@@ -136,6 +136,11 @@ struct PcParams {
     long long seg_len;         // a multiple of the tile (8 * 64 / channels per wave)
     int nw;                    // waves per workgroup
     const int *in_row;         // [channels]: channel ch hears row in_row[ch] of x (msdr_chain_set_input_rows), x being [n_inputs][n]; null: row ch
+    // msdr_chain_set_meter (msdr_chain_meter.hiph; read by the metered instantiations alone): the caller gives meter = d_meter [channels] (null:
+    // off) and the chain's partials buffer; the launcher points `meter` at where the main kernel writes entry ch * nseg + segment
+    unsigned long long *meter;
+    unsigned long long *meter_part;        // [meter_cap] partials for calls in more than one time segment
+    long long meter_cap;
 };
 
 // chain_f32pc_kernel (msdr_chain_f32pc.hiph): the fp32 chain / the arm_fir_f32 stage with per-channel coefficients
@@ -160,6 +165,9 @@ struct PcfParams {
     int nw;                    // waves per workgroup
     const int *in_row;         // [channels]: channel ch hears row in_row[ch] of x (msdr_chain_set_input_rows), x being [n_inputs][n]; null: row ch
                                // (chains only: the FIR stage leaves it null)
+    double *meter;             // msdr_chain_set_meter, as in PcParams: sums of squares in in_scale units
+    double *meter_part;
+    long long meter_cap;
 };
 
 // chain_q15pcn_kernel / chain_f32pcn_kernel (msdr_chain_ncopc.hiph): the two blocks above with the phase-accumulator oscillator's operands.

@@ -8,6 +8,7 @@
 // Every block is a block batch in HBM (AudioStream.h); update() enqueues kernels, never touches samples.
 #pragma once
 #include <atomic>
+#include <cstring>
 #include <vector>
 
 #include "AudioStream.h"
@@ -274,11 +275,13 @@ private:
 // ------------------------------------------------------------------------------------------------
 class AudioSDRDemodulator : public AudioStream {
 public:
-    AudioSDRDemodulator(void) : AudioStream(1, inputQueueArray), chain(nullptr), num_taps(0) {}
-    ~AudioSDRDemodulator() { if (chain) msdr_chain_destroy(chain); }
+    AudioSDRDemodulator(void) : AudioStream(1, inputQueueArray), chain(nullptr), num_taps(0), d_meter(nullptr), f32(false), in_scale(0.0f) {}
+    ~AudioSDRDemodulator() { if (chain) msdr_chain_destroy(chain); freeMeter(); }
     int begin(const msdr_chain_config &cfg)
     {
         if (chain) { msdr_chain_destroy(chain); chain = nullptr; }
+        freeMeter();
+        f32 = cfg.arith == MSDR_ARITH_F32; in_scale = cfg.in_scale != 0.0f ? cfg.in_scale : 1.0f / 32768.0f;
         const bool i16_audio = cfg.arith == MSDR_ARITH_Q15 || (cfg.arith == MSDR_ARITH_F32 && (cfg.flags & MSDR_CHAIN_OUT_I16));
         if (!i16_audio || cfg.channels != AudioGPU.channels()) return MSDR_STATUS_ARGUMENT_ERROR;
         num_taps = cfg.num_taps;
@@ -366,6 +369,37 @@ public:
         if (!chain || n_inputs > AudioGPU.channels()) return MSDR_STATUS_ARGUMENT_ERROR;
         return msdr_chain_set_input_rows(chain, n_inputs, rows);
     }
+    // the bank's S-meter (msdr_chain_set_meter; the sketch's to-do list begins with it, Minimal-SDR.ino:48-50): every tick measures each receiver's
+    // power behind its channel filter; the node owns the device buffer.  setMeter(false) switches the measurement off and frees it.
+    int setMeter(bool on)
+    {
+        if (!chain) return MSDR_STATUS_ARGUMENT_ERROR;
+        if (on && !d_meter) {
+            void *p = nullptr;
+            if (int rc = msdr_malloc(AudioGPU.context(), (size_t)AudioGPU.channels() * 8, &p)) return rc;
+            if (int rc = msdr_chain_set_meter(chain, p)) { msdr_free(AudioGPU.context(), p); return rc; }
+            d_meter = p;
+        } else if (!on && d_meter) {
+            if (int rc = msdr_chain_set_meter(chain, nullptr)) return rc;
+            freeMeter();
+        }
+        return 0;
+    }
+    // the last tick's level of every receiver in dBFS (msdr_meter_dbfs: 0 = a full-scale carrier at the tuned frequency), channels() doubles.
+    // Copies the meter back, so this one waits for the tick's kernels; -HUGE_VAL for a silent receiver.
+    int readLevels(double *dbfs)
+    {
+        if (!chain || !d_meter || !dbfs) return MSDR_STATUS_ARGUMENT_ERROR;
+        const uint32_t ch = AudioGPU.channels();
+        std::vector<uint64_t> raw(ch);
+        if (int rc = msdr_memcpy_d2h(AudioGPU.context(), raw.data(), d_meter, (size_t)ch * 8)) return rc;
+        for (uint32_t c = 0; c < ch; c++) {
+            double s;
+            if (f32) memcpy(&s, &raw[c], 8); else s = (double)raw[c];          // (F32 chains write doubles, Q15 chains exact integers)
+            dbfs[c] = msdr_meter_dbfs(s, AUDIO_BLOCK_SAMPLES, f32 ? 32768.0 * (double)in_scale : 32768.0);
+        }
+        return 0;
+    }
     virtual void update(void)
     {
         audio_block_t *in = receiveReadOnly();
@@ -380,7 +414,15 @@ public:
     }
 
 private:
+    void freeMeter(void)
+    {
+        if (d_meter) msdr_free(AudioGPU.context(), d_meter);
+        d_meter = nullptr;
+    }
     audio_block_t *inputQueueArray[1];
     msdr_chain *chain;
     uint32_t num_taps;
+    void *d_meter;              // setMeter(true): [channels()] 8-byte sums, the node's own
+    bool f32;                   // the chain's arithmetic and int16 -> float scale, for readLevels
+    float in_scale;
 };

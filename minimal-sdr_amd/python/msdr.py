@@ -34,6 +34,7 @@ FLAVOUR_OSC_PC = 0x20000
 FLAVOUR_SHARED_IF = 0x40000
 FLAVOUR_NCO_PC = 0x80000
 FLAVOUR_DECIMATED = 0x100000
+FLAVOUR_METER = 0x200000
 MAX_DECIMATION_Q15, MAX_DECIMATION_F32 = 60, 59
 FE_DCBLOCK, FE_AMP, FE_AGC, FE_ALL = 1, 2, 4, 7
 
@@ -112,6 +113,9 @@ def load_library(path=None):
                        ("msdr_chain_get_nco", [_p, C.c_uint32, _p, _p]),
                        ("msdr_chain_set_decimation", [_p, C.c_uint32]),
                        ("msdr_chain_get_decimation", [_p, _p]),
+                       ("msdr_chain_set_meter", [_p, _p]),
+                       ("msdr_chain_get_meter", [_p, _p]),
+                       ("msdr_meter_dbfs", [C.c_double, C.c_uint64, C.c_double]),
                        ("msdr_nco_step", [C.c_double, C.c_double]),
                        ("msdr_nco_table", [_p]),
                        ("msdr_nco_q15", [_p, C.c_size_t, _p, _p]),
@@ -119,6 +123,8 @@ def load_library(path=None):
                        ("msdr_chain_get_cmsis_state", [_p, C.c_uint32, _p])):
             if hasattr(_lib, n):
                 getattr(_lib, n).argtypes = sig
+        if hasattr(_lib, "msdr_meter_dbfs"):
+            _lib.msdr_meter_dbfs.restype = C.c_double
         if hasattr(_lib, "msdr_nco_step"):
             _lib.msdr_nco_step.restype = C.c_uint32
             _lib.msdr_nco_table.restype = None
@@ -552,6 +558,13 @@ def _nco_words(what, a, count):
     return np.ascontiguousarray(t, np.uint32)
 
 
+def meter_dbfs(sum_sq, n_out, full_scale=32768.0):
+    """msdr_meter_dbfs: 10 log10((sum_sq / n_out) / (full_scale^2 / 4)) -- a Chain.set_meter() entry over n_out outputs in dB relative to a
+    full-scale carrier at the tuned frequency (full_scale = 32768 for Q15, 32768 * in_scale for F32); -inf for sum_sq <= 0 or n_out == 0.
+    Host only."""
+    return float(load_library().msdr_meter_dbfs(float(sum_sq), int(n_out), float(full_scale)))
+
+
 def nco_step(f_hz, fs_hz=24000.0):
     """msdr_nco_step: llround(f / fs * 2^32) mod 2^32 -- the step of a phase-accumulator oscillator at f_hz (negative wraps).  Host only."""
     return int(load_library().msdr_nco_step(float(f_hz), float(fs_hz)))
@@ -916,6 +929,21 @@ class Chain(_Instance):
         d = C.c_uint32(0)
         _ck(self.ctx.lib.msdr_chain_get_decimation(self.h, C.byref(d)))
         return d.value
+
+    def set_meter(self, d_meter):
+        """The S-meter: from the next process() on every call overwrites d_meter[channels] -- a device buffer of 8-byte entries (DeviceArray /
+        DeviceView / address), uint64 for Q15 chains, float64 for F32 -- with each channel's sum of I^2 + Q^2 behind the channel filter over
+        the call's outputs, stream-ordered.  None switches it off.  The per-channel kernel family from the first call on; every state kept
+        (msdr_chain_set_meter)."""
+        ptr = None if d_meter is None else int(getattr(d_meter, "ptr", d_meter))
+        _ck(self.ctx.lib.msdr_chain_set_meter(self.h, _p(ptr)))
+        self._meter = d_meter          # (the buffer stays the caller's; this keeps a DeviceArray alive while the kernels write it)
+
+    def meter(self):
+        """the address of the meter buffer in force, None on a chain without one (msdr_chain_get_meter)"""
+        p = _p()
+        _ck(self.ctx.lib.msdr_chain_get_meter(self.h, C.byref(p)))
+        return p.value
 
     def set_block_kernel(self, on):
         """F32: a block-cadence call of a chain in per-channel mode as ONE launch (chain_f32pcb_kernel: demodulator, CMSIS-order cascade, int16

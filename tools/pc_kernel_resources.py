@@ -65,7 +65,9 @@ def main():
     print("|---" * (len(cols) + (3 if old else 1)) + "|")
     for k in sorted(new):
         row = "| `%s` | " % k + " | ".join(str(v) for v in new[k])
-        if old:
+        if old and k not in old:          # an instantiation the parent does not have (e.g. the metered flavours)
+            row += " | %d / - | new" % ((new[k][0] + 7) // 8 * 8)
+        elif old:
             o = old[k]
             diff = ", ".join("%s %d -> %d" % (c, ov, nv) for c, ov, nv in zip(cols, o, new[k]) if ov != nv)
             row += " | %d / %d | %s" % ((new[k][0] + 7) // 8 * 8, (o[0] + 7) // 8 * 8, "same figures" if not diff else "parent -> this: " + diff)
