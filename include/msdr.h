@@ -758,6 +758,30 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   -HUGE_VAL for sum_sq <= 0 or n_out == 0.  0 dBFS is a full-scale real carrier at the tuned frequency behind a unity-gain channel
  *   filter (I^2 + Q^2 = A^2 / 4): round(32767 sin(2 pi 40 t / 128 + 0.3)) against bin 40 of 128 behind calc_FIR_coeffs(102, 2500 Hz)
  *   reads -0.005 dBFS from the second block on.
+ * msdr_chain_set_iq_out: what a digital down-converter hands out -- the complex baseband I[m], Q[m] behind the channel filter at fs / D, for
+ *   decoders of digital modes and every demodulator this library does not have (the reference's feature list ends with "Decoding of time
+ *   signals or other digital modes [tbd]", Minimal-SDR.ino:40).  The per-receiver kernels hold the pair in registers where their demodulator
+ *   consumes it; with a buffer set they store it too, at no extra pass over the IF stream.
+ *   d_iq: device memory of the caller, [channels][pitch] pairs {I, Q}, interleaved; NULL = off (the default).
+ *     Q15   two int16_t per pair: ssat16(acc >> 15) of each stream
+ *     F32   two floats per pair (also under MSDR_CHAIN_OUT_I16): the two fp32 sums in in_scale units
+ *   For a call of msdr_chain_process with n_out = n_samples / D outputs per channel, pair m < n_out of row c is I_c[m], Q_c[m] of the meter's
+ *   definition above -- the two FIR outputs the demodulator of output m receives, whatever the channel's mode.  I is the stream filtered
+ *   with coeffs_i, the oracle's i_out: LSB audio is I - Q, USB audio I + Q.  Pairs m >= n_out of a row are never written.
+ *   From the next msdr_chain_process on every successful call OVERWRITES pairs 0 .. n_out - 1 of all rows, on the chain's stream, without
+ *   synchronising; a call that returns an error writes nothing.  n_out > pitch is MSDR_STATUS_LENGTH_ERROR: nothing enqueued, no state moved.
+ *   d_iq must be 16-byte aligned and pitch a non-zero multiple of 8 (a lane's 8 outputs are whole 16-byte slots of a row); chains in
+ *   phase-accumulator mode only (msdr_chain_set_nco_channels has been called -- msdr_chain_set_decimation's scope rule), Q15 and F32.
+ *   Anything else, a NULL chain included, is MSDR_STATUS_ARGUMENT_ERROR, nothing changed.  The setting survives everything the meter pointer
+ *   survives: msdr_chain_reset and init_fir, every tap / NCO / node / cascade / mode setter, msdr_chain_set_input_rows,
+ *   msdr_chain_set_decimation, msdr_chain_set_meter; it combines with all of them in either order.
+ *   I/Q-only calls: while a buffer is set msdr_chain_process(chain, d_if, NULL, n) is accepted (without one NULL stays refused).  Mixer, FIR
+ *   pair, history, the chain's time, the oscillator generations, the I/Q store and the meter (if set) run as always; the demodulator and the
+ *   audio store, the Q15 nodes, the PLL / LMS passes, the fp32 cascade and the int16 conversion do not run and their states are untouched.
+ *   The length rules of an audio call apply unchanged.
+ *   Reporting: msdr_chain_get_info().kernel keeps its names; on fp32 chains flavour carries MSDR_FLAVOUR_IQ_OUT exactly while a buffer is
+ *   set.  Graphs stay refused, as on every chain in this mode.
+ * msdr_chain_get_iq_out: the buffer and pitch in force (NULL, 0 on a chain without one); either output may be NULL.
  * msdr_nco_step (host only): llround(f_hz / fs_hz * 2^32) mod 2^32; a negative frequency wraps (-6000 at 24000: 0xC0000000).
  * msdr_nco_table (host only): T[i] = (int16) lround(32767 sin(2 pi i / 1024)), i = 0 .. 1024, T[1024] = 0.
  * msdr_nco_q15 (host only; what the kernels compute): for each uint32 phase, i = phase >> 22, f = (phase >> 6) & 0xFFFF,
@@ -775,6 +799,8 @@ int msdr_chain_get_decimation(msdr_chain *chain, uint32_t *D);
 int msdr_chain_set_meter(msdr_chain *chain, void *d_meter);   /* NULL = off (default) */
 int msdr_chain_get_meter(msdr_chain *chain, void **d_meter);
 double msdr_meter_dbfs(double sum_sq, uint64_t n_out, double full_scale);
+int msdr_chain_set_iq_out(msdr_chain *chain, void *d_iq, uint64_t pitch);   /* NULL = off (default) */
+int msdr_chain_get_iq_out(msdr_chain *chain, void **d_iq, uint64_t *pitch); /* either may be NULL */
 int msdr_chain_set_taps(msdr_chain *chain, uint32_t tapset, const void *coeffs_i, const void *coeffs_q);
 int msdr_chain_set_taps_channels(msdr_chain *chain, uint32_t first_channel, uint32_t count,
                                  const q15_t *coeffs_i, const q15_t *coeffs_q);
@@ -850,6 +876,9 @@ enum { MSDR_FLAVOUR_DECIMATED = 0x100000u };
 /* And another: the demodulator kernel measured the channels' power -- the metered flavour of a per-receiver kernel, msdr_chain_set_meter with
  * a buffer (always beside MSDR_FLAVOUR_TAPS_PC). */
 enum { MSDR_FLAVOUR_METER = 0x200000u };
+/* And another: the demodulator kernel stored the pair behind the channel filter -- the IQ flavour of a phase-accumulator kernel,
+ * msdr_chain_set_iq_out with a buffer (always beside MSDR_FLAVOUR_NCO_PC). */
+enum { MSDR_FLAVOUR_IQ_OUT = 0x400000u };
 int msdr_chain_get_info(msdr_chain *chain, msdr_chain_info *info);
 /* Which kernel ran the serial recurrences (introspection for tests: tests/q15_ladder_cases.py is the table of every branch below, and
  * tests/test_gpu_q15_ladders.py holds each of them to the oracle bit for bit).  Each getter returns a static string -- the kernel's name

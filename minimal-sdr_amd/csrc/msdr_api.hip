@@ -2520,6 +2520,11 @@ struct msdr_chain {
     void *d_meter_part = nullptr;         // partials [meter_part_cap] of calls in more than one time segment, the chain's own
     size_t meter_part_cap = 0;
     uint64_t meter_epoch = 0;             // bumped by every msdr_chain_set_meter call: part of a HIP graph's key
+    // msdr_chain_set_iq_out: the caller's [channels][iq_pitch] pairs {I, Q} behind the channel filter (two int16 for Q15, two floats for F32),
+    // written by the IQ flavours of the phase-accumulator kernels (msdr_chain_iq.hiph) in every call while it is set; with it set a call
+    // without an audio batch is accepted (chains with nco_active only, which no graph captures)
+    void *d_iq = nullptr;
+    uint64_t iq_pitch = 0;
     msdr_chain_info info;
     // optional per-launch timing of the main kernel
     bool timing;
@@ -4082,6 +4087,13 @@ static void pc_params_meter(Q &q, const msdr_chain *c)
 {
     q.meter = (decltype(q.meter))c->d_meter; q.meter_part = (decltype(q.meter_part))c->d_meter_part; q.meter_cap = (long long)c->meter_part_cap;
 }
+// msdr_chain_set_iq_out: the two fields of PcnParams / PcfnParams (the launchers pick the IQ instantiations by q.iq); only chains with the
+// phase-accumulator oscillator have a buffer
+template <typename Q>
+static void pc_params_iq(Q &q, const msdr_chain *c)
+{
+    q.iq = (decltype(q.iq))c->d_iq; q.iq_pitch = (long long)c->iq_pitch;
+}
 static void pc_geometry_of(const PcLaunch &geo, ChainLaunch &r)
 {
     r.grid = geo.grid; r.block = geo.block; r.lds_bytes = geo.lds_bytes; r.nseg = geo.nseg; r.tile = geo.tile;
@@ -4114,6 +4126,7 @@ static int chain_launch_f32pc(msdr_chain *c, const ChainDecision &, const ChainP
     pc_params(q, c, p);
     q.out = (float *)p.out; q.taps = c->d_pcf_taps; q.mixer = c->mixer; q.in_scale = c->in_scale; q.osc_hist = p.osc_hist;
     pc_params_meter(q, c);
+    pc_params_iq(q, c);
     PcLaunch geo;
     if (c->nco_active && c->decim > 1) {          // msdr_chain_set_decimation: p.out is [channels][n / D]
         PcfndParams qd;
@@ -4138,7 +4151,7 @@ static int chain_launch_f32pc(msdr_chain *c, const ChainDecision &, const ChainP
     }
     pc_geometry_of(geo, r);
     r.flavour |= MSDR_FLAVOUR_TAPS_PC | (geo.nseg > 1 ? MSDR_FLAVOUR_SEGMENTED : 0u) | (c->n_inputs ? (uint32_t)MSDR_FLAVOUR_SHARED_IF : 0u) |
-                 (c->d_meter ? (uint32_t)MSDR_FLAVOUR_METER : 0u);
+                 (c->d_meter ? (uint32_t)MSDR_FLAVOUR_METER : 0u) | (c->d_iq ? (uint32_t)MSDR_FLAVOUR_IQ_OUT : 0u);
     return 0;
 }
 
@@ -4308,6 +4321,7 @@ static int chain_launch_q15pc(msdr_chain *c, const ChainDecision &, const ChainP
     pc_params(q, c, p);
     q.out = (short *)p.out; q.taps = c->d_pc_taps; q.mixer = c->mixer; q.sqrt_kind = c->sqrt_kind; q.syncam_q = p.syncam_q; q.osc_hist = p.osc_hist;
     pc_params_meter(q, c);
+    pc_params_iq(q, c);
     PcLaunch geo;
     if (c->nco_active && c->decim > 1) {          // msdr_chain_set_decimation: p.out is [channels][n / D]
         PcndParams qd;
@@ -4392,7 +4406,10 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
     if (int rc = bind(c->ctx)) return rc;
     if (n_samples == 0) return 0;
-    if (!d_if || !d_audio) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null buffer");
+    // msdr_chain_set_iq_out: with a buffer set a call may be for the pairs alone (d_audio null) -- demodulator, audio store and every pass
+    // behind them stay out of it, their states untouched
+    if (!d_if || (!d_audio && !c->d_iq)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null buffer");
+    const bool audio = d_audio != nullptr;
     if (n_samples > (1ull << 31) - 4096) return fail(MSDR_STATUS_LENGTH_ERROR, "n_samples too large for one call");
     const bool f32 = (c->arith == MSDR_ARITH_F32);
     if (!f32 && c->nnodes && (n_samples & 1u))
@@ -4404,6 +4421,8 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     const uint64_t n_out = n_samples / c->decim;
     if (!f32 && c->nnodes && (n_out & 1u))
         return fail(MSDR_STATUS_LENGTH_ERROR, "AudioFilterBiquad processes sample pairs: n_samples / decimation (%llu) must be even; nothing enqueued", (unsigned long long)n_out);
+    if (c->d_iq && n_out > c->iq_pitch)
+        return fail(MSDR_STATUS_LENGTH_ERROR, "I/Q output: %llu outputs per channel do not fit a row of %llu pairs (msdr_chain_set_iq_out); nothing enqueued", (unsigned long long)n_out, (unsigned long long)c->iq_pitch);
 
     // ---- decide, prepare
     ChainDecision d = chain_decide(c, d_if, d_audio, n_samples);
@@ -4411,6 +4430,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     ChainParams p;
     ChainLaunch r;
     if (int rc = chain_prepare(c, d, t, d_if, d_audio, n_samples, p, r)) return rc;
+    if (!audio) { p.out = nullptr; p.syncam_q = nullptr; }          // an I/Q-only call: the IQ instantiations skip demodulator and audio store
     void *const fout = p.out;                                    // where the fp32 passes of this call read and write the audio
     if (c->dry_run) {            // msdr_chain_graph_create: everything a block-cadence call needs from the host is in place now; make no launch
         const char *why = chain_not_capturable(c, d, n_samples);
@@ -4442,29 +4462,29 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     if (e0) { HIP_TRY(hipEventRecord(e1, c->ctx->stream)); c->events.emplace_back(e0, e1); }
 
     // ---- the passes behind it: n_out samples per channel (n_samples / decimation; the two are equal without msdr_chain_set_decimation)
-    if (c->seq_bq && d.path != kPathF32Pcb) // F32, ill-conditioned cascade: arm_biquad_cascade_df1_f32 in CMSIS order, in place on the audio (chain_f32pcb_kernel ran it itself)
+    if (c->seq_bq && d.path != kPathF32Pcb && audio) // F32, ill-conditioned cascade: arm_biquad_cascade_df1_f32 in CMSIS order, in place on the audio (chain_f32pcb_kernel ran it itself)
         { if (int rc2 = msdr_biquad_df1_f32_process(c->seq_bq, (const float *)fout, (float *)fout, (uint32_t)n_out)) return rc2; r.flavour |= MSDR_FLAVOUR_SEQ_CASCADE | (c->seq_bq->per_channel ? (uint32_t)MSDR_FLAVOUR_CASCADE_PC : 0u); }
 
-    if (d.pll_active)          // SYNCAM channels: I (in d_audio) and Q (scratch) -> PLL demodulator -> audio, before the biquad nodes
+    if (d.pll_active && audio)          // SYNCAM channels: I (in d_audio) and Q (scratch) -> PLL demodulator -> audio, before the biquad nodes
         if (int rc2 = msdr_syncam_q15(c->pll, c->d_mode, (const q15_t *)d_audio, c->d_pll_q, (q15_t *)d_audio, (uint32_t)n_out)) return rc2;
 
-    if (d.anr_active)          // LMS notch / noise reduction (.ino:702-770), then the biquad nodes
+    if (d.anr_active && audio)          // LMS notch / noise reduction (.ino:702-770), then the biquad nodes
         if (int rc2 = msdr_anr_q15(c->anr, c->d_anr_on, c->anr_all, (q15_t *)d_audio, (uint32_t)n_out)) return rc2;
 
-    if (d.path == kPathQ15Pcb) { /* (chain_q15pcb_kernel ran the nodes as its third phase, on the same records) */ }
+    if (d.path == kPathQ15Pcb || !audio) { /* (chain_q15pcb_kernel ran the nodes as its third phase, on the same records; an I/Q-only call has no audio for them) */ }
     else if (c->nnodes == 2 && !d.nodes_fused) {
         if (int rc2 = chain_two_nodes(c, d_audio, n_out, &r.node_kname)) return rc2;
     } else if (c->nnodes == 1) {
         if (int rc2 = msdr_biquad_q15_update(c->nodes[0], (q15_t *)d_audio, (uint32_t)n_out)) return rc2;
         r.node_kname = c->nodes[0]->last_kernel;
     }
-    c->node_kernel = r.node_kname;
+    if (audio) c->node_kernel = r.node_kname;
 
     // rows f2 / f3 inside the fp32 chain: PLL / LMS channels are redone behind the main kernel (before the history moves on: a rebuilt
     // auxiliary chain takes over the history and table position this call started from)
     // (no chain with a decimator has such channels: msdr_chain_set_nco_channels and msdr_chain_set_anr refuse them)
-    if (f32) if (int rc2 = chain_post_run(c, d_if, (float *)fout, n_samples)) return rc2;
-    if (d.i16 == kI16ViaScratch) {
+    if (f32 && audio) if (int rc2 = chain_post_run(c, d_if, (float *)fout, n_samples)) return rc2;
+    if (d.i16 == kI16ViaScratch && audio) {
         const long long total = (long long)c->channels * (long long)n_out;
         hipLaunchKernelGGL(f32_to_q15_kernel, dim3(grid_1d((total + 3) / 4)), dim3(256), 0, c->ctx->stream, (const float *)fout, (short *)d_audio, total);
         if (int rc2 = launch_check("f32_to_q15_kernel")) return rc2;
@@ -4892,6 +4912,7 @@ static int chain_rebuild(msdr_chain *c, const ChainCfgStore &edited, void **stea
     n->nco_active = c->nco_active; std::swap(n->d_nco_bank, c->d_nco_bank); std::swap(n->d_nco_tab, c->d_nco_tab);
     n->h_nco_base.swap(c->h_nco_base); n->h_nco_step.swap(c->h_nco_step); n->nco_T = c->nco_T; n->hist_clear = c->hist_clear;
     n->decim = c->decim;          // (msdr_chain_set_decimation holds through every rebuild)
+    n->d_iq = c->d_iq; n->iq_pitch = c->iq_pitch;          // (and so does msdr_chain_set_iq_out)
     std::swap(*c, *n);
     if (steal_osc) { *steal_osc = n->d_osc; n->d_osc = nullptr; }
     chain_free(n);
@@ -5408,6 +5429,29 @@ extern "C" int msdr_chain_get_decimation(msdr_chain *c, uint32_t *D)
 {
     if (!c || !D) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
     *D = c->decim;
+    return 0;
+}
+
+// What a down-converter hands out: from the next call on the IQ flavours of the phase-accumulator kernels (msdr_chain_iq.hiph) store the pair
+// behind the channel filter of every output to d_iq, on the chain's stream.  A switch of the host's, read by the next msdr_chain_process,
+// under msdr_chain_set_decimation's scope rule.  Everything that can fail happens before anything changes.
+extern "C" int msdr_chain_set_iq_out(msdr_chain *c, void *d_iq, uint64_t pitch)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (!c->nco_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "I/Q output: only on a chain with the phase-accumulator oscillator (msdr_chain_set_nco_channels); nothing changed");
+    if (d_iq) {
+        if (reinterpret_cast<uintptr_t>(d_iq) & 15) return fail(MSDR_STATUS_ARGUMENT_ERROR, "I/Q output: d_iq is written in 16-byte slots: it must be 16-byte aligned; nothing changed");
+        if (pitch == 0 || (pitch & 7)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "I/Q output: pitch %llu: a non-zero multiple of 8 pairs (a lane's 8 outputs are whole 16-byte slots of a row); nothing changed", (unsigned long long)pitch);
+    }
+    c->d_iq = d_iq; c->iq_pitch = d_iq ? pitch : 0;
+    return 0;
+}
+
+extern "C" int msdr_chain_get_iq_out(msdr_chain *c, void **d_iq, uint64_t *pitch)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (d_iq) *d_iq = c->d_iq;
+    if (pitch) *pitch = c->iq_pitch;
     return 0;
 }
 

@@ -12,6 +12,7 @@
 //   msdr_chain_ncopc.hip   the same frames with the policy "a phase accumulator per channel": chain_q15pcn_kernel, chain_f32pcn_kernel
 //   msdr_chain_decpc.hip   that policy under a decimating tile loop: chain_q15pcnd_kernel, chain_f32pcnd_kernel
 //   msdr_chain_meter.hip   the S-meter's second step behind those kernels' metered flavours: meter_reduce_kernel
+//                          (the baseband I/Q output, msdr_chain_iq.hiph, is a flavour of the four phase-accumulator kernels in their own units: chain_*_iq_kernel, chain_*_iq_meter_kernel)
 //   msdr_chain_f32pcb.hip  the fp32 chain with per-channel settings at block cadence, one launch per call: chain_f32pcb_kernel
 //   msdr_chain_q15pcb.hip  the Q15 chain with per-channel settings at block cadence, one launch per call: chain_q15pcb_kernel
 // Host-side geometry helpers (LDS sizes, table formats) live with the kernels' headers; the launch geometry of the per-receiver chain kernels

@@ -176,10 +176,16 @@ struct PcfParams {
 struct PcnParams : PcParams {
     const unsigned *sin_tab;   // [1024] packed sine table (msdr_nco.h: nco_pack), copied to LDS once per workgroup
     unsigned t0;               // chain time of sample 0 of this call: the low 32 bits of the sample count since msdr_chain_reset
+    // msdr_chain_set_iq_out (msdr_chain_iq.hiph; read by the IQ instantiations alone, which the launchers pick by it): [channels][iq_pitch]
+    // pairs {I, Q} of two int16, 16-byte aligned, iq_pitch a multiple of 8; null: off.  In those instantiations a null `out` skips the audio.
+    int *iq;
+    long long iq_pitch;
 };
 struct PcfnParams : PcfParams {
     const unsigned *sin_tab;
     unsigned t0;
+    float *iq;                 // msdr_chain_set_iq_out, as in PcnParams: pairs of two floats ([channels][iq_pitch][2])
+    long long iq_pitch;
 };
 
 // chain_q15pcnd_kernel / chain_f32pcnd_kernel (msdr_chain_decpc.hiph): the two blocks above with a decimator behind the FIR pair.  x, n, t0

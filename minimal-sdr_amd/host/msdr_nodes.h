@@ -275,12 +275,13 @@ private:
 // ------------------------------------------------------------------------------------------------
 class AudioSDRDemodulator : public AudioStream {
 public:
-    AudioSDRDemodulator(void) : AudioStream(1, inputQueueArray), chain(nullptr), num_taps(0), d_meter(nullptr), f32(false), in_scale(0.0f) {}
-    ~AudioSDRDemodulator() { if (chain) msdr_chain_destroy(chain); freeMeter(); }
+    AudioSDRDemodulator(void) : AudioStream(1, inputQueueArray), chain(nullptr), num_taps(0), d_meter(nullptr), d_iq(nullptr), f32(false), in_scale(0.0f) {}
+    ~AudioSDRDemodulator() { if (chain) msdr_chain_destroy(chain); freeMeter(); freeIq(); }
     int begin(const msdr_chain_config &cfg)
     {
         if (chain) { msdr_chain_destroy(chain); chain = nullptr; }
         freeMeter();
+        freeIq();
         f32 = cfg.arith == MSDR_ARITH_F32; in_scale = cfg.in_scale != 0.0f ? cfg.in_scale : 1.0f / 32768.0f;
         const bool i16_audio = cfg.arith == MSDR_ARITH_Q15 || (cfg.arith == MSDR_ARITH_F32 && (cfg.flags & MSDR_CHAIN_OUT_I16));
         if (!i16_audio || cfg.channels != AudioGPU.channels()) return MSDR_STATUS_ARGUMENT_ERROR;
@@ -400,6 +401,38 @@ public:
         }
         return 0;
     }
+    // the bank's baseband output (msdr_chain_set_iq_out; the sketch's feature list ends with "Decoding of time signals or other digital modes [tbd]",
+    // Minimal-SDR.ino:40): every tick stores each receiver's pairs {I, Q} behind its channel filter; the node owns the device buffer,
+    // [channels()][AUDIO_BLOCK_SAMPLES] pairs (two int16 on Q15 chains, two floats on F32).  After setNco() only.  setIqOut(false) switches the
+    // output off and frees the buffer.
+    int setIqOut(bool on)
+    {
+        if (!chain) return MSDR_STATUS_ARGUMENT_ERROR;
+        if (on && !d_iq) {
+            void *p = nullptr;
+            if (int rc = msdr_malloc(AudioGPU.context(), iqBytes(), &p)) return rc;
+            if (int rc = msdr_chain_set_iq_out(chain, p, AUDIO_BLOCK_SAMPLES)) { msdr_free(AudioGPU.context(), p); return rc; }
+            d_iq = p;
+        } else if (!on && d_iq) {
+            if (int rc = msdr_chain_set_iq_out(chain, nullptr, 0)) return rc;
+            freeIq();
+        }
+        return 0;
+    }
+    // the buffer and pitch the chain writes to (msdr_chain_get_iq_out): for kernels of the caller's that consume the pairs on the device
+    int iqOut(void **d_iq_out, uint64_t *pitch) { return chain ? msdr_chain_get_iq_out(chain, d_iq_out, pitch) : MSDR_STATUS_ARGUMENT_ERROR; }
+    // the last tick's pairs of every receiver: `pairs` takes the whole buffer, [channels()][AUDIO_BLOCK_SAMPLES] pairs, of which the first
+    // *n_out = AUDIO_BLOCK_SAMPLES / decimation of each row are the tick's (the rest is whatever an earlier tick left).  Copies the buffer
+    // back, so this one waits for the tick's kernels.  n_out may be nullptr.
+    int readIq(void *pairs, uint32_t *n_out)
+    {
+        if (!chain || !d_iq || !pairs) return MSDR_STATUS_ARGUMENT_ERROR;
+        uint32_t D = 1;
+        if (int rc = msdr_chain_get_decimation(chain, &D)) return rc;
+        if (int rc = msdr_memcpy_d2h(AudioGPU.context(), pairs, d_iq, iqBytes())) return rc;
+        if (n_out) *n_out = AUDIO_BLOCK_SAMPLES / D;
+        return 0;
+    }
     virtual void update(void)
     {
         audio_block_t *in = receiveReadOnly();
@@ -419,10 +452,17 @@ private:
         if (d_meter) msdr_free(AudioGPU.context(), d_meter);
         d_meter = nullptr;
     }
+    size_t iqBytes(void) const { return (size_t)AudioGPU.channels() * AUDIO_BLOCK_SAMPLES * (f32 ? 2 * sizeof(float) : 2 * sizeof(int16_t)); }
+    void freeIq(void)
+    {
+        if (d_iq) msdr_free(AudioGPU.context(), d_iq);
+        d_iq = nullptr;
+    }
     audio_block_t *inputQueueArray[1];
     msdr_chain *chain;
     uint32_t num_taps;
     void *d_meter;              // setMeter(true): [channels()] 8-byte sums, the node's own
-    bool f32;                   // the chain's arithmetic and int16 -> float scale, for readLevels
+    void *d_iq;                 // setIqOut(true): [channels()][AUDIO_BLOCK_SAMPLES] pairs {I, Q}, the node's own
+    bool f32;                   // the chain's arithmetic and int16 -> float scale, for readLevels and the size of a pair
     float in_scale;
 };

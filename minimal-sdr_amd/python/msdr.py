@@ -35,6 +35,7 @@ FLAVOUR_SHARED_IF = 0x40000
 FLAVOUR_NCO_PC = 0x80000
 FLAVOUR_DECIMATED = 0x100000
 FLAVOUR_METER = 0x200000
+FLAVOUR_IQ_OUT = 0x400000
 MAX_DECIMATION_Q15, MAX_DECIMATION_F32 = 60, 59
 FE_DCBLOCK, FE_AMP, FE_AGC, FE_ALL = 1, 2, 4, 7
 
@@ -116,6 +117,8 @@ def load_library(path=None):
                        ("msdr_chain_set_meter", [_p, _p]),
                        ("msdr_chain_get_meter", [_p, _p]),
                        ("msdr_meter_dbfs", [C.c_double, C.c_uint64, C.c_double]),
+                       ("msdr_chain_set_iq_out", [_p, _p, C.c_uint64]),
+                       ("msdr_chain_get_iq_out", [_p, _p, _p]),
                        ("msdr_nco_step", [C.c_double, C.c_double]),
                        ("msdr_nco_table", [_p]),
                        ("msdr_nco_q15", [_p, C.c_size_t, _p, _p]),
@@ -837,9 +840,9 @@ class Chain(_Instance):
         self.h = h
 
     def process(self, d_if, d_audio, n):
-        """d_if / d_audio: DeviceArray or raw device pointers (int)."""
+        """d_if / d_audio: DeviceArray or raw device pointers (int).  d_audio None: an I/Q-only call (accepted while set_iq_out() has a buffer)."""
         pi = d_if.ptr if hasattr(d_if, "ptr") else int(d_if)
-        po = d_audio.ptr if hasattr(d_audio, "ptr") else int(d_audio)
+        po = None if d_audio is None else d_audio.ptr if hasattr(d_audio, "ptr") else int(d_audio)
         _ck(self.ctx.lib.msdr_chain_process(self.h, pi, po, n))
 
     def graph(self, d_ifs, d_audios, n):
@@ -944,6 +947,21 @@ class Chain(_Instance):
         p = _p()
         _ck(self.ctx.lib.msdr_chain_get_meter(self.h, C.byref(p)))
         return p.value
+
+    def set_iq_out(self, d_iq, pitch=0):
+        """Baseband I/Q output: from the next process() on every call overwrites pairs 0 .. n_out - 1 of every row of d_iq[channels][pitch] -- a
+        16-byte aligned device buffer (DeviceArray / DeviceView / address) of interleaved pairs {I, Q}, two int16 for Q15 chains, two float32
+        for F32, pitch a non-zero multiple of 8 -- with the two FIR outputs behind each channel's filter, stream-ordered.  None switches it
+        off.  While it is set process(d_if, None, n) is an I/Q-only call.  Chains with set_nco_channels only (msdr_chain_set_iq_out)."""
+        ptr = None if d_iq is None else int(getattr(d_iq, "ptr", d_iq))
+        _ck(self.ctx.lib.msdr_chain_set_iq_out(self.h, _p(ptr), C.c_uint64(int(pitch))))
+        self._iq_out = d_iq          # (the buffer stays the caller's; this keeps a DeviceArray alive while the kernels write it)
+
+    def iq_out(self):
+        """(the address of the I/Q buffer in force or None, its pitch in pairs) (msdr_chain_get_iq_out)"""
+        p, pitch = _p(), C.c_uint64()
+        _ck(self.ctx.lib.msdr_chain_get_iq_out(self.h, C.byref(p), C.byref(pitch)))
+        return p.value, pitch.value
 
     def set_block_kernel(self, on):
         """F32: a block-cadence call of a chain in per-channel mode as ONE launch (chain_f32pcb_kernel: demodulator, CMSIS-order cascade, int16
