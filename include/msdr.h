@@ -880,6 +880,14 @@ enum { MSDR_FLAVOUR_METER = 0x200000u };
  * msdr_chain_set_iq_out with a buffer (always beside MSDR_FLAVOUR_NCO_PC). */
 enum { MSDR_FLAVOUR_IQ_OUT = 0x400000u };
 int msdr_chain_get_info(msdr_chain *chain, msdr_chain_info *info);
+/* The wave-stream kernels read the run geometry of a tap table (which chunks of the window each accumulator walks, which runs merge their first
+ * and last step) from the table's header -- or, for the geometries the library instantiates, have it as compile-time constants: the same
+ * products in the same order, bit-identical results, fewer instructions.  The host compares every table header it builds (create and every
+ * live update) with the instantiated geometries and launches such a kernel only where every table the launch can meet has that geometry.
+ * *id = what the last call ran: 0 = every launch read the headers (also before the first call, on every other kernel path, and on a chain
+ * created with MSDR_MFW_GEOM=0 in the environment); 1 = envelope tables behind the exact Fs/4 mixer, 256 taps, two-section cascade with a
+ * row-local section; 2 = the same with 512 taps.  msdr_chain_info is as it was: `kernel`, `env_scan` and `flavour` do not tell the two apart. */
+int msdr_chain_get_geometry(msdr_chain *chain, uint32_t *id);
 /* Which kernel ran the serial recurrences (introspection for tests: tests/q15_ladder_cases.py is the table of every branch below, and
  * tests/test_gpu_q15_ladders.py holds each of them to the oracle bit for bit).  Each getter returns a static string -- the kernel's name
  * with its template arguments, set in the branch that made the launch and handed to the launch's error check as well -- "" before the

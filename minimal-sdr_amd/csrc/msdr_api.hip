@@ -2391,6 +2391,12 @@ struct msdr_chain {
     int mf_halo, mf_bsteps, mf_stride;
     int mf_xsteps = 0;                   // 2 KB steps of merged first + last k-steps behind the dense fragments (msdr_sparse24.h); wave-stream kernel only
     int mf_merged[2] = {0, 0};           // runs every SSB table / every envelope table merges: k-steps the wave-stream kernel does NOT issue
+    // run geometry as compile-time constants (msdr_chain_mfw.hiph, MwGeom): per table [table set * mf_P + rotation] the id of the instantiated
+    // geometry its header has, 0 = none (empty: MSDR_MFW_GEOM=0 at create time, or no matrix-core tables); the table sets each of the two
+    // launches' units use (chain_mfw_units); what the last call's launches ran with (msdr_chain_get_geometry)
+    std::vector<uint8_t> mf_tab_geom;
+    std::vector<int> part_fsets[2];
+    uint32_t last_geom = 0;
     char *d_mf_tab;
     BiquadCascadeTables<kMfL> *d_bq_mf;
     BiquadCascadeTables<32> *d_bq_mf32;
@@ -3330,6 +3336,13 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
             if (!rc) {
                 c->mf_ok = true; c->mf_halo = H; c->mf_bsteps = bsteps; c->mf_stride = stride; c->mf_compact = compact;
                 c->mf_xsteps = xsteps; c->mf_merged[0] = merged_min[0]; c->mf_merged[1] = merged_min[1];
+                // every header as uploaded (a refused merge above has cleared its sp fields) against the instantiated geometries;
+                // MSDR_MFW_GEOM=0 at create time keeps the run-time kernels (A/B runs, tests)
+                static_assert(kMwMergedBytes == kSp24Bytes, "MwGeom places the merged steps as the table builder does");
+                bool geom_on = true;
+                if (const char *e = getenv("MSDR_MFW_GEOM")) geom_on = atoi(e) != 0;
+                c->mf_tab_geom.clear();
+                if (geom_on && !fr) for (const Tab &T : tabs) c->mf_tab_geom.push_back((uint8_t)mw_geom_of(T.h, H));
                 // wave-stream variant: waves per workgroup that put the most waves on a CU (<= 16: the kernel's <= 128 VGPRs allow
                 // 4 per SIMD) under the 160 KB of LDS -- counted in whole waves per SIMD.  A SIMD's tile rate is the same from two waves
                 // on (profiles/r03/c3_trims.txt), so a workgroup is as slow as its fullest SIMD: 13 waves (4 + 3 + 3 + 3) ran 4 % behind
@@ -3910,6 +3923,7 @@ struct ChainLaunch {
     uint32_t flavour;            // MSDR_FLAVOUR_* of the launches, set where each one is made
     uint32_t env_scan;           // how the folded envelope flavour of chain_mfw_kernel scanned its row states
     int merged_steps;            // chain_mfw_kernel: k-steps per tile that went into merged steps (the least over the launches), -1 = no such launch
+    uint32_t geom;               // chain_mfw_kernel: id of the constant run geometry a launch ran with (MwGeom), 0 = every launch read the table headers
     const char *node_kname;      // the kernel that runs the biquad nodes of this call ("": no nodes, fp32 chains)
 };
 
@@ -3935,6 +3949,8 @@ static int chain_mfw_units(msdr_chain *c, const ChainTiles &t)
     std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return key_of(a) < key_of(b); });
     long long count[2] = {0, 0};
     for (uint32_t ch : order) count[env_of(ch)]++;
+    c->part_fsets[0].clear(); c->part_fsets[1].clear();
+    for (uint32_t ch : order) { std::vector<int> &f = c->part_fsets[env_of(ch)]; if (f.empty() || f.back() != fset_of(ch)) f.push_back(fset_of(ch)); }
     for (int part = 0; part < 2; part++) {
         c->part_nseg[part] = chain_choose_nseg(c, t, count[part]);
         c->part_seg_len[part] = ((t.tiles + c->part_nseg[part] - 1) / c->part_nseg[part]) * t.tile;
@@ -4024,7 +4040,7 @@ static int chain_prepare(msdr_chain *c, ChainDecision &d, const ChainTiles &t, c
     r.kname = ""; r.node_kname = "";
     r.grid = (unsigned)(c->channels * r.nseg); r.block = kThreads; r.tile = t.tile;
     r.lds_bytes = t.mfw ? mw_lds_bytes(c->mf_halo, c->mf_bsteps + c->mf_xsteps, c->mfw_nw, c->mf_fr) : d.path == kPathFold ? fold_lds_bytes(p.ntaps_pad) : chain_lds_bytes(p.ntaps_pad);
-    r.flavour = 0; r.env_scan = 0; r.merged_steps = -1;
+    r.flavour = 0; r.env_scan = 0; r.merged_steps = -1; r.geom = 0;
 
     switch (d.path) {
     case kPathMfb:
@@ -4204,7 +4220,20 @@ static int chain_launch_mfw(msdr_chain *c, const ChainDecision &, const ChainTil
             r.flavour |= MSDR_FLAVOUR_AMTR;
             continue;
         }
-        (void)launch_chain_mfw(c->ctx->stream, (int)c->nstages, part == 1, fold, c->mf_fr, rowlocal, g, r.block, r.lds_bytes, q);
+        // a workgroup reads the table of its first unit's table set at this call's rotation: the kernel with a constant run geometry runs
+        // only where every table set this launch's units use has that one geometry there
+        int geom = 0;
+        if (mw_geom_flavour((int)c->nstages, part == 1, fold, c->mf_fr, rowlocal) && !c->mf_tab_geom.empty()) {
+            const int P = std::max(q.fold_period, 1);
+            for (size_t k = 0; k < c->part_fsets[part].size(); k++) {
+                const size_t ti = (size_t)c->part_fsets[part][k] * P + q.fold_rot;
+                const int id = ti < c->mf_tab_geom.size() ? c->mf_tab_geom[ti] : 0;
+                geom = (k == 0 || id == geom) ? id : 0;
+                if (!geom) break;
+            }
+        }
+        r.geom = std::max(r.geom, (uint32_t)geom);
+        (void)launch_chain_mfw(c->ctx->stream, (int)c->nstages, part == 1, fold, c->mf_fr, rowlocal, g, r.block, r.lds_bytes, q, geom);
         const int part_merged = mw_merges_steps((int)c->nstages, part == 1, fold, c->mf_fr, rowlocal) ? c->mf_merged[part] : 0;
         r.merged_steps = r.merged_steps < 0 ? part_merged : std::min(r.merged_steps, part_merged);
         if (int rc = launch_check("chain_mfw_kernel")) return rc;
@@ -4522,6 +4551,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     c->info.time_segments = (uint32_t)r.nseg; c->info.warmup = (uint32_t)p.warm; c->info.tile = (uint32_t)r.tile;
     c->info.taps_padded = path_per_channel(d.path) ? (uint32_t)c->pc_np : c->ntaps_pad;
     c->info.mfma_ksteps = d.mf ? (uint32_t)(c->mf_bsteps - std::max(r.merged_steps, 0)) : path_qm(d.path) ? (uint32_t)c->qm_bsteps : 0u;
+    c->last_geom = r.geom;
     return 0;
 }
 
@@ -4896,7 +4926,7 @@ static int chain_rebuild(msdr_chain *c, const ChainCfgStore &edited, void **stea
     n->gen = c->gen; n->dh_cache = c->dh_cache; n->dh_gen = c->dh_gen;
     n->floor_d = used_d; n->floor_sig = used_sig; n->floor_gen = c->gen;
     n->timing = c->timing; n->events.swap(c->events); n->timed_ms = c->timed_ms; n->timed_launches = c->timed_launches;
-    n->info = c->info;
+    n->info = c->info; n->last_geom = c->last_geom;
     n->osc_pending.swap(c->osc_pending); n->force_generic = c->force_generic;
     // per-channel taps survive every rebuild; the channels still on a shared tap set follow that set's (possibly new) coefficients
     n->rebuild_gen = c->rebuild_gen + 1;
@@ -5657,6 +5687,12 @@ extern "C" int msdr_chain_destroy(msdr_chain *c)
 }
 
 extern "C" const char *msdr_chain_node_kernel(msdr_chain *c) { return c ? c->node_kernel : nullptr; }
+extern "C" int msdr_chain_get_geometry(msdr_chain *c, uint32_t *id)
+{
+    if (!c || !id) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
+    *id = c->last_geom;
+    return 0;
+}
 extern "C" int msdr_chain_get_info(msdr_chain *c, msdr_chain_info *info)
 {
     if (!c || !info) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");

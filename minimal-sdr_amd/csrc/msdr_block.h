@@ -30,7 +30,7 @@ hipError_t launch_chain_mfb(hipStream_t stream, int stages, bool am, unsigned gr
 // nodes: the two AudioFilterBiquad nodes as the kernel's second phase (p.bq_state / p.bq_state_out = their records; one tile per wave, >= 3 waves, n = 128)
 hipError_t launch_chain_q15mb(hipStream_t stream, int flavour, bool nodes, unsigned grid, unsigned block, size_t lds_bytes, const ChainParams &p);
 // ---- msdr_chain_stream.hip ----
-hipError_t launch_chain_mfw(hipStream_t stream, int stages, bool am, bool fold, bool full_rate, int rowlocal, unsigned grid, unsigned block, size_t lds_bytes, const ChainParams &p);
+hipError_t launch_chain_mfw(hipStream_t stream, int stages, bool am, bool fold, bool full_rate, int rowlocal, unsigned grid, unsigned block, size_t lds_bytes, const ChainParams &p, int geom = 0);
 hipError_t launch_chain_amtr(hipStream_t stream, int ns, int stages, unsigned grid, unsigned block, size_t lds_bytes, const ChainParams &p);
 hipError_t launch_chain_fold(hipStream_t stream, int period, unsigned grid, size_t lds_bytes, const ChainParams &p);           // period 1, 2, 4
 hipError_t launch_chain_generic(hipStream_t stream, bool q15, unsigned grid, size_t lds_bytes, const ChainParams &p);          // chain_kernel<ArithF32 / ArithQ15>

@@ -12,8 +12,16 @@
 
 namespace msdr {
 
-hipError_t launch_chain_mfw(hipStream_t stream, int stages, bool am, bool fold, bool fr, int rowlocal, unsigned grid, unsigned block, size_t lds, const ChainParams &q)
+hipError_t launch_chain_mfw(hipStream_t stream, int stages, bool am, bool fold, bool fr, int rowlocal, unsigned grid, unsigned block, size_t lds, const ChainParams &q, int geom)
 {
+    if (geom) {              // the run geometry as constants (MwGeom): the caller has matched every table of this launch against it
+        if (!mw_geom_flavour(stages, am, fold, fr, rowlocal) || rowlocal > 2 || geom > kMwGeomCount) return hipErrorInvalidValue;
+#define MSDR_MFW_GEOM_LAUNCH(G) do { if (rowlocal == 1) hipLaunchKernelGGL((chain_mfw_geom_kernel<1, G>), dim3(grid), dim3(block), lds, stream, q); \
+                              else hipLaunchKernelGGL((chain_mfw_geom_kernel<2, G>), dim3(grid), dim3(block), lds, stream, q); } while (0)
+        if (geom == MwGeomEnv256::id) MSDR_MFW_GEOM_LAUNCH(MwGeomEnv256); else MSDR_MFW_GEOM_LAUNCH(MwGeomEnv512);
+#undef MSDR_MFW_GEOM_LAUNCH
+        return hipGetLastError();
+    }
     if (rowlocal) {          // envelope tables, two sections as matrix products, section rowlocal - 1 out of the row scan
         if (stages != 2 || !am || !fold || fr || rowlocal > 2) return hipErrorInvalidValue;
         if (rowlocal == 1) hipLaunchKernelGGL((chain_mfw_rowlocal_kernel<1>), dim3(grid), dim3(block), lds, stream, q);

@@ -114,6 +114,7 @@ def load_library(path=None):
                        ("msdr_chain_get_nco", [_p, C.c_uint32, _p, _p]),
                        ("msdr_chain_set_decimation", [_p, C.c_uint32]),
                        ("msdr_chain_get_decimation", [_p, _p]),
+                       ("msdr_chain_get_geometry", [_p, _p]),
                        ("msdr_chain_set_meter", [_p, _p]),
                        ("msdr_chain_get_meter", [_p, _p]),
                        ("msdr_meter_dbfs", [C.c_double, C.c_uint64, C.c_double]),
@@ -1032,6 +1033,12 @@ class Chain(_Instance):
         return {"kernel": i.kernel.decode(), "grid": i.grid, "block": i.block, "lds_bytes": i.lds_bytes,
                 "time_segments": i.time_segments, "warmup": i.warmup, "tile": i.tile, "taps_padded": i.taps_padded,
                 "mfma_ksteps": i.mfma_ksteps, "env_scan": i.env_scan, "flavour": i.flavour}
+
+    def geometry(self):
+        """msdr_chain_get_geometry: the constant run geometry the last process() ran with on the wave-stream kernels, 0 = read from the table headers"""
+        g = C.c_uint32(0)
+        _ck(self.ctx.lib.msdr_chain_get_geometry(self.h, C.byref(g)))
+        return g.value
 
     def enable_timing(self, on=True):
         _ck(self.ctx.lib.msdr_chain_enable_timing(self.h, int(on)))
