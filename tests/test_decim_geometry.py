@@ -138,6 +138,11 @@ def test_launch_geometry_follows_the_documented_rule(probe):
     # the shapes of tests/test_gpu_decim_per_channel.py, 102 taps: (cpw, tile) by nout and D
     assert [geometry(0, 2, 104, n, 11, 256, 0)[3:6:2] for n in (32, 128, 256, 768)] == [(4, 128), (4, 128), (2, 256), (1, 512)]
     assert [geometry(0, 32, 104, n, 11, 256, 0)[3:6:2] for n in (32, 128, 256, 768)] == [(4, 32), (4, 32), (2, 64), (1, 128)]
+    # the census (tests/decim_census_cases.py): its three call lengths at an entry whose CPW the fit lowers -- D = 59 beside 48 (Q15) / 36 (fp32)
+    # taps leaves room for one wave with one channel and two outputs per lane, whatever n / D chose: (cpw, tile), and the block and the LDS
+    assert [geometry(0, 59, 48, n, 2, 256, 0)[3:6:2] for n in (30, 130, 258)] == [(1, 128)] * 3
+    assert [geometry(1, 59, 36, n, 2, 256, 0)[3:6:2] for n in (30, 130, 258)] == [(1, 128)] * 3
+    assert [geometry(0, 59, 48, n, 2, 256, 0)[:3] for n in (30, 130, 258)] == [(2, 64, 65088)] * 3
 
 
 def test_the_setters_limits_are_what_the_rule_yields(probe):
