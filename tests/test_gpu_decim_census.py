@@ -49,12 +49,16 @@ def ran(info, e):
     assert info["lds_bytes"] == e["lds"], (info, e)
 
 
-def run_entry(ctx, chain, e, adtype, pdtype=None, mdtype=None, flavour=None):
+def run_entry(ctx, chain, e, adtype, pdtype=None, mdtype=None, flavour=None, x=None, calls=None, ran=ran, feed=None, read=(0, 2)):
     """the entry's three calls -> (audio [ch, outputs], pairs [ch, outputs, 2] or None, meters [3, ch] or None); every buffer lies between guard
-    stretches of the sentinel, and everything outside the written rows must still hold it.  flavour(info): a check of the family's own."""
-    ch, D, x = e["channels"], e["D"], cases.data(e)["x"]
+    stretches of the sentinel, and everything outside the written rows must still hold it.  flavour(info): a check of the family's own.
+    The census of the sliding-window kernels (tests/pc_census_cases.py: no "D" in an entry, audio of n samples per row) hands in its own stream
+    x, its calls' lengths, its reading of info() (ran; None: an instance without an info call; read: behind which calls) and, for an input map,
+    feed(the call's columns of x) -> what is uploaded."""
+    ch, D = e["channels"], e.get("D", 1)
+    x = cases.data(e)["x"] if x is None else x
     audio, pairs, meters, lo = [], [], [], 0
-    for k, nout in enumerate(cases.call_outputs(e)):
+    for k, nout in enumerate(cases.call_outputs(e) if calls is None else calls):
         n = nout * D
         guard = 2 * nout + 8                                             # guarded_call: guard rows in front and behind, n - n / D of slack per row
         a_flat = fresh(guard + ch * nout + ch * (n - nout) + guard, adtype)
@@ -67,7 +71,8 @@ def run_entry(ctx, chain, e, adtype, pdtype=None, mdtype=None, flavour=None):
         if mdtype is not None:
             m_buf = ctx.to_device(fresh(METER_GUARD + ch + METER_GUARD, mdtype))
             chain.set_meter(m_buf.offset(8 * METER_GUARD))
-        chain.process(ctx.to_device(np.ascontiguousarray(x[:, lo:lo + n])), a_buf.offset(guard * a_flat.itemsize), n)
+        part = np.ascontiguousarray(x[:, lo:lo + n])
+        chain.process(ctx.to_device(part if feed is None else feed(part)), a_buf.offset(guard * a_flat.itemsize), n)
         back = a_buf.download()
         assert untouched(back[:guard]) and untouched(back[guard + ch * nout:]), (k, "audio: written outside the batch")
         audio.append(back[guard:guard + ch * nout].reshape(ch, nout))
@@ -81,13 +86,13 @@ def run_entry(ctx, chain, e, adtype, pdtype=None, mdtype=None, flavour=None):
             back = m_buf.download()
             assert untouched(back[:METER_GUARD]) and untouched(back[METER_GUARD + ch:]), (k, "meter: written outside the entries")
             meters.append(back[METER_GUARD:METER_GUARD + ch])
-        if k != 1:
+        if k in read and ran is not None:
             info = chain.info()
             ran(info, e)
             if flavour is not None:
                 flavour(info)
         lo += n
-    assert lo == cases.data(e)["n"]
+    assert lo == x.shape[1]
     if pdtype is not None:
         chain.set_iq_out(None)
     if mdtype is not None:
@@ -95,11 +100,13 @@ def run_entry(ctx, chain, e, adtype, pdtype=None, mdtype=None, flavour=None):
     return np.concatenate(audio, axis=1), (np.concatenate(pairs, axis=1) if pairs else None), (np.stack(meters) if meters else None)
 
 
-def refusal(ctx, e, make, run):
+def refusal(ctx, e, make, run, ask=None, x=None):
     """part D: one step beyond the limit -- a chain of e["refuse"] taps -- the factor is refused with MSDR_STATUS_ARGUMENT_ERROR and the chain
     is what a control chain that was never asked is: the same decimation, the same bits, the same info().  (Beyond 4096 taps the interface
-    refuses the filter itself.)  make(nt) -> a chain of nt taps in phase-accumulator mode; run(chain, x) -> its audio of one call."""
-    D, nt = e["D"], e["refuse"]
+    refuses the filter itself.)  make(nt) -> a chain of nt taps in phase-accumulator mode; run(chain, x) -> its audio of one call.
+    The census of the sliding-window kernels asks another setter: ask(chain) makes the call that must be refused (and make(nt) the chain in the
+    state before it); x: the 128 samples per row both chains then process."""
+    nt = e["refuse"]
     if nt > cases.TAP_CAP:
         with pytest.raises(msdr.MsdrError) as err:
             make(nt)
@@ -107,10 +114,10 @@ def refusal(ctx, e, make, run):
         return
     a, control = make(nt), make(nt)
     with pytest.raises(msdr.MsdrError) as err:
-        a.set_decimation(D)
+        a.set_decimation(e["D"]) if ask is None else ask(a)
     assert err.value.status == ARG and "nothing changed" in str(err.value), err.value
     assert a.decimation() == control.decimation() == 1
-    x = cases.data(e)["x"][:, :128]
+    x = cases.data(e)["x"][:, :128] if x is None else x
     ga, gb = run(a, x), run(control, x)
     assert np.array_equal(raw(ga), raw(gb)) and a.info() == control.info()
     assert "pcnd" not in a.info()["kernel"], a.info()

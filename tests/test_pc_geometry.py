@@ -9,7 +9,9 @@ Python statement of the documented rule:
 
 The LDS layouts of the families are restated twice, in the program (C++) and here (Python), from the comments of the kernels' headers; a second
 program, compiled with hipcc against the kernels' headers, prints what the sizing functions the launchers pass (pc_lds_bytes, f32pc_lds_bytes,
-pco_lds_bytes, f32pco_lds_bytes, f32pcb_lds_bytes) give, and the restatement is held to them."""
+pco_lds_bytes, f32pco_lds_bytes, f32pcb_lds_bytes, pcn_lds_bytes, f32pcn_lds_bytes) give, and the restatement is held to them.
+The GPU half of this file is the census of tests/pc_census_cases.py (tests/test_gpu_pc_census.py, tests/test_gpu_pc_census_f32.py): every
+geometry this rule can reach, run on the kernels and held to the oracle."""
 import itertools
 import os
 import subprocess
@@ -26,6 +28,9 @@ CUS = [1, 256]
 SEGS = [0, 1, 3]
 OSCS = [0, 24, 128, 8192]
 FAMILIES = ["q15pc", "q15fir", "f32pc", "f32fs4", "f32fir", "q15pco", "f32pco", "f32pcb"]
+# the kernels with a phase-accumulator oscillator: the channel areas of q15pc / f32pc and, ONCE per workgroup, the packed sine table (kPcnTabBytes)
+NCO_FAMILIES = {"q15pcn": "q15pc", "f32pcn": "f32pc"}
+TAB_BYTES = 4 * 1024
 
 PROBE = r"""
 #include <cstdio>
@@ -75,13 +80,16 @@ int main()
 SIZES = r"""
 #include <cstdio>
 #include "msdr_chain_f32pcb.hiph"
+#include "msdr_chain_ncopc.hiph"
 int main()
 {
     using namespace msdr;
     const int nps[] = {8, 104, 512, 2048, 3840}, oscs[] = {0, 24, 128, 8192}, cpws[] = {1, 2, 4}, nws[] = {1, 2, 4};
+    printf("%zu\n", kPcnTabBytes);
     for (int np : nps) for (int o : oscs) for (int c : cpws) for (int w : nws)
-        printf("%d %d %d %d %zu %zu %zu %zu %zu %zu %zu %zu\n", np, o, c, w, pc_lds_bytes(np, c, false, w), pc_lds_bytes(np, c, true, w), f32pc_lds_bytes(np, c, false, false, w),
-               f32pc_lds_bytes(np, c, false, true, w), f32pc_lds_bytes(np, c, true, false, w), pco_lds_bytes(np, o, c, w), f32pco_lds_bytes(np, o, c, w), f32pcb_lds_bytes(np, o, c, w));
+        printf("%d %d %d %d %zu %zu %zu %zu %zu %zu %zu %zu %zu %zu\n", np, o, c, w, pc_lds_bytes(np, c, false, w), pc_lds_bytes(np, c, true, w), f32pc_lds_bytes(np, c, false, false, w),
+               f32pc_lds_bytes(np, c, false, true, w), f32pc_lds_bytes(np, c, true, false, w), pco_lds_bytes(np, o, c, w), f32pco_lds_bytes(np, o, c, w), f32pcb_lds_bytes(np, o, c, w),
+               pcn_lds_bytes(np, c, w), f32pcn_lds_bytes(np, c, w));
     return 0;
 }
 """
@@ -107,9 +115,16 @@ def chan_bytes(fam, np_, o, cpw):
     return 4 * floats
 
 
+def lds_bytes(fam, np_, o, cpw, nw):
+    """the workgroup's LDS: cpw x nw channel areas, and behind them what a family keeps once per workgroup"""
+    if fam in NCO_FAMILIES:
+        return chan_bytes(NCO_FAMILIES[fam], np_, 0, cpw) * cpw * nw + TAB_BYTES
+    return chan_bytes(fam, np_, o, cpw) * cpw * nw
+
+
 def fit(fam, n, np_, o):
     cpw, nw = (4 if n <= 128 else 2 if n <= 256 else 1), 4
-    size = lambda: chan_bytes(fam, np_, o, cpw) * cpw * nw          # noqa: E731
+    size = lambda: lds_bytes(fam, np_, o, cpw, nw)          # noqa: E731
     while size() > CAP and nw > 1:
         nw //= 2
     while size() > CAP and cpw > 1:
@@ -190,9 +205,12 @@ def test_restated_layouts_are_the_kernels_sizing_functions(tmp_path):
         f.write(SIZES)
     subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O1", "-std=c++17", "-fwrapv", "-Wno-unused-value", "-I" + CSRC, "-o", exe, src])
     lines = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.splitlines()
+    assert int(lines[0]) == TAB_BYTES          # kPcnTabBytes
+    lines = lines[1:]
     assert len(lines) == len(NPS) * len(OSCS) * 9
     for ln in lines:
         np_, o, cpw, nw, *got = (int(v) for v in ln.split())
-        assert got == [chan_bytes(fam, np_, o, cpw) * cpw * nw for fam in FAMILIES], ln
+        assert got[:8] == [chan_bytes(fam, np_, o, cpw) * cpw * nw for fam in FAMILIES], ln
+        assert got == [lds_bytes(fam, np_, o, cpw, nw) for fam in FAMILIES + list(NCO_FAMILIES)], ln
     # the figures of msdr_chain_f32pcb.hiph, from f32pcb_lds_bytes itself
-    assert "104 128 4 2 " in "\n".join(lines) and [ln.split()[-1] for ln in lines if ln.startswith(("104 128 4 2 ", "104 0 4 4 "))] == ["40960", "36864"]
+    assert "104 128 4 2 " in "\n".join(lines) and [ln.split()[11] for ln in lines if ln.startswith(("104 128 4 2 ", "104 0 4 4 "))] == ["40960", "36864"]
