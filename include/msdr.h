@@ -782,6 +782,34 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   Reporting: msdr_chain_get_info().kernel keeps its names; on fp32 chains flavour carries MSDR_FLAVOUR_IQ_OUT exactly while a buffer is
  *   set.  Graphs stay refused, as on every chain in this mode.
  * msdr_chain_get_iq_out: the buffer and pitch in force (NULL, 0 on a chain without one); either output may be NULL.
+ * msdr_chain_set_complex_input: what a wideband front end delivers -- interleaved complex int16 pairs {I, Q} instead of the Teensy's one ADC
+ *   pin.  The reference's mixer node is a complex mixer already: AudioEffectFreqConv::update (freq_conv.cpp:30-116) takes two input ports and
+ *   forms all four products, in two directions; the chain's real input is its degenerate form "real IF on port 0, zeros on port 1, dir = 1".
+ *   While on, d_if of msdr_chain_process is [channels or n_inputs][n_samples] PAIRS, two int16_t each, I first, 4-byte aligned (anything else:
+ *   MSDR_STATUS_ARGUMENT_ERROR, nothing enqueued).  n_samples still counts samples (pairs) and every length rule stays in samples: the
+ *   multiple of D, the even n / D with Q15 nodes, the I/Q pitch.  The input map (msdr_chain_set_input_rows) selects rows of pairs.
+ *   With c = cosq and s = sinq of the receiver's phase at that sample (msdr_nco_q15):
+ *     Q15   freq_conv.cpp:67-103 exactly: the four products ssat16((a * b) >> 15) of the original pair, then
+ *             dir == 0:  I' = ssat16(I c + Q s)   Q' = ssat16(Q c - I s)          (the spectrum moves DOWN by the receiver's frequency)
+ *             dir == 1:  I' = ssat16(I c - Q s)   Q' = ssat16(Q c + I s)          (up)
+ *           dir is a sign on the second product of each sum, not on the oscillator: (-a) >> 15 is not -(a >> 15).
+ *     F32   the same four products and two sums in fp32 on I in_scale, Q in_scale, c / 32768, s / 32768, each rounded on its own.
+ *   I' feeds the coeffs_i filter and Q' the coeffs_q filter, as always.  With Q = 0 and dir = 1 this is the real chain, bit for bit on Q15.
+ *   The FIR history becomes raw pairs (hist_len samples of 4 bytes per channel; a history sample keeps the oscillator generation of its own
+ *   time, as always), and while on msdr_chain_get_fir_history returns 2 * hist_len int16_t, interleaved, oldest first: `capacity` counts
+ *   int16_t, *hist_len stays in samples.
+ *   Chains in phase-accumulator mode only (msdr_chain_set_decimation's scope rule), Q15 and F32; dir must be 0 or 1 when turning on; and the
+ *   switch, on or off or to the other direction, is accepted only while the FIR history is clear -- before the first msdr_chain_process, or
+ *   directly after msdr_chain_reset / msdr_chain_init_fir, the rule of the first msdr_chain_set_nco_channels call -- so no history is ever
+ *   converted.  A repeat call with the values in force does nothing and is always accepted.  Anything else, a NULL chain included, is
+ *   MSDR_STATUS_ARGUMENT_ERROR, nothing changed.  The setting survives everything the decimation factor survives and combines, in either
+ *   order, with msdr_chain_set_decimation, set_meter, set_iq_out (I/Q-only calls included), set_input_rows, the tap / NCO / mode / node /
+ *   cascade setters, MSDR_CHAIN_OUT_I16, and on Q15 chains MSDR_CHAIN_SYNCAM_PLL at D = 1 and msdr_chain_set_anr.
+ *   The meter: msdr_meter_dbfs's 0 dBFS is a full-scale REAL carrier (I^2 + Q^2 = A^2 / 4).  A complex exponential of the same amplitude at
+ *   the tuned frequency has no image to lose in the channel filter (I^2 + Q^2 = A^2) and reads +6.02 dB.
+ *   Reporting: msdr_chain_get_info().kernel keeps its names (the complex-input twins, chain_q15pcn_cx_kernel ..., run under them); on fp32
+ *   chains flavour carries MSDR_FLAVOUR_COMPLEX_IN exactly while the mode is on.  Graphs stay refused, as on every chain in this mode.
+ * msdr_chain_get_complex_input: the switch and the direction in force (0, 0 on a chain that never set them); either output may be NULL.
  * msdr_nco_step (host only): llround(f_hz / fs_hz * 2^32) mod 2^32; a negative frequency wraps (-6000 at 24000: 0xC0000000).
  * msdr_nco_table (host only): T[i] = (int16) lround(32767 sin(2 pi i / 1024)), i = 0 .. 1024, T[1024] = 0.
  * msdr_nco_q15 (host only; what the kernels compute): for each uint32 phase, i = phase >> 22, f = (phase >> 6) & 0xFFFF,
@@ -801,6 +829,8 @@ int msdr_chain_get_meter(msdr_chain *chain, void **d_meter);
 double msdr_meter_dbfs(double sum_sq, uint64_t n_out, double full_scale);
 int msdr_chain_set_iq_out(msdr_chain *chain, void *d_iq, uint64_t pitch);   /* NULL = off (default) */
 int msdr_chain_get_iq_out(msdr_chain *chain, void **d_iq, uint64_t *pitch); /* either may be NULL */
+int msdr_chain_set_complex_input(msdr_chain *chain, int on, int dir);   /* off (default): real IF */
+int msdr_chain_get_complex_input(msdr_chain *chain, int *on, int *dir); /* either may be NULL */
 int msdr_chain_set_taps(msdr_chain *chain, uint32_t tapset, const void *coeffs_i, const void *coeffs_q);
 int msdr_chain_set_taps_channels(msdr_chain *chain, uint32_t first_channel, uint32_t count,
                                  const q15_t *coeffs_i, const q15_t *coeffs_q);
@@ -879,6 +909,9 @@ enum { MSDR_FLAVOUR_METER = 0x200000u };
 /* And another: the demodulator kernel stored the pair behind the channel filter -- the IQ flavour of a phase-accumulator kernel,
  * msdr_chain_set_iq_out with a buffer (always beside MSDR_FLAVOUR_NCO_PC). */
 enum { MSDR_FLAVOUR_IQ_OUT = 0x400000u };
+/* And another: the demodulator kernel mixed rows of complex pairs -- the complex-input twin of a phase-accumulator kernel,
+ * msdr_chain_set_complex_input on (always beside MSDR_FLAVOUR_NCO_PC). */
+enum { MSDR_FLAVOUR_COMPLEX_IN = 0x800000u };
 int msdr_chain_get_info(msdr_chain *chain, msdr_chain_info *info);
 /* The wave-stream kernels read the run geometry of a tap table (which chunks of the window each accumulator walks, which runs merge their first
  * and last step) from the table's header -- or, for the geometries the library instantiates, have it as compile-time constants: the same

@@ -2531,6 +2531,11 @@ struct msdr_chain {
     // without an audio batch is accepted (chains with nco_active only, which no graph captures)
     void *d_iq = nullptr;
     uint64_t iq_pitch = 0;
+    // msdr_chain_set_complex_input (chains with nco_active only): d_if and the FIR history are rows of pairs {I, Q} of two int16 and the
+    // complex-input twins of the phase-accumulator kernels run (msdr_chain_cxpc.hiph) with freq_conv's direction cx_dir.  d_hist has room for
+    // pairs on every chain (2 x channels x hist_len int16), so the switch, made over a clear history only, converts and allocates nothing.
+    bool cx_on = false;
+    int cx_dir = 0;
     msdr_chain_info info;
     // optional per-launch timing of the main kernel
     bool timing;
@@ -2804,8 +2809,9 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
         if (!rc) rc = upload(ctx, ts, &c->d_tapset);
         c->h_mode = m; c->h_tapset = ts;
     }
-    if (!rc) rc = dzalloc(ctx, (size_t)c->channels * c->hist_len, &c->d_hist[0]);
-    if (!rc) rc = dzalloc(ctx, (size_t)c->channels * c->hist_len, &c->d_hist[1]);
+    // (room for pairs: msdr_chain_set_complex_input keeps the history as {I, Q} per sample)
+    if (!rc) rc = dzalloc(ctx, (size_t)2 * c->channels * c->hist_len, &c->d_hist[0]);
+    if (!rc) rc = dzalloc(ctx, (size_t)2 * c->channels * c->hist_len, &c->d_hist[1]);
     // ---- Q15 on the integer matrix cores (msdr_chain_q15mf.hiph): byte-split Toeplitz fragments per (tap set, phase mod 4) ----
     // mixer: the Fs/4 loop, or a freq_conv table of period 4 that is zero in osc_q at one parity of phases and zero in osc_i at the
     // other (the reference node driven at fs/4): then, too, every sample feeds only the I or only the Q filter
@@ -4145,17 +4151,21 @@ static int chain_launch_f32pc(msdr_chain *c, const ChainDecision &, const ChainP
     pc_params_iq(q, c);
     PcLaunch geo;
     if (c->nco_active && c->decim > 1) {          // msdr_chain_set_decimation: p.out is [channels][n / D]
-        PcfndParams qd;
+        PcfndCxParams qd;          // (msdr_chain_set_complex_input: the twin's block is the real kernel's and the direction)
         static_cast<PcfnParams &>(qd) = q;
-        qd.sin_tab = c->d_nco_tab; qd.t0 = (unsigned)c->nco_T; qd.dec = (int)c->decim; qd.opl = 0; qd.nout = 0;
-        if (launch_chain_f32pcnd(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, qd, &geo) != hipSuccess)
+        qd.sin_tab = c->d_nco_tab; qd.t0 = (unsigned)c->nco_T; qd.dec = (int)c->decim; qd.opl = 0; qd.nout = 0; qd.cx_dir = c->cx_dir;
+        if ((c->cx_on ? launch_chain_f32pcnd_cx(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, qd, &geo)
+                      : launch_chain_f32pcnd(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, qd, &geo)) != hipSuccess)
             return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pcnd_kernel launch failed");
-        r.kname = kPcfndKernelName; r.flavour |= MSDR_FLAVOUR_NCO_PC | MSDR_FLAVOUR_DECIMATED;
+        r.kname = kPcfndKernelName; r.flavour |= MSDR_FLAVOUR_NCO_PC | MSDR_FLAVOUR_DECIMATED | (c->cx_on ? (uint32_t)MSDR_FLAVOUR_COMPLEX_IN : 0u);
     } else if (c->nco_active) {
-        q.sin_tab = c->d_nco_tab; q.t0 = (unsigned)c->nco_T;
-        if (launch_chain_f32pcn(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, q, &geo) != hipSuccess)
+        PcfnCxParams qn;
+        static_cast<PcfnParams &>(qn) = q;
+        qn.sin_tab = c->d_nco_tab; qn.t0 = (unsigned)c->nco_T; qn.cx_dir = c->cx_dir;
+        if ((c->cx_on ? launch_chain_f32pcn_cx(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, qn, &geo)
+                      : launch_chain_f32pcn(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, qn, &geo)) != hipSuccess)
             return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pcn_kernel launch failed");
-        r.kname = kPcfnKernelName; r.flavour |= MSDR_FLAVOUR_NCO_PC;
+        r.kname = kPcfnKernelName; r.flavour |= MSDR_FLAVOUR_NCO_PC | (c->cx_on ? (uint32_t)MSDR_FLAVOUR_COMPLEX_IN : 0u);
     } else if (c->opc_active) {
         if (launch_chain_f32pco(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, q, &geo) != hipSuccess)
             return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pco_kernel launch failed");
@@ -4353,15 +4363,17 @@ static int chain_launch_q15pc(msdr_chain *c, const ChainDecision &, const ChainP
     pc_params_iq(q, c);
     PcLaunch geo;
     if (c->nco_active && c->decim > 1) {          // msdr_chain_set_decimation: p.out is [channels][n / D]
-        PcndParams qd;
+        PcndCxParams qd;          // (msdr_chain_set_complex_input: the twin's block is the real kernel's and the direction)
         static_cast<PcnParams &>(qd) = q;
-        qd.sin_tab = c->d_nco_tab; qd.t0 = (unsigned)c->nco_T; qd.dec = (int)c->decim; qd.opl = 0; qd.nout = 0;
-        if (launch_chain_q15pcnd(c->ctx->stream, c->ctx->num_cus, qd, &geo) != hipSuccess)
+        qd.sin_tab = c->d_nco_tab; qd.t0 = (unsigned)c->nco_T; qd.dec = (int)c->decim; qd.opl = 0; qd.nout = 0; qd.cx_dir = c->cx_dir;
+        if ((c->cx_on ? launch_chain_q15pcnd_cx(c->ctx->stream, c->ctx->num_cus, qd, &geo) : launch_chain_q15pcnd(c->ctx->stream, c->ctx->num_cus, qd, &geo)) != hipSuccess)
             return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pcnd_kernel launch failed");
         r.kname = kPcndKernelName;
     } else if (c->nco_active) {
-        q.sin_tab = c->d_nco_tab; q.t0 = (unsigned)c->nco_T;
-        if (launch_chain_q15pcn(c->ctx->stream, c->ctx->num_cus, q, &geo) != hipSuccess)
+        PcnCxParams qn;
+        static_cast<PcnParams &>(qn) = q;
+        qn.sin_tab = c->d_nco_tab; qn.t0 = (unsigned)c->nco_T; qn.cx_dir = c->cx_dir;
+        if ((c->cx_on ? launch_chain_q15pcn_cx(c->ctx->stream, c->ctx->num_cus, qn, &geo) : launch_chain_q15pcn(c->ctx->stream, c->ctx->num_cus, qn, &geo)) != hipSuccess)
             return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pcn_kernel launch failed");
         r.kname = kPcnKernelName;
     } else if (c->opc_active) {
@@ -4440,6 +4452,8 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     if (!d_if || (!d_audio && !c->d_iq)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null buffer");
     const bool audio = d_audio != nullptr;
     if (n_samples > (1ull << 31) - 4096) return fail(MSDR_STATUS_LENGTH_ERROR, "n_samples too large for one call");
+    if (c->cx_on && (reinterpret_cast<uintptr_t>(d_if) & 3))
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "complex input: d_if holds pairs {I, Q} that are read as dwords: it must be 4-byte aligned (msdr_chain_set_complex_input); nothing enqueued");
     const bool f32 = (c->arith == MSDR_ARITH_F32);
     if (!f32 && c->nnodes && (n_samples & 1u))
         return fail(MSDR_STATUS_LENGTH_ERROR, "AudioFilterBiquad processes sample pairs: n_samples must be even");
@@ -4521,6 +4535,17 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
 
     // ---- history and bookkeeping (the block kernels write the next history themselves)
     if (path_block(d.path)) { }
+    else if (c->cx_on) {          // msdr_chain_set_complex_input: the same two kernels over pairs, one dword each
+        if (c->n_inputs)
+            hipLaunchKernelGGL((history_rows_kernel<int32_t>), dim3(grid_1d((long long)c->channels * c->hist_len)), dim3(256), 0, c->ctx->stream,
+                               (const int32_t *)d_if, (const int32_t *)c->d_hist[c->cur], (int32_t *)c->d_hist[c->cur ^ 1], (long long)n_samples, (int)c->hist_len,
+                               (int)c->channels, (const int *)c->d_in_row);
+        else
+            hipLaunchKernelGGL((history_kernel<int32_t>), dim3(grid_1d((long long)c->channels * c->hist_len)), dim3(256), 0, c->ctx->stream,
+                               (const int32_t *)d_if, (const int32_t *)c->d_hist[c->cur], (int32_t *)c->d_hist[c->cur ^ 1], (long long)n_samples, (int)c->hist_len,
+                               (int)c->channels);
+        if (int rc2 = launch_check(c->n_inputs ? "history_rows_kernel" : "history_kernel")) return rc2;
+    }
     else if (c->n_inputs) {          // msdr_chain_set_input_rows: each channel's history from the row it heard
         hipLaunchKernelGGL((history_rows_kernel<int16_t>), dim3(grid_1d((long long)c->channels * c->hist_len)), dim3(256), 0, c->ctx->stream,
                            d_if, (const int16_t *)c->d_hist[c->cur], c->d_hist[c->cur ^ 1], (long long)n_samples, (int)c->hist_len,
@@ -4707,7 +4732,7 @@ extern "C" int msdr_chain_reset(msdr_chain *c)
 {
     if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
     if (int rc = bind(c->ctx)) return rc;
-    size_t hb = (size_t)c->channels * c->hist_len * sizeof(int16_t);
+    size_t hb = (size_t)2 * c->channels * c->hist_len * sizeof(int16_t);          // (the whole buffer: pairs under msdr_chain_set_complex_input)
     HIP_TRY(hipMemsetAsync(c->d_hist[0], 0, hb, c->ctx->stream));
     HIP_TRY(hipMemsetAsync(c->d_hist[1], 0, hb, c->ctx->stream));
     if (c->d_bq_state_alt) HIP_TRY(hipMemsetAsync(c->d_bq_state_alt, 0, (size_t)c->channels * kBqStateFloats * sizeof(float), c->ctx->stream));
@@ -4810,7 +4835,7 @@ extern "C" int msdr_chain_init_fir(msdr_chain *c)
         HIP_TRY(hipMemcpy(c->d_bq_state, st.data(), st.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     if (c->aux) if (int rc = msdr_chain_init_fir(c->aux)) return rc;             // the PLL / LMS channels' filters with it
-    const size_t hb = (size_t)c->channels * c->hist_len * sizeof(int16_t);
+    const size_t hb = (size_t)2 * c->channels * c->hist_len * sizeof(int16_t);          // (the whole buffer: pairs under msdr_chain_set_complex_input)
     HIP_TRY(hipMemsetAsync(c->d_hist[0], 0, hb, c->ctx->stream));
     HIP_TRY(hipMemsetAsync(c->d_hist[1], 0, hb, c->ctx->stream));
     c->hist_clear = true;
@@ -4866,12 +4891,14 @@ extern "C" int msdr_chain_set_mode(msdr_chain *c, uint32_t channel, int32_t mode
 // tables over the old state.  The stream is drained first: the old tables are freed with the husk.
 // raw IF history carried into a rebuilt chain whose history length differs (a cascade that moves between the chain kernel and the
 // CMSIS-order pass changes the matrix-core window's halo): the newest min(hl_src, hl_dst) samples, older entries zero; both "oldest first"
-__global__ void hist_resize_kernel(const int16_t *__restrict__ src, int16_t *__restrict__ dst, int channels, int hl_src, int hl_dst)
+// (T: int16_t, or int32_t for the pairs of msdr_chain_set_complex_input)
+template <typename T>
+__global__ void hist_resize_kernel(const T *__restrict__ src, T *__restrict__ dst, int channels, int hl_src, int hl_dst)
 {
     const long long total = (long long)channels * hl_dst;
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
         const int ch = (int)(i / hl_dst), k = (int)(i - (long long)ch * hl_dst), back = hl_dst - k;       // back = 1: the newest sample
-        dst[i] = (back <= hl_src) ? src[(long long)ch * hl_src + (hl_src - back)] : (int16_t)0;
+        dst[i] = (back <= hl_src) ? src[(long long)ch * hl_src + (hl_src - back)] : (T)0;
     }
 }
 
@@ -4903,8 +4930,12 @@ static int chain_rebuild(msdr_chain *c, const ChainCfgStore &edited, void **stea
     // FIR history and table position
     if (n->hist_len == c->hist_len) { std::swap(n->d_hist[0], c->d_hist[0]); std::swap(n->d_hist[1], c->d_hist[1]); n->cur = c->cur; }
     else {
-        hipLaunchKernelGGL(hist_resize_kernel, dim3(grid_1d((long long)n->channels * n->hist_len)), dim3(256), 0, c->ctx->stream,
-                           (const int16_t *)c->d_hist[c->cur], n->d_hist[n->cur], (int)n->channels, (int)c->hist_len, (int)n->hist_len);
+        if (c->cx_on)
+            hipLaunchKernelGGL((hist_resize_kernel<int32_t>), dim3(grid_1d((long long)n->channels * n->hist_len)), dim3(256), 0, c->ctx->stream,
+                               (const int32_t *)c->d_hist[c->cur], (int32_t *)n->d_hist[n->cur], (int)n->channels, (int)c->hist_len, (int)n->hist_len);
+        else
+            hipLaunchKernelGGL((hist_resize_kernel<int16_t>), dim3(grid_1d((long long)n->channels * n->hist_len)), dim3(256), 0, c->ctx->stream,
+                               (const int16_t *)c->d_hist[c->cur], n->d_hist[n->cur], (int)n->channels, (int)c->hist_len, (int)n->hist_len);
         if (int rc2 = launch_check("hist_resize_kernel")) { chain_free(n); return rc2; }
         if (hipStreamSynchronize(c->ctx->stream) != hipSuccess) { chain_free(n); return fail(MSDR_STATUS_HIP_ERROR, "hist_resize_kernel failed"); }
     }
@@ -4943,6 +4974,7 @@ static int chain_rebuild(msdr_chain *c, const ChainCfgStore &edited, void **stea
     n->h_nco_base.swap(c->h_nco_base); n->h_nco_step.swap(c->h_nco_step); n->nco_T = c->nco_T; n->hist_clear = c->hist_clear;
     n->decim = c->decim;          // (msdr_chain_set_decimation holds through every rebuild)
     n->d_iq = c->d_iq; n->iq_pitch = c->iq_pitch;          // (and so does msdr_chain_set_iq_out)
+    n->cx_on = c->cx_on; n->cx_dir = c->cx_dir;          // (and msdr_chain_set_complex_input: the history above went over as pairs)
     std::swap(*c, *n);
     if (steal_osc) { *steal_osc = n->d_osc; n->d_osc = nullptr; }
     chain_free(n);
@@ -5485,6 +5517,32 @@ extern "C" int msdr_chain_get_iq_out(msdr_chain *c, void **d_iq, uint64_t *pitch
     return 0;
 }
 
+// What a wideband front end delivers: from the next call on d_if and the FIR history are rows of pairs {I, Q} and the complex-input twins of
+// the phase-accumulator kernels (msdr_chain_cxpc.hiph) apply freq_conv's full mix (freq_conv.cpp:67-103) in direction dir.  A switch of the
+// host's under msdr_chain_set_decimation's scope rule, made over a clear history only (the rule of the first msdr_chain_set_nco_channels), so
+// no history is ever converted.  Everything that can fail happens before anything changes.
+extern "C" int msdr_chain_set_complex_input(msdr_chain *c, int on, int dir)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (!c->nco_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "complex input: only on a chain with the phase-accumulator oscillator (msdr_chain_set_nco_channels); nothing changed");
+    if (on && dir != 0 && dir != 1) return fail(MSDR_STATUS_ARGUMENT_ERROR, "complex input: dir %d: 0 or 1 (freq_conv.cpp:67-103); nothing changed", dir);
+    const bool want = on != 0;
+    const int want_dir = want ? dir : 0;
+    if (want == c->cx_on && want_dir == c->cx_dir) return 0;
+    if (!c->hist_clear)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "complex input: the switch needs a clear FIR history (before the first msdr_chain_process, or directly after msdr_chain_reset / msdr_chain_init_fir); nothing changed");
+    c->cx_on = want; c->cx_dir = want_dir;
+    return 0;
+}
+
+extern "C" int msdr_chain_get_complex_input(msdr_chain *c, int *on, int *dir)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (on) *on = c->cx_on ? 1 : 0;
+    if (dir) *dir = c->cx_dir;
+    return 0;
+}
+
 extern "C" int msdr_chain_set_node_coefficients(msdr_chain *c, uint32_t node, uint32_t stage, const int32_t coef[5])
 {
     if (!c || !coef) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
@@ -5707,9 +5765,10 @@ extern "C" int msdr_chain_get_fir_history(msdr_chain *c, uint32_t channel, int16
     if (int rc = bind(c->ctx)) return rc;
     if (hist_len) *hist_len = c->hist_len;
     if (!hist) return 0;
-    if (capacity < c->hist_len) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the history holds %u samples, room for %u given", c->hist_len, capacity);
+    const uint32_t per = c->cx_on ? 2u : 1u;          // msdr_chain_set_complex_input: pairs {I, Q}, interleaved
+    if (capacity < per * c->hist_len) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the history holds %u int16, room for %u given", per * c->hist_len, capacity);
     HIP_TRY(hipStreamSynchronize(c->ctx->stream));
-    HIP_TRY(hipMemcpy(hist, c->d_hist[c->cur] + (size_t)channel * c->hist_len, (size_t)c->hist_len * sizeof(int16_t), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(hist, c->d_hist[c->cur] + (size_t)per * channel * c->hist_len, (size_t)per * c->hist_len * sizeof(int16_t), hipMemcpyDeviceToHost));
     return 0;
 }
 extern "C" int msdr_chain_get_cmsis_state(msdr_chain *c, uint32_t channel, float32_t *pState)

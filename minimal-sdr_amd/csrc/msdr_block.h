@@ -84,6 +84,13 @@ int chain_dec_max(bool f32);
 int chain_dec_max_taps(bool f32, int D);
 hipError_t launch_chain_q15pcnd(hipStream_t stream, int num_cus, PcndParams p, PcLaunch *geo);
 hipError_t launch_chain_f32pcnd(hipStream_t stream, int num_cus, int time_segments, PcfndParams p, PcLaunch *geo);
+// ---- msdr_chain_cxncopc.hip, msdr_chain_cxdecpc.hip ----
+// chain_q15pcn_cx_kernel<CPW> ... chain_f32pcnd_cx_kernel<CPW, AL> (msdr_chain_cxpc.hiph): the four families above on rows of pairs {I, Q}
+// (msdr_chain_set_complex_input), p.cx_dir freq_conv's direction; validation, geometry and LDS exactly as their real twins'.
+hipError_t launch_chain_q15pcn_cx(hipStream_t stream, int num_cus, PcnCxParams p, PcLaunch *geo);
+hipError_t launch_chain_f32pcn_cx(hipStream_t stream, int num_cus, int time_segments, PcfnCxParams p, PcLaunch *geo);
+hipError_t launch_chain_q15pcnd_cx(hipStream_t stream, int num_cus, PcndCxParams p, PcLaunch *geo);
+hipError_t launch_chain_f32pcnd_cx(hipStream_t stream, int num_cus, int time_segments, PcfndCxParams p, PcLaunch *geo);
 // ---- msdr_chain_meter.hip ----
 // meter_reduce_kernel<T> (msdr_chain_meter.hiph): d_meter[ch] = the sum of part[ch][0 .. nseg) in that order -- the S-meter of a call that the
 // per-receiver kernels above ran in nseg > 1 time segments (their launchers call it; uint64_t sums for Q15, double for F32)

@@ -2,7 +2,9 @@
 // a launcher's own validation.  Host code of the translation units that hold the kernels; the geometry rule itself is msdr_pc_geometry.h.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "msdr_pc_geometry.h"
+#include "msdr_decpc_geometry.h"
 #include "msdr_block.h"
 
 namespace msdr {
@@ -36,6 +38,32 @@ inline hipError_t pc_launch(hipStream_t stream, P &p, bool valid, int num_cus, i
 {
     PcGeometry g;
     return pc_launch_geometry(stream, p, valid && pc_geometry(p.n, p.channels, num_cus, time_segments, outs_per_lane, kPcLdsCap, lds_bytes, &g), g, kernel_of, geo);
+}
+
+// f(std::integral_constant<int, AL>) for the kernels' read widths
+template <typename F>
+inline auto dec_dispatch_al(int al, F f)
+{
+    switch (al) {
+    case 4: return f(std::integral_constant<int, 4>());
+    case 2: return f(std::integral_constant<int, 2>());
+    case 1: return f(std::integral_constant<int, 1>());
+    default: return f(std::integral_constant<int, 0>());
+    }
+}
+
+// pc_launch for the decimating kernels (msdr_chain_decpc.hip and the complex-input twins, msdr_chain_cxdecpc.hip): launch geometry from
+// dec_geometry (msdr_decpc_geometry.h), everything in outputs; p.nout and p.opl beside the fields every parameter block carries.
+// kernel_of(CPW, AL): the instantiation for the read width al.
+template <typename P, typename KernelOf>
+inline hipError_t dec_launch(hipStream_t stream, P &p, bool valid, bool f32, int num_cus, int time_segments, int al, KernelOf kernel_of, PcLaunch *geo)
+{
+    if (!valid || p.dec < 2 || p.n % p.dec) return hipErrorInvalidValue;
+    p.nout = p.n / p.dec;
+    DecGeometry g;
+    const bool ok = dec_geometry(p.nout, p.channels, num_cus, time_segments, kPcLdsCap, [&](int cpw, int nw, int opl) { return dec_lds_bytes(f32, p.np, p.dec, cpw, nw, opl); }, &g);
+    if (ok) p.opl = g.opl;
+    return pc_launch_geometry(stream, p, ok, g, [&](auto cpw) { return dec_dispatch_al(al, [&](auto a) { return kernel_of(cpw, a); }); }, geo);
 }
 
 }  // namespace msdr

@@ -202,6 +202,18 @@ struct PcfndParams : PcfnParams {
     long long nout;
 };
 
+// the complex-input twins of those four (msdr_chain_cxpc.hiph; msdr_chain_set_complex_input): x is [channels or n_inputs][n] and hist_in
+// [channels][hist_len] PAIRS {I, Q} of two int16, one 4-byte aligned dword each; n, hist_len and every other count stay in samples.  A block of
+// its own, so that the real kernels keep their argument layout.
+template <typename P>
+struct CxParams : P {
+    int cx_dir;                // freq_conv's dir: 0 mixes with exp(-j phase), 1 with exp(+j phase)
+};
+typedef CxParams<PcnParams> PcnCxParams;
+typedef CxParams<PcfnParams> PcfnCxParams;
+typedef CxParams<PcndParams> PcndCxParams;
+typedef CxParams<PcfndParams> PcfndCxParams;
+
 // chain_f32pcb_kernel (msdr_chain_f32pcb.hiph): a whole block-cadence call of the fp32 chain with per-channel settings in one launch
 struct PcbParams {
     const int16_t *x;          // [channels][n] IF samples

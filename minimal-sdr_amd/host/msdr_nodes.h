@@ -275,13 +275,15 @@ private:
 // ------------------------------------------------------------------------------------------------
 class AudioSDRDemodulator : public AudioStream {
 public:
-    AudioSDRDemodulator(void) : AudioStream(1, inputQueueArray), chain(nullptr), num_taps(0), d_meter(nullptr), d_iq(nullptr), f32(false), in_scale(0.0f) {}
-    ~AudioSDRDemodulator() { if (chain) msdr_chain_destroy(chain); freeMeter(); freeIq(); }
+    // (two input ports, as AudioEffectFreqConv has: port 1 is the Q block of a complex stream under setComplexInput, released unread otherwise)
+    AudioSDRDemodulator(void) : AudioStream(2, inputQueueArray), chain(nullptr), num_taps(0), d_meter(nullptr), d_iq(nullptr), d_cx(nullptr), f32(false), in_scale(0.0f) {}
+    ~AudioSDRDemodulator() { if (chain) msdr_chain_destroy(chain); freeMeter(); freeIq(); freeCx(); }
     int begin(const msdr_chain_config &cfg)
     {
         if (chain) { msdr_chain_destroy(chain); chain = nullptr; }
         freeMeter();
         freeIq();
+        freeCx();
         f32 = cfg.arith == MSDR_ARITH_F32; in_scale = cfg.in_scale != 0.0f ? cfg.in_scale : 1.0f / 32768.0f;
         const bool i16_audio = cfg.arith == MSDR_ARITH_Q15 || (cfg.arith == MSDR_ARITH_F32 && (cfg.flags & MSDR_CHAIN_OUT_I16));
         if (!i16_audio || cfg.channels != AudioGPU.channels()) return MSDR_STATUS_ARGUMENT_ERROR;
@@ -433,17 +435,38 @@ public:
         if (n_out) *n_out = AUDIO_BLOCK_SAMPLES / D;
         return 0;
     }
+    // a complex antenna stream (msdr_chain_set_complex_input; AudioEffectFreqConv's two ports in front of every receiver's filters): while on, port 0
+    // carries I and port 1 carries Q of the tick -- a missing Q block counts as zeros -- and the node interleaves them into the block of pairs
+    // {I, Q} it uploads for the chain, which applies freq_conv's full mix in direction dir (0: down by the receiver's frequency, 1: up).  After
+    // setNco() only, and only over a clear FIR history: before the first tick, or directly after init_FIR().  The two blocks pass through the
+    // host, so this tick waits for what produced them.  setComplexInput(false, 0) brings the real input back and frees the buffer.
+    int setComplexInput(bool on, int dir)
+    {
+        if (!chain) return MSDR_STATUS_ARGUMENT_ERROR;
+        void *p = nullptr;
+        if (on && !d_cx) if (int rc = msdr_malloc(AudioGPU.context(), 2 * AudioGPU.block_bytes(), &p)) return rc;
+        if (int rc = msdr_chain_set_complex_input(chain, on ? 1 : 0, dir)) { if (p) msdr_free(AudioGPU.context(), p); return rc; }
+        if (p) d_cx = p;
+        if (!on) freeCx();
+        return 0;
+    }
     virtual void update(void)
     {
-        audio_block_t *in = receiveReadOnly();
-        if (!in) return;
+        audio_block_t *in = receiveReadOnly(0);
+        audio_block_t *inq = receiveReadOnly(1);
+        if (!in) { if (inq) release(inq); return; }
         audio_block_t *out = chain ? allocate() : nullptr;
         if (out) {
-            msdr_chain_process(chain, in->data, out->data, AUDIO_BLOCK_SAMPLES);
-            transmit(out);
+            // (a tick whose pairs could not be put together is dropped: the chain must never read a real block as pairs)
+            const bool ok = !d_cx || interleave(in, inq) == 0;
+            if (ok) {
+                msdr_chain_process(chain, d_cx ? (const int16_t *)d_cx : in->data, out->data, AUDIO_BLOCK_SAMPLES);
+                transmit(out);
+            }
             release(out);
         }
         release(in);
+        if (inq) release(inq);
     }
 
 private:
@@ -458,11 +481,28 @@ private:
         if (d_iq) msdr_free(AudioGPU.context(), d_iq);
         d_iq = nullptr;
     }
-    audio_block_t *inputQueueArray[1];
+    void freeCx(void)
+    {
+        if (d_cx) msdr_free(AudioGPU.context(), d_cx);
+        d_cx = nullptr;
+    }
+    // the tick's I block and Q block (nullptr: zeros) as [channels()][AUDIO_BLOCK_SAMPLES] pairs in d_cx
+    int interleave(const audio_block_t *bi, const audio_block_t *bq)
+    {
+        const size_t n = (size_t)AudioGPU.channels() * AUDIO_BLOCK_SAMPLES;
+        h_i.resize(n); h_q.assign(n, 0); h_pairs.resize(2 * n);
+        if (int rc = msdr_memcpy_d2h(AudioGPU.context(), h_i.data(), bi->data, AudioGPU.block_bytes())) return rc;
+        if (bq) if (int rc = msdr_memcpy_d2h(AudioGPU.context(), h_q.data(), bq->data, AudioGPU.block_bytes())) return rc;
+        for (size_t k = 0; k < n; k++) { h_pairs[2 * k] = h_i[k]; h_pairs[2 * k + 1] = h_q[k]; }
+        return msdr_memcpy_h2d(AudioGPU.context(), d_cx, h_pairs.data(), 2 * AudioGPU.block_bytes());
+    }
+    audio_block_t *inputQueueArray[2];
     msdr_chain *chain;
     uint32_t num_taps;
     void *d_meter;              // setMeter(true): [channels()] 8-byte sums, the node's own
     void *d_iq;                 // setIqOut(true): [channels()][AUDIO_BLOCK_SAMPLES] pairs {I, Q}, the node's own
+    void *d_cx;                 // setComplexInput(true, dir): [channels()][AUDIO_BLOCK_SAMPLES] pairs {I, Q} of the tick, the node's own
+    std::vector<int16_t> h_i, h_q, h_pairs;          // ... and the host side of the interleave
     bool f32;                   // the chain's arithmetic and int16 -> float scale, for readLevels and the size of a pair
     float in_scale;
 };

@@ -36,6 +36,7 @@ FLAVOUR_NCO_PC = 0x80000
 FLAVOUR_DECIMATED = 0x100000
 FLAVOUR_METER = 0x200000
 FLAVOUR_IQ_OUT = 0x400000
+FLAVOUR_COMPLEX_IN = 0x800000
 MAX_DECIMATION_Q15, MAX_DECIMATION_F32 = 60, 59
 FE_DCBLOCK, FE_AMP, FE_AGC, FE_ALL = 1, 2, 4, 7
 
@@ -120,6 +121,8 @@ def load_library(path=None):
                        ("msdr_meter_dbfs", [C.c_double, C.c_uint64, C.c_double]),
                        ("msdr_chain_set_iq_out", [_p, _p, C.c_uint64]),
                        ("msdr_chain_get_iq_out", [_p, _p, _p]),
+                       ("msdr_chain_set_complex_input", [_p, C.c_int, C.c_int]),
+                       ("msdr_chain_get_complex_input", [_p, _p, _p]),
                        ("msdr_nco_step", [C.c_double, C.c_double]),
                        ("msdr_nco_table", [_p]),
                        ("msdr_nco_q15", [_p, C.c_size_t, _p, _p]),
@@ -964,6 +967,19 @@ class Chain(_Instance):
         _ck(self.ctx.lib.msdr_chain_get_iq_out(self.h, C.byref(p), C.byref(pitch)))
         return p.value, pitch.value
 
+    def set_complex_input(self, on, dir=0):
+        """Complex I/Q input: from the next process() on d_if is [channels or n_inputs, n] PAIRS {I, Q} of two int16 (an int16 array
+        [rows, n, 2], 4-byte aligned) and the kernels apply freq_conv's full mix in direction dir (0: down by the receiver's frequency, 1: up;
+        Q = 0 with dir = 1 is the real chain).  Chains with set_nco_channels only, and only over a clear FIR history: before the first
+        process(), or directly after reset() / init_fir() (msdr_chain_set_complex_input)."""
+        _ck(self.ctx.lib.msdr_chain_set_complex_input(self.h, C.c_int(1 if on else 0), C.c_int(int(dir))))
+
+    def complex_input(self):
+        """(on, dir) in force (msdr_chain_get_complex_input)"""
+        on, d = C.c_int(0), C.c_int(0)
+        _ck(self.ctx.lib.msdr_chain_get_complex_input(self.h, C.byref(on), C.byref(d)))
+        return bool(on.value), d.value
+
     def set_block_kernel(self, on):
         """F32: a block-cadence call of a chain in per-channel mode as ONE launch (chain_f32pcb_kernel: demodulator, CMSIS-order cascade, int16
         conversion and the next history), bit-identical to the unfused launches, and capturable by graph().  Off by default; every state kept."""
@@ -986,10 +1002,12 @@ class Chain(_Instance):
         _ck(self.ctx.lib.msdr_chain_set_input_rows(self.h, C.c_uint32(ni), _hp(r)))
 
     def fir_history(self, channel):
-        """the raw int16 samples the chain carries for `channel`, oldest first (msdr_chain_get_fir_history)"""
+        """the raw int16 samples the chain carries for `channel`, oldest first; [hist_len, 2] pairs {I, Q} under set_complex_input
+        (msdr_chain_get_fir_history)"""
         n = C.c_uint32(0)
         _ck(self.ctx.lib.msdr_chain_get_fir_history(self.h, C.c_uint32(channel), None, C.c_uint32(0), C.byref(n)))
-        h = np.zeros(n.value, np.int16)
+        cx = hasattr(self.ctx.lib, "msdr_chain_get_complex_input") and self.complex_input()[0]
+        h = np.zeros((n.value, 2) if cx else n.value, np.int16)
         _ck(self.ctx.lib.msdr_chain_get_fir_history(self.h, C.c_uint32(channel), _hp(h), C.c_uint32(h.size), None))
         return h
 
