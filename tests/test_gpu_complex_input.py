@@ -137,8 +137,10 @@ def dec_ref(orc, golden):
 @pytest.mark.parametrize("D", [2, 3, 4, 8, 32])
 def test_decimation(ctx, dec_ref, D):
     """odd D: two window copies (AL 0); 2, 4, 8, 32: AL 1, 2, 4, 4.  256 D inputs in calls of 32 and 128 outputs (4 channels per wave) and one of
-    256 (2 per wave); one call of 301 outputs -- not a multiple of any tile: a partial last tile -- at 2 or 1 channels per wave; meter and I/Q
-    buffer both set"""
+    256 (2 per wave); one call of 301 outputs -- not a multiple of any tile: a partial last tile -- at 1 channel per wave; meter and I/Q
+    buffer both set.  So every launch here is the _cx_iq_meter twin: its 12 (CPW, AL) instantiations are met, at 102 taps (no CPW lowered by the LDS fit); the
+    36 of the plain, metered and I/Q twins are not (test_one_channel_per_wave_decimated adds one of them).  tests/test_gpu_cx_census.py holds
+    all 48, under every launch geometry"""
     r = dec_ref
     cpws = set()
     for nout in (32, 128, 256, 301):

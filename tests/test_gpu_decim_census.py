@@ -54,7 +54,8 @@ def run_entry(ctx, chain, e, adtype, pdtype=None, mdtype=None, flavour=None, x=N
     stretches of the sentinel, and everything outside the written rows must still hold it.  flavour(info): a check of the family's own.
     The census of the sliding-window kernels (tests/pc_census_cases.py: no "D" in an entry, audio of n samples per row) hands in its own stream
     x, its calls' lengths, its reading of info() (ran; None: an instance without an info call; read: behind which calls) and, for an input map,
-    feed(the call's columns of x) -> what is uploaded."""
+    feed(the call's columns of x) -> what is uploaded.  The census of the complex-input twins (tests/cx_census_cases.py) hands in a stream of
+    pairs, x [rows, n, 2]: a call's columns are then n pairs per row, and nothing else changes."""
     ch, D = e["channels"], e.get("D", 1)
     x = cases.data(e)["x"] if x is None else x
     audio, pairs, meters, lo = [], [], [], 0
@@ -105,7 +106,8 @@ def refusal(ctx, e, make, run, ask=None, x=None):
     is what a control chain that was never asked is: the same decimation, the same bits, the same info().  (Beyond 4096 taps the interface
     refuses the filter itself.)  make(nt) -> a chain of nt taps in phase-accumulator mode; run(chain, x) -> its audio of one call.
     The census of the sliding-window kernels asks another setter: ask(chain) makes the call that must be refused (and make(nt) the chain in the
-    state before it); x: the 128 samples per row both chains then process."""
+    state before it); x: the 128 samples per row both chains then process.  Under msdr_chain_set_complex_input (tests/cx_census_cases.py: make
+    gives a chain with the mode on, x is pairs) the refusal leaves the mode as it was, too."""
     nt = e["refuse"]
     if nt > cases.TAP_CAP:
         with pytest.raises(msdr.MsdrError) as err:
@@ -116,7 +118,7 @@ def refusal(ctx, e, make, run, ask=None, x=None):
     with pytest.raises(msdr.MsdrError) as err:
         a.set_decimation(e["D"]) if ask is None else ask(a)
     assert err.value.status == ARG and "nothing changed" in str(err.value), err.value
-    assert a.decimation() == control.decimation() == 1
+    assert a.decimation() == control.decimation() == 1 and a.complex_input() == control.complex_input()
     x = cases.data(e)["x"][:, :128] if x is None else x
     ga, gb = run(a, x), run(control, x)
     assert np.array_equal(raw(ga), raw(gb)) and a.info() == control.info()

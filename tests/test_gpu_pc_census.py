@@ -40,21 +40,27 @@ def ran(info, e):
     assert info["lds_bytes"] == e["lds"] and info["time_segments"] == e["nseg"], (info, e)
 
 
-def antenna(e):
-    """(the stream that is uploaded, feed of run_entry): with an input map the two antenna rows at the start of a buffer of the replicated size"""
-    x = cases.data(e)["x"]
+def antenna(e, x=None):
+    """(the stream that is uploaded, feed of run_entry): with an input map the two antenna rows at the start of a buffer of the replicated size.
+    x: a stream in place of the entry's own -- [channels, total], or [channels, total, 2] pairs (tests/cx_census_cases.py): the antenna rows
+    are then rows of pairs, with the same junk behind them"""
+    x = cases.data(e)["x"] if x is None else x
     if not e["inmap"]:
         return x, None
 
     def feed(part):
-        full = np.full((e["channels"], part.shape[1]), JUNK, part.dtype)
+        full = np.full((e["channels"],) + part.shape[1:], JUNK, part.dtype)
         full.reshape(-1)[:part.size] = part.reshape(-1)
         return full
     return x[:2], feed
 
 
-def run_pc(ctx, chain, e, adtype, pdtype=None, mdtype=None, flavour=None, replicated=False):
-    x, feed = (cases.heard(e), None) if replicated else antenna(e)
+def run_pc(ctx, chain, e, adtype, pdtype=None, mdtype=None, flavour=None, replicated=False, x=None):
+    """the entry's calls through run_entry; replicated: every channel's own row is uploaded (the chain has no input map); x: as antenna's"""
+    if replicated:
+        x, feed = (cases.heard(e) if x is None else x[np.arange(e["channels"]) % 2] if e["inmap"] else x), None
+    else:
+        x, feed = antenna(e, x)
     return run_entry(ctx, chain, e, adtype, pdtype, mdtype, flavour, x=x, calls=cases.calls(e), ran=ran if e["chain"] else None, feed=feed, read=cases.read_at(e))
 
 
