@@ -810,6 +810,39 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   Reporting: msdr_chain_get_info().kernel keeps its names (the complex-input twins, chain_q15pcn_cx_kernel ..., run under them); on fp32
  *   chains flavour carries MSDR_FLAVOUR_COMPLEX_IN exactly while the mode is on.  Graphs stay refused, as on every chain in this mode.
  * msdr_chain_get_complex_input: the switch and the direction in force (0, 0 on a chain that never set them); either output may be NULL.
+ * msdr_chain_set_gain / msdr_chain_set_gain_channels / msdr_chain_set_agc: gain control per RECEIVER.  The reference levels the signal in front
+ *   of the FIR with amp_adc.gain(AGC_val) and AGC() (Minimal-SDR.ino:385, 445-515); msdr_frontend has that pair once per input row, and with
+ *   one antenna row feeding a bank that is one gain for stations 60 dB apart.  Behind a Q15 channel filter the 15 dropped bits cannot be
+ *   amplified back, so the bank's amplifier works on the FIR accumulators.  Every receiver holds AGC_val (float) and
+ *   multiplier = AudioAmplifier::gain's (mixer.h:75-79: clamp to +-32767, (int32)(n * 65536.0f)).  While gain is on, the pair I, Q of every
+ *   output -- the two FIR outputs the demodulator receives -- is
+ *     Q15   ssat16((int64(acc) * multiplier) >> 31), arithmetic shift, acc the wrapping 32-bit accumulator of arm_fir_fast_q15:
+ *           applyGain's (mult * s) >> 16 moved in front of the >> 15.  multiplier 65536 is ssat16(acc >> 15) exactly, 0 gives zeros.
+ *     F32   acc * gain, one rounded fp32 multiply, gain = AGC_val after the same clamp.
+ *   The demodulator (every mode), the hand-over to the Q15 PLL at D = 1 and msdr_chain_set_iq_out receive the GAINED pair (USB / LSB audio
+ *   stays I +- Q of the stored pairs); msdr_chain_set_meter keeps measuring the UNGAINED pair: an S-meter does not move with the AGC.
+ *   AGC(): behind every successful msdr_chain_process (I/Q-only calls included; a call that returns an error steps nothing), on the chain's
+ *   stream and without a host synchronisation, every receiver whose AGC is on takes ONE step of Minimal-SDR.ino:479-513 with
+ *     absmax = min(32767, max over the call's n_out outputs of max(|I|, |Q|)) of the gained pair
+ *   (F32: (int32) fminf(peak / in_scale, 32767.0f), the division IEEE-rounded): the ring of 25 with the dropped 26th store, the integer mean,
+ *   f = 16000 / mean (mean 0: +inf), the five rules and AGC_Max, the multiplier recomputed when a rule fires.  The new multiplier holds from
+ *   the NEXT call: inside a call the gain is constant.  At 128 outputs per call this is the reference's cadence; longer calls step more
+ *   slowly (one step per call, whatever its length).  absmax is recorded for every receiver, held or stepped.
+ *   msdr_chain_set_gain(on): off (default) runs the kernels of a chain without gain and leaves the state alone; on runs the gain twins.
+ *   msdr_chain_set_gain_channels: msdr_frontend_gain per receiver -- AGC_val = gain[k] (host array, read during the call) and its multiplier,
+ *   behind every call enqueued so far, in force from the next call; the ring is untouched.  msdr_chain_set_agc: agc_on is a host array of
+ *   `channels` values or NULL (agc_on_all for every receiver), 0 = held, 1 = stepped.  The state of a receiver is made by the first of these
+ *   three calls -- AGC_val 1.0, multiplier 65536, ring zero, agc_idx 25, AGC off, so that msdr_chain_set_gain(on) alone changes no bit of
+ *   any output -- and lives until msdr_chain_destroy.
+ *   msdr_chain_get_agc synchronises and returns a receiver's record: [0] multiplier (F32: the bits of the clamped gain), [1] agc_idx,
+ *   [2] AGC_val (float bits), [3] absmax of the last call, [4] steps taken, [5..6] zero, [7..31] agc_buffer[0..24].
+ *   Chains in phase-accumulator mode only (msdr_chain_set_decimation's scope rule), Q15 and F32, every D, real and complex input.  A NULL
+ *   chain, a chain in another mode, a range past `channels`, a NULL gain with count > 0, a gain that is not finite and an agc_on value other
+ *   than 0 or 1 are MSDR_STATUS_ARGUMENT_ERROR, nothing changed.  Everything survives what the decimation factor survives and combines, in
+ *   either order, with msdr_chain_set_decimation, set_meter, set_iq_out, set_complex_input, set_input_rows and MSDR_CHAIN_OUT_I16, and on
+ *   Q15 chains with MSDR_CHAIN_SYNCAM_PLL at D = 1 and msdr_chain_set_anr.
+ *   Reporting: msdr_chain_get_info().kernel keeps its names (the gain twins, chain_q15pcn_gain_kernel ..., run under them); on fp32 chains
+ *   flavour carries MSDR_FLAVOUR_GAIN exactly while gain is on.  Graphs stay refused, as on every chain in this mode.
  * msdr_nco_step (host only): llround(f_hz / fs_hz * 2^32) mod 2^32; a negative frequency wraps (-6000 at 24000: 0xC0000000).
  * msdr_nco_table (host only): T[i] = (int16) lround(32767 sin(2 pi i / 1024)), i = 0 .. 1024, T[1024] = 0.
  * msdr_nco_q15 (host only; what the kernels compute): for each uint32 phase, i = phase >> 22, f = (phase >> 6) & 0xFFFF,
@@ -831,6 +864,12 @@ int msdr_chain_set_iq_out(msdr_chain *chain, void *d_iq, uint64_t pitch);   /* N
 int msdr_chain_get_iq_out(msdr_chain *chain, void **d_iq, uint64_t *pitch); /* either may be NULL */
 int msdr_chain_set_complex_input(msdr_chain *chain, int on, int dir);   /* off (default): real IF */
 int msdr_chain_get_complex_input(msdr_chain *chain, int *on, int *dir); /* either may be NULL */
+int msdr_chain_set_gain(msdr_chain *chain, int on);                       /* off (default): the kernels of a chain without gain */
+int msdr_chain_get_gain(msdr_chain *chain, int *on);
+int msdr_chain_set_gain_channels(msdr_chain *chain, uint32_t first_channel, uint32_t count, const float *gain);
+int msdr_chain_set_agc(msdr_chain *chain, const int32_t *agc_on, int32_t agc_on_all);   /* msdr_chain_set_anr's argument shape */
+#define MSDR_AGC_STATE_WORDS 32u
+int msdr_chain_get_agc(msdr_chain *chain, uint32_t channel, int32_t state[MSDR_AGC_STATE_WORDS]);
 int msdr_chain_set_taps(msdr_chain *chain, uint32_t tapset, const void *coeffs_i, const void *coeffs_q);
 int msdr_chain_set_taps_channels(msdr_chain *chain, uint32_t first_channel, uint32_t count,
                                  const q15_t *coeffs_i, const q15_t *coeffs_q);
@@ -912,6 +951,9 @@ enum { MSDR_FLAVOUR_IQ_OUT = 0x400000u };
 /* And another: the demodulator kernel mixed rows of complex pairs -- the complex-input twin of a phase-accumulator kernel,
  * msdr_chain_set_complex_input on (always beside MSDR_FLAVOUR_NCO_PC). */
 enum { MSDR_FLAVOUR_COMPLEX_IN = 0x800000u };
+/* And another: the demodulator kernel multiplied the pair by every receiver's gain -- the gain twin of a phase-accumulator kernel,
+ * msdr_chain_set_gain on (always beside MSDR_FLAVOUR_NCO_PC). */
+enum { MSDR_FLAVOUR_GAIN = 0x1000000u };
 int msdr_chain_get_info(msdr_chain *chain, msdr_chain_info *info);
 /* The wave-stream kernels read the run geometry of a tap table (which chunks of the window each accumulator walks, which runs merge their first
  * and last step) from the table's header -- or, for the geometries the library instantiates, have it as compile-time constants: the same

@@ -2536,6 +2536,12 @@ struct msdr_chain {
     // pairs on every chain (2 x channels x hist_len int16), so the switch, made over a clear history only, converts and allocates nothing.
     bool cx_on = false;
     int cx_dir = 0;
+    // msdr_chain_set_gain (chains with nco_active only): while gain_on the gain twins of the phase-accumulator kernels run (msdr_chain_gain.hiph)
+    // and agc_step_kernel follows every call.  d_agc holds every receiver's record [channels][kGainWords], made by the first of
+    // msdr_chain_set_gain / msdr_chain_set_gain_channels / msdr_chain_set_agc and kept for the chain's life; the host keeps no copy of it (the
+    // step kernel rewrites it on the stream).
+    bool gain_on = false;
+    int *d_agc = nullptr;
     msdr_chain_info info;
     // optional per-launch timing of the main kernel
     bool timing;
@@ -2643,7 +2649,7 @@ static void chain_free(msdr_chain *c)
     hipFree(c->d_anr_on);
     for (auto &e : c->events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (auto &o : c->osc_pending) hipFree(o.d_tab);
-    hipFree(c->d_f32_scratch); hipFree(c->d_osc_hist); hipFree(c->d_btiles); hipFree(c->d_pc_taps); hipFree(c->d_pcf_taps); hipFree(c->d_osc_bank); hipFree(c->d_in_row); hipFree(c->d_meter_part);
+    hipFree(c->d_f32_scratch); hipFree(c->d_osc_hist); hipFree(c->d_btiles); hipFree(c->d_pc_taps); hipFree(c->d_pcf_taps); hipFree(c->d_osc_bank); hipFree(c->d_in_row); hipFree(c->d_meter_part); hipFree(c->d_agc);
     hipFree(c->d_nco_bank); hipFree(c->d_nco_tab);
     delete c;
 }
@@ -3645,6 +3651,47 @@ static int chain_post_run(msdr_chain *c, const int16_t *d_if, float *d_audio, ui
     return launch_check("post_scatter_rows_kernel");
 }
 
+// ---- AGC(), one lane per receiver (Minimal-SDR.ino:479-513; the float operations are msdr_frontend.hiph's, which match orc_agc_block) -------------------
+// absmax of the call that just ran: Q15 min(32767, peak); F32 (int) fminf(peak / in_scale, 32767), the division IEEE-rounded.  Every receiver's
+// word 3 takes it and word 6 is zeroed for the next call; a receiver with AGC on takes one step.
+__global__ __launch_bounds__(64) void agc_step_kernel(int *__restrict__ agc, int channels, int f32, float in_scale)
+{
+    const int ch = blockIdx.x * 64 + threadIdx.x;
+    if (ch >= channels) return;
+    int *st = agc + (long long)ch * kGainWords;
+    const unsigned pk = (unsigned)st[kGainPeak];
+    st[kGainPeak] = 0;
+    const int absmax = f32 ? (int)fminf(__fdiv_rn(__uint_as_float(pk), in_scale), 32767.0f) : (int)min(pk, 32767u);
+    st[kGainAbsmax] = absmax;
+    if (!st[kGainOn]) return;
+    st[kGainSteps] += 1;
+    int idx = st[kGainIdx] - 1;                                                       // :480 (the store to [-1] is dropped)
+    if (idx >= 0) st[kGainRing + idx] = absmax;
+    else idx = kGainRingLen;                                                          // :481
+    st[kGainIdx] = idx;
+    int m = 0;
+    for (int k = 0; k < kGainRingLen; k++) m += st[kGainRing + k];
+    const int d = m / kGainRingLen;                                                   // :485
+    const float f = __fdiv_rn(16000.0f, (float)d);                                    // :488 (d == 0: +inf)
+    float v = __int_as_float(st[kGainVal]);
+    bool set = false;
+    if ((double)f > 1.3) {
+        const float fagc = fe_add(v, __fdiv_rn(fe_mul(v, f), 1500.0f));
+        if (fagc < 40.0f) { v = fagc; set = true; }                                   // AGC_Max, :95
+    } else if ((double)v > 0.1) {
+        float div = 0.0f;
+        if ((double)f < 0.6) div = 50.0f;
+        else if ((double)f < 0.7) div = 200.0f;
+        else if ((double)f < 0.8) div = 2000.0f;
+        else if ((double)f < 0.9) div = 4000.0f;
+        if (div != 0.0f) { v = fe_sub(v, __fdiv_rn(fe_mul(v, f), div)); set = true; }
+    }
+    if (set) {
+        st[kGainVal] = __float_as_int(v);
+        st[kGainMult] = f32 ? __float_as_int(gain_clamp(v)) : fe_multiplier(v);
+    }
+}
+
 // fp32 audio -> int16 as arm_float_to_q15 (MSDR_CHAIN_OUT_I16 behind the kernels that do not convert in their own store phase)
 __global__ void f32_to_q15_kernel(const float *__restrict__ src, short *__restrict__ dst, long long total)
 {
@@ -4154,16 +4201,22 @@ static int chain_launch_f32pc(msdr_chain *c, const ChainDecision &, const ChainP
         PcfndCxParams qd;          // (msdr_chain_set_complex_input: the twin's block is the real kernel's and the direction)
         static_cast<PcfnParams &>(qd) = q;
         qd.sin_tab = c->d_nco_tab; qd.t0 = (unsigned)c->nco_T; qd.dec = (int)c->decim; qd.opl = 0; qd.nout = 0; qd.cx_dir = c->cx_dir;
-        if ((c->cx_on ? launch_chain_f32pcnd_cx(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, qd, &geo)
-                      : launch_chain_f32pcnd(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, qd, &geo)) != hipSuccess)
+        PcfndGainParams qg;          // (msdr_chain_set_gain: the twin's block is that one and the receivers' records)
+        static_cast<PcfndCxParams &>(qg) = qd; qg.agc = c->d_agc;
+        if ((c->gain_on ? launch_chain_f32pcnd_gain(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, c->cx_on, qg, &geo)
+             : c->cx_on ? launch_chain_f32pcnd_cx(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, qd, &geo)
+                        : launch_chain_f32pcnd(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, qd, &geo)) != hipSuccess)
             return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pcnd_kernel launch failed");
         r.kname = kPcfndKernelName; r.flavour |= MSDR_FLAVOUR_NCO_PC | MSDR_FLAVOUR_DECIMATED | (c->cx_on ? (uint32_t)MSDR_FLAVOUR_COMPLEX_IN : 0u);
     } else if (c->nco_active) {
         PcfnCxParams qn;
         static_cast<PcfnParams &>(qn) = q;
         qn.sin_tab = c->d_nco_tab; qn.t0 = (unsigned)c->nco_T; qn.cx_dir = c->cx_dir;
-        if ((c->cx_on ? launch_chain_f32pcn_cx(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, qn, &geo)
-                      : launch_chain_f32pcn(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, qn, &geo)) != hipSuccess)
+        PcfnGainParams qg;
+        static_cast<PcfnCxParams &>(qg) = qn; qg.agc = c->d_agc;
+        if ((c->gain_on ? launch_chain_f32pcn_gain(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, c->cx_on, qg, &geo)
+             : c->cx_on ? launch_chain_f32pcn_cx(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, qn, &geo)
+                        : launch_chain_f32pcn(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, qn, &geo)) != hipSuccess)
             return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pcn_kernel launch failed");
         r.kname = kPcfnKernelName; r.flavour |= MSDR_FLAVOUR_NCO_PC | (c->cx_on ? (uint32_t)MSDR_FLAVOUR_COMPLEX_IN : 0u);
     } else if (c->opc_active) {
@@ -4177,7 +4230,8 @@ static int chain_launch_f32pc(msdr_chain *c, const ChainDecision &, const ChainP
     }
     pc_geometry_of(geo, r);
     r.flavour |= MSDR_FLAVOUR_TAPS_PC | (geo.nseg > 1 ? MSDR_FLAVOUR_SEGMENTED : 0u) | (c->n_inputs ? (uint32_t)MSDR_FLAVOUR_SHARED_IF : 0u) |
-                 (c->d_meter ? (uint32_t)MSDR_FLAVOUR_METER : 0u) | (c->d_iq ? (uint32_t)MSDR_FLAVOUR_IQ_OUT : 0u);
+                 (c->d_meter ? (uint32_t)MSDR_FLAVOUR_METER : 0u) | (c->d_iq ? (uint32_t)MSDR_FLAVOUR_IQ_OUT : 0u) |
+                 ((c->nco_active && c->gain_on) ? (uint32_t)MSDR_FLAVOUR_GAIN : 0u);
     return 0;
 }
 
@@ -4366,14 +4420,20 @@ static int chain_launch_q15pc(msdr_chain *c, const ChainDecision &, const ChainP
         PcndCxParams qd;          // (msdr_chain_set_complex_input: the twin's block is the real kernel's and the direction)
         static_cast<PcnParams &>(qd) = q;
         qd.sin_tab = c->d_nco_tab; qd.t0 = (unsigned)c->nco_T; qd.dec = (int)c->decim; qd.opl = 0; qd.nout = 0; qd.cx_dir = c->cx_dir;
-        if ((c->cx_on ? launch_chain_q15pcnd_cx(c->ctx->stream, c->ctx->num_cus, qd, &geo) : launch_chain_q15pcnd(c->ctx->stream, c->ctx->num_cus, qd, &geo)) != hipSuccess)
+        PcndGainParams qg;          // (msdr_chain_set_gain: the twin's block is that one and the receivers' records)
+        static_cast<PcndCxParams &>(qg) = qd; qg.agc = c->d_agc;
+        if ((c->gain_on ? launch_chain_q15pcnd_gain(c->ctx->stream, c->ctx->num_cus, c->cx_on, qg, &geo)
+             : c->cx_on ? launch_chain_q15pcnd_cx(c->ctx->stream, c->ctx->num_cus, qd, &geo) : launch_chain_q15pcnd(c->ctx->stream, c->ctx->num_cus, qd, &geo)) != hipSuccess)
             return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pcnd_kernel launch failed");
         r.kname = kPcndKernelName;
     } else if (c->nco_active) {
         PcnCxParams qn;
         static_cast<PcnParams &>(qn) = q;
         qn.sin_tab = c->d_nco_tab; qn.t0 = (unsigned)c->nco_T; qn.cx_dir = c->cx_dir;
-        if ((c->cx_on ? launch_chain_q15pcn_cx(c->ctx->stream, c->ctx->num_cus, qn, &geo) : launch_chain_q15pcn(c->ctx->stream, c->ctx->num_cus, qn, &geo)) != hipSuccess)
+        PcnGainParams qg;
+        static_cast<PcnCxParams &>(qg) = qn; qg.agc = c->d_agc;
+        if ((c->gain_on ? launch_chain_q15pcn_gain(c->ctx->stream, c->ctx->num_cus, c->cx_on, qg, &geo)
+             : c->cx_on ? launch_chain_q15pcn_cx(c->ctx->stream, c->ctx->num_cus, qn, &geo) : launch_chain_q15pcn(c->ctx->stream, c->ctx->num_cus, qn, &geo)) != hipSuccess)
             return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pcn_kernel launch failed");
         r.kname = kPcnKernelName;
     } else if (c->opc_active) {
@@ -4564,6 +4624,12 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
         for (auto &o : c->osc_pending) o.elapsed += (long long)n_samples;
         if (c->osc_pending.empty() || c->osc_pending.back().elapsed >= (long long)c->hist_len)
             if (int rc2 = chain_leave_generic(c)) return rc2;
+    }
+    // msdr_chain_set_gain: AGC(), once per call as demodulation() runs it, behind everything that can fail -- the call's peaks to the records, one
+    // step for every receiver whose AGC is on; the multipliers it leaves are the next call's
+    if (c->nco_active && c->gain_on) {
+        hipLaunchKernelGGL(agc_step_kernel, dim3((c->channels + 63) / 64), dim3(64), 0, c->ctx->stream, c->d_agc, (int)c->channels, f32 ? 1 : 0, c->in_scale);
+        if (int rc2 = launch_check("agc_step_kernel")) return rc2;
     }
 
     // ---- info
@@ -4975,6 +5041,7 @@ static int chain_rebuild(msdr_chain *c, const ChainCfgStore &edited, void **stea
     n->decim = c->decim;          // (msdr_chain_set_decimation holds through every rebuild)
     n->d_iq = c->d_iq; n->iq_pitch = c->iq_pitch;          // (and so does msdr_chain_set_iq_out)
     n->cx_on = c->cx_on; n->cx_dir = c->cx_dir;          // (and msdr_chain_set_complex_input: the history above went over as pairs)
+    n->gain_on = c->gain_on; std::swap(n->d_agc, c->d_agc);          // (and msdr_chain_set_gain with every receiver's record)
     std::swap(*c, *n);
     if (steal_osc) { *steal_osc = n->d_osc; n->d_osc = nullptr; }
     chain_free(n);
@@ -5540,6 +5607,101 @@ extern "C" int msdr_chain_get_complex_input(msdr_chain *c, int *on, int *dir)
     if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
     if (on) *on = c->cx_on ? 1 : 0;
     if (dir) *dir = c->cx_dir;
+    return 0;
+}
+
+// ---- per-receiver gain and AGC (msdr_chain_gain.hiph) ----
+// the receivers' records, made once: AGC_val 1.0, its multiplier (Q15: 65536, the plain kernels' arithmetic; F32: 1.0f), ring zero,
+// agc_idx 25 (Minimal-SDR.ino:451), AGC off
+static int chain_agc_ensure(msdr_chain *c)
+{
+    if (c->d_agc) return 0;
+    std::vector<int> h((size_t)c->channels * kGainWords, 0);
+    const float one = 1.0f;
+    int one_bits;
+    memcpy(&one_bits, &one, sizeof one_bits);
+    for (uint32_t ch = 0; ch < c->channels; ch++) {
+        int *st = h.data() + (size_t)ch * kGainWords;
+        st[kGainMult] = c->arith == MSDR_ARITH_F32 ? one_bits : fe_multiplier(one);
+        st[kGainIdx] = kGainRingLen; st[kGainVal] = one_bits;
+    }
+    return upload(c->ctx, h, &c->d_agc);
+}
+// what the three setters share: the scope rule of msdr_chain_set_decimation
+static int chain_gain_scope(msdr_chain *c, const char *what)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (int rc = bind(c->ctx)) return rc;
+    if (!c->nco_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "%s: only on a chain with the phase-accumulator oscillator (msdr_chain_set_nco_channels); nothing changed", what);
+    return 0;
+}
+
+// A switch of the host's, read by the next msdr_chain_process: on, the gain twins run and AGC() follows every call; off, the plain kernels
+// run and the records rest.  Everything that can fail happens before anything changes.
+extern "C" int msdr_chain_set_gain(msdr_chain *c, int on)
+{
+    if (int rc = chain_gain_scope(c, "gain")) return rc;
+    if (on) if (int rc = chain_agc_ensure(c)) return rc;
+    c->gain_on = on != 0;
+    return 0;
+}
+
+extern "C" int msdr_chain_get_gain(msdr_chain *c, int *on)
+{
+    if (!c || !on) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
+    *on = c->gain_on ? 1 : 0;
+    return 0;
+}
+
+// msdr_frontend_gain per receiver: AGC_val = gain[k] and its multiplier, behind every call enqueued so far; the ring stays
+extern "C" int msdr_chain_set_gain_channels(msdr_chain *c, uint32_t first_channel, uint32_t count, const float *gain)
+{
+    if (int rc = chain_gain_scope(c, "gain")) return rc;
+    if (first_channel > c->channels || count > c->channels - first_channel)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "channels %u .. %llu of %u; nothing changed", first_channel, (unsigned long long)first_channel + count - 1, c->channels);
+    if (count && !gain) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null gain array; nothing changed");
+    for (uint32_t k = 0; k < count; k++) if (!std::isfinite(gain[k])) return fail(MSDR_STATUS_ARGUMENT_ERROR, "gain %u is not finite; nothing changed", k);
+    if (int rc = chain_agc_ensure(c)) return rc;
+    if (count == 0) return 0;
+    std::vector<int> words((size_t)count * 2);          // [count] multipliers | [count] AGC_val bits
+    for (uint32_t k = 0; k < count; k++) {
+        const float v = gain[k], g = gain_clamp(v);
+        if (c->arith == MSDR_ARITH_F32) memcpy(&words[k], &g, sizeof(int)); else words[k] = fe_multiplier(v);
+        memcpy(&words[count + k], &v, sizeof(int));
+    }
+    HIP_TRY(hipStreamSynchronize(c->ctx->stream));          // (the step kernel of a call in flight rewrites the same words)
+    int *first = c->d_agc + (size_t)first_channel * kGainWords;
+    HIP_TRY(hipMemcpy2D(first + kGainMult, kGainWords * sizeof(int), words.data(), sizeof(int), sizeof(int), count, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy2D(first + kGainVal, kGainWords * sizeof(int), words.data() + count, sizeof(int), sizeof(int), count, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// which receivers AGC() steps (1) and which it leaves at their gain (0): msdr_chain_set_anr's argument shape
+extern "C" int msdr_chain_set_agc(msdr_chain *c, const int32_t *agc_on, int32_t agc_on_all)
+{
+    if (int rc = chain_gain_scope(c, "AGC")) return rc;
+    if (!agc_on && agc_on_all != 0 && agc_on_all != 1) return fail(MSDR_STATUS_ARGUMENT_ERROR, "agc_on_all %d: 0 (held) or 1 (stepped); nothing changed", (int)agc_on_all);
+    if (agc_on) for (uint32_t ch = 0; ch < c->channels; ch++)
+        if (agc_on[ch] != 0 && agc_on[ch] != 1) return fail(MSDR_STATUS_ARGUMENT_ERROR, "agc_on[%u] = %d: 0 (held) or 1 (stepped); nothing changed", ch, (int)agc_on[ch]);
+    if (int rc = chain_agc_ensure(c)) return rc;
+    std::vector<int> h(c->channels, (int)agc_on_all);
+    if (agc_on) for (uint32_t ch = 0; ch < c->channels; ch++) h[ch] = (int)agc_on[ch];
+    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+    HIP_TRY(hipMemcpy2D(c->d_agc + kGainOn, kGainWords * sizeof(int), h.data(), sizeof(int), sizeof(int), c->channels, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// a receiver's record behind every call enqueued so far (synchronises); words 5 and 6 are the kernels' own and read as zero
+extern "C" int msdr_chain_get_agc(msdr_chain *c, uint32_t channel, int32_t state[MSDR_AGC_STATE_WORDS])
+{
+    static_assert(MSDR_AGC_STATE_WORDS == kGainWords, "the record is what the kernels keep");
+    if (!c || !state) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
+    if (int rc = bind(c->ctx)) return rc;
+    if (!c->nco_active || !c->d_agc) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has no gain state (msdr_chain_set_gain / msdr_chain_set_gain_channels / msdr_chain_set_agc)");
+    if (channel >= c->channels) return fail(MSDR_STATUS_ARGUMENT_ERROR, "channel %u of %u", channel, c->channels);
+    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+    HIP_TRY(hipMemcpy(state, c->d_agc + (size_t)channel * kGainWords, kGainWords * sizeof(int), hipMemcpyDeviceToHost));
+    state[kGainOn] = 0; state[kGainPeak] = 0;
     return 0;
 }
 

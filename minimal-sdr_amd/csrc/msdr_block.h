@@ -11,6 +11,7 @@
 //   msdr_chain_oscpc.hip   the frames of the two chains above with the oscillator policy "a row of a bank per channel": chain_q15pco_kernel, chain_f32pco_kernel
 //   msdr_chain_ncopc.hip   the same frames with the policy "a phase accumulator per channel": chain_q15pcn_kernel, chain_f32pcn_kernel
 //   msdr_chain_decpc.hip   that policy under a decimating tile loop: chain_q15pcnd_kernel, chain_f32pcnd_kernel
+//   msdr_chain_gncopc.hip, msdr_chain_gdecpc.hip   the gain twins of the phase-accumulator and decimating kernels, real and complex input: chain_*_gain_kernel
 //   msdr_chain_meter.hip   the S-meter's second step behind those kernels' metered flavours: meter_reduce_kernel
 //                          (the baseband I/Q output, msdr_chain_iq.hiph, is a flavour of the four phase-accumulator kernels in their own units: chain_*_iq_kernel, chain_*_iq_meter_kernel)
 //   msdr_chain_f32pcb.hip  the fp32 chain with per-channel settings at block cadence, one launch per call: chain_f32pcb_kernel
@@ -91,6 +92,15 @@ hipError_t launch_chain_q15pcn_cx(hipStream_t stream, int num_cus, PcnCxParams p
 hipError_t launch_chain_f32pcn_cx(hipStream_t stream, int num_cus, int time_segments, PcfnCxParams p, PcLaunch *geo);
 hipError_t launch_chain_q15pcnd_cx(hipStream_t stream, int num_cus, PcndCxParams p, PcLaunch *geo);
 hipError_t launch_chain_f32pcnd_cx(hipStream_t stream, int num_cus, int time_segments, PcfndCxParams p, PcLaunch *geo);
+// ---- msdr_chain_gncopc.hip, msdr_chain_gdecpc.hip ----
+// chain_q15pcn_gain_kernel<CPW> ... chain_f32pcnd_cx_gain_kernel<CPW, AL> (msdr_chain_gain.hiph): the gain twins of the eight families above
+// (msdr_chain_set_gain), one per family and geometry -- the metered I/Q body with the receiver's gain on the pair; a null p.meter / p.iq skips
+// that part.  cx: rows of pairs, p.cx_dir (else not read).  p.agc: the receivers' records [channels][kGainWords]; word 6 of each takes the
+// call's peak, which agc_step_kernel (msdr_api.hip) consumes behind the call.  Validation, geometry and LDS exactly as the plain twins'.
+hipError_t launch_chain_q15pcn_gain(hipStream_t stream, int num_cus, bool cx, PcnGainParams p, PcLaunch *geo);
+hipError_t launch_chain_f32pcn_gain(hipStream_t stream, int num_cus, int time_segments, bool cx, PcfnGainParams p, PcLaunch *geo);
+hipError_t launch_chain_q15pcnd_gain(hipStream_t stream, int num_cus, bool cx, PcndGainParams p, PcLaunch *geo);
+hipError_t launch_chain_f32pcnd_gain(hipStream_t stream, int num_cus, int time_segments, bool cx, PcfndGainParams p, PcLaunch *geo);
 // ---- msdr_chain_meter.hip ----
 // meter_reduce_kernel<T> (msdr_chain_meter.hiph): d_meter[ch] = the sum of part[ch][0 .. nseg) in that order -- the S-meter of a call that the
 // per-receiver kernels above ran in nseg > 1 time segments (their launchers call it; uint64_t sums for Q15, double for F32)

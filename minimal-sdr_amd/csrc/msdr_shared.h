@@ -214,6 +214,18 @@ typedef CxParams<PcfnParams> PcfnCxParams;
 typedef CxParams<PcndParams> PcndCxParams;
 typedef CxParams<PcfndParams> PcfndCxParams;
 
+// the gain twins of those eight (msdr_chain_gain.hiph; msdr_chain_set_gain): the complex-input block of the family -- cx_dir is read by the
+// twins on rows of pairs alone -- and the receivers' records.  A block of its own again.
+constexpr int kGainWords = 32;          // ints per record (MSDR_AGC_STATE_WORDS)
+template <typename P>
+struct GainParams : P {
+    int *agc;                  // [channels][kGainWords]: word 0 is read by every unit, word 6 takes the call's peak (atomicMax)
+};
+typedef GainParams<PcnCxParams> PcnGainParams;
+typedef GainParams<PcfnCxParams> PcfnGainParams;
+typedef GainParams<PcndCxParams> PcndGainParams;
+typedef GainParams<PcfndCxParams> PcfndGainParams;
+
 // chain_f32pcb_kernel (msdr_chain_f32pcb.hiph): a whole block-cadence call of the fp32 chain with per-channel settings in one launch
 struct PcbParams {
     const int16_t *x;          // [channels][n] IF samples

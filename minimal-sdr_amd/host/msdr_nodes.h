@@ -450,6 +450,17 @@ public:
         if (!on) freeCx();
         return 0;
     }
+    // the bank's amp_adc / AGC() pair, once per receiver (msdr_chain_set_gain ...; Minimal-SDR.ino:385, 445-515): while on, every receiver's pair
+    // behind its channel filter is amplified on the FIR accumulators before the demodulator sees it, and every tick ends with one AGC() step of
+    // the receivers whose AGC is on -- the reference's cadence.  After setNco() only.  setGain(true) alone changes nothing (gain 1.0, AGC off).
+    int setGain(bool on) { return chain ? msdr_chain_set_gain(chain, on ? 1 : 0) : MSDR_STATUS_ARGUMENT_ERROR; }
+    // amp_adc.gain(n) of receiver rx: AGC_val = n and its multiplier from the next tick on
+    int gain(uint32_t rx, float n) { return chain ? msdr_chain_set_gain_channels(chain, rx, 1, &n) : MSDR_STATUS_ARGUMENT_ERROR; }
+    // AGC_on per receiver (host array of channels() values of 0 / 1; nullptr: agc_on_all for every receiver)
+    int setAgc(const int32_t *agc_on, int32_t agc_on_all = 0) { return chain ? msdr_chain_set_agc(chain, agc_on, agc_on_all) : MSDR_STATUS_ARGUMENT_ERROR; }
+    // receiver rx's record behind the last tick (msdr_chain_get_agc: multiplier, agc_idx, AGC_val bits, absmax, steps, 0, 0, agc_buffer[25]);
+    // waits for the tick's kernels
+    int readAgc(uint32_t rx, int32_t state[MSDR_AGC_STATE_WORDS]) { return chain ? msdr_chain_get_agc(chain, rx, state) : MSDR_STATUS_ARGUMENT_ERROR; }
     virtual void update(void)
     {
         audio_block_t *in = receiveReadOnly(0);

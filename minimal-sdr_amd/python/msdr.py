@@ -37,6 +37,8 @@ FLAVOUR_DECIMATED = 0x100000
 FLAVOUR_METER = 0x200000
 FLAVOUR_IQ_OUT = 0x400000
 FLAVOUR_COMPLEX_IN = 0x800000
+FLAVOUR_GAIN = 0x1000000
+AGC_STATE_WORDS = 32
 MAX_DECIMATION_Q15, MAX_DECIMATION_F32 = 60, 59
 FE_DCBLOCK, FE_AMP, FE_AGC, FE_ALL = 1, 2, 4, 7
 
@@ -123,6 +125,11 @@ def load_library(path=None):
                        ("msdr_chain_get_iq_out", [_p, _p, _p]),
                        ("msdr_chain_set_complex_input", [_p, C.c_int, C.c_int]),
                        ("msdr_chain_get_complex_input", [_p, _p, _p]),
+                       ("msdr_chain_set_gain", [_p, C.c_int]),
+                       ("msdr_chain_get_gain", [_p, _p]),
+                       ("msdr_chain_set_gain_channels", [_p, C.c_uint32, C.c_uint32, _p]),
+                       ("msdr_chain_set_agc", [_p, _p, C.c_int32]),
+                       ("msdr_chain_get_agc", [_p, C.c_uint32, _p]),
                        ("msdr_nco_step", [C.c_double, C.c_double]),
                        ("msdr_nco_table", [_p]),
                        ("msdr_nco_q15", [_p, C.c_size_t, _p, _p]),
@@ -979,6 +986,41 @@ class Chain(_Instance):
         on, d = C.c_int(0), C.c_int(0)
         _ck(self.ctx.lib.msdr_chain_get_complex_input(self.h, C.byref(on), C.byref(d)))
         return bool(on.value), d.value
+
+    def set_gain(self, on):
+        """Per-receiver gain: while on, the pair behind every receiver's channel filter is multiplied by that receiver's gain on the FIR
+        accumulators (Q15: ssat16((acc * multiplier) >> 31); F32: acc * gain) before demodulator, PLL hand-over and I/Q output see it -- the
+        meter keeps the ungained pair -- and AGC() steps once behind every process().  On alone changes no output bit (gain 1.0, AGC off).
+        Chains with set_nco_channels only (msdr_chain_set_gain)."""
+        _ck(self.ctx.lib.msdr_chain_set_gain(self.h, C.c_int(1 if on else 0)))
+
+    def gain(self):
+        """whether gain is on (msdr_chain_get_gain)"""
+        on = C.c_int(0)
+        _ck(self.ctx.lib.msdr_chain_get_gain(self.h, C.byref(on)))
+        return bool(on.value)
+
+    def set_gain_channels(self, first_channel, gains):
+        """receiver first_channel + i gets AGC_val = gains[i] (float32 [count]) and its multiplier from the next process() on: amp_adc.gain()
+        of ONE receiver.  The AGC's ring is untouched (msdr_chain_set_gain_channels)."""
+        g = np.ascontiguousarray(gains, np.float32).reshape(-1)
+        _ck(self.ctx.lib.msdr_chain_set_gain_channels(self.h, C.c_uint32(first_channel), C.c_uint32(g.size), _hp(g) if g.size else None))
+
+    def set_agc(self, agc_on=None, agc_on_all=0):
+        """which receivers AGC() steps behind every process(): agc_on int32 [channels] of 0 (held) / 1 (stepped), or None: agc_on_all for all
+        (msdr_chain_set_agc)"""
+        a = np.ascontiguousarray(agc_on, np.int32) if agc_on is not None else None
+        if a is not None and a.size != self.channels:
+            raise ValueError("set_agc: %d values for %d channels" % (a.size, self.channels))
+        _ck(self.ctx.lib.msdr_chain_set_agc(self.h, _hp(a), C.c_int32(agc_on_all)))
+
+    def agc_state(self, channel):
+        """a receiver's gain record behind every call so far (synchronises; msdr_chain_get_agc): multiplier (F32: the bits of the clamped
+        gain), agc_idx, AGC_val, absmax of the last call, steps taken, agc_buffer[25], and the raw words"""
+        w = np.zeros(AGC_STATE_WORDS, np.int32)
+        _ck(self.ctx.lib.msdr_chain_get_agc(self.h, C.c_uint32(channel), _hp(w)))
+        return {"multiplier": int(w[0]), "agc_idx": int(w[1]), "AGC_val": float(w[2:3].view(np.float32)[0]), "absmax": int(w[3]),
+                "steps": int(w[4]), "agc_buffer": w[7:32].copy(), "words": w}
 
     def set_block_kernel(self, on):
         """F32: a block-cadence call of a chain in per-channel mode as ONE launch (chain_f32pcb_kernel: demodulator, CMSIS-order cascade, int16
