@@ -660,7 +660,8 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   fp32 chains whose PLL / LMS channels run through the auxiliary chain are out of scope (it gathers its rows from d_if by channel and is
  *   built from the shared tables): the call is refused (ARGUMENT_ERROR, nothing changed) on an fp32 chain created with
  *   MSDR_CHAIN_SYNCAM_PLL or with any LMS channel on, and while a map is in force msdr_chain_set_anr with any channel on is refused on an
- *   fp32 chain.  Q15 chains have no such limit: their PLL / LMS / node kernels work on the demodulator's output.
+ *   fp32 chain, all three unless msdr_chain_set_bank_post is on.  Q15 chains have no such limit: their PLL / LMS / node kernels work on
+ *   the demodulator's output.
  *   Graphs: a msdr_chain_graph made before a msdr_chain_set_input_rows call is refused at launch after it -- after ANY later call, the return
  *   to the identity included.  One made while a map is in force is accepted under the conditions per-channel chains have already (Q15: those
  *   of per-channel taps / oscillator tables; F32: only with msdr_chain_set_block_kernel on), its d_if[k] are [n_inputs][n_samples], and it
@@ -687,11 +688,11 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   (a cleared history needs no generation of the old tables); otherwise MSDR_STATUS_ARGUMENT_ERROR, nothing changed.
  *   Refused (ARGUMENT_ERROR, nothing changed): a NULL chain, a NULL step, a range past `channels`, a chain created with MSDR_MIXER_FS4, a
  *   chain holding per-channel oscillator tables (msdr_chain_set_osc_channels), an fp32 chain created with MSDR_CHAIN_SYNCAM_PLL or with an
- *   LMS channel on, and a filter too long for 64 KB of LDS beside the 4 KB sine table (Q15: more than 4 776 taps, no chain; F32: more than
+ *   LMS channel on (both unless msdr_chain_set_bank_post is on), and a filter too long for 64 KB of LDS beside the 4 KB sine table (Q15: more than 4 776 taps, no chain; F32: more than
  *   3 584).  count == 0 does nothing.
  *   On a chain in this mode msdr_chain_set_osc and msdr_chain_set_osc_channels are refused; msdr_chain_graph_create is refused (the time
  *   of a call's first sample is a launch operand: a replay would repeat one phase) and a graph made earlier is refused at launch;
- *   msdr_chain_set_anr with any channel on is refused on fp32 chains; msdr_chain_set_block_kernel[_q15] is accepted and such calls run
+ *   msdr_chain_set_anr with any channel on is refused on fp32 chains unless msdr_chain_set_bank_post is on; msdr_chain_set_block_kernel[_q15] is accepted and such calls run
  *   the unfused launches.  The bank survives msdr_chain_set_taps[_channels][_f32], set_mode, the node and cascade setters,
  *   msdr_chain_set_input_rows (in either order) and, on Q15 chains, set_anr.  msdr_chain_init_fir keeps phases and steps;
  *   msdr_chain_reset sets the chain's time and every phase to 0, keeps the steps and drops the pending generations.
@@ -715,7 +716,8 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   (msdr_biquad_design takes the sample rate).
  *   Scope: chains in phase-accumulator mode only (msdr_chain_set_nco_channels has been called), Q15 and F32; every other chain is
  *   MSDR_STATUS_ARGUMENT_ERROR, nothing changed.  Also refused: a Q15 chain created with MSDR_CHAIN_SYNCAM_PLL, a Q15 chain with an LMS
- *   channel on (and, while D > 1, msdr_chain_set_anr with any channel on); fp32 chains in this mode refuse both already.
+ *   channel on (and, while D > 1, msdr_chain_set_anr with any channel on), all three unless msdr_chain_set_bank_post is on; fp32 chains in this mode
+ *   refuse both already.
  *   Values: 1 .. MSDR_MAX_DECIMATION_Q15 (60) / MSDR_MAX_DECIMATION_F32 (59).  The kernel's window of one wave with one channel --
  *   128 D + np mixed samples per stream (np = num_taps rounded up to 8 (Q15) / 4 (F32)), twice for odd D on Q15 chains -- must fit 64 KB of
  *   LDS beside the tap rows and the 4 KB sine table:
@@ -744,7 +746,7 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   misaligned pointer or a NULL chain is MSDR_STATUS_ARGUMENT_ERROR, nothing changed.
  *   The first non-NULL call enters the per-channel kernel family exactly as msdr_chain_set_input_rows does (tap table filled from the
  *   shared tap sets, fp32 cascade behind the kernel in CMSIS order), with that call's refusals: an fp32 chain created with
- *   MSDR_CHAIN_SYNCAM_PLL or with an LMS channel on (and, while a meter is set, msdr_chain_set_anr with a channel on), a filter beyond
+ *   MSDR_CHAIN_SYNCAM_PLL or with an LMS channel on (and, while a meter is set, msdr_chain_set_anr with a channel on; all three unless msdr_chain_set_bank_post is on), a filter beyond
  *   the per-channel kernel's tap limit.  NULL leaves the chain in that family with the meter off.  The pointer survives everything the
  *   input map survives: msdr_chain_reset and init_fir, every tap / oscillator / NCO / node / cascade / mode setter,
  *   msdr_chain_set_input_rows, msdr_chain_set_decimation.
@@ -843,6 +845,44 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   Q15 chains with MSDR_CHAIN_SYNCAM_PLL at D = 1 and msdr_chain_set_anr.
  *   Reporting: msdr_chain_get_info().kernel keeps its names (the gain twins, chain_q15pcn_gain_kernel ..., run under them); on fp32 chains
  *   flavour carries MSDR_FLAVOUR_GAIN exactly while gain is on.  Graphs stay refused, as on every chain in this mode.
+ * msdr_chain_set_bank_post: synchronous AM and the LMS filter for the bank.  SYNCAM is one of the reference's four modes and the LMS notch its
+ *   only interference filter (Minimal-SDR.ino:631-688, 702-770); on = 1 means: once this chain is in phase-accumulator mode
+ *   (msdr_chain_set_nco_channels), its PLL demodulator and LMS filter run behind the per-receiver kernel on the PAIR HAND-OVER, at fs / D,
+ *   and never through an auxiliary chain.  The hand-over is the pair I_c[m], Q_c[m] of msdr_chain_set_iq_out's definition: a call that
+ *   needs it launches the I/Q twin of the kernel it would have launched, which stores into the caller's d_iq where one is set (no second
+ *   store) and else into a buffer of the chain's own, [channels][n_out rounded up to 8] pairs, grown on demand.  bank_pll_q15_kernel /
+ *   bank_pll_f32_kernel (one lane = one channel) then write the PLL's audio over the rows of the channels whose mode is SYNCAM -- the
+ *   statement sequence of msdr_syncam_q15 / the fp32 chain's PLL, state records shared with them -- and leave every other row alone.
+ *   With gain on the PLL receives the GAINED pair, the rule of the D = 1 hand-over.
+ *   Accepted on Q15 and F32 chains whose mixer is the NCO (not MSDR_MIXER_FS4), only while the FIR history is clear -- the rule of the first
+ *   msdr_chain_set_nco_channels call -- and it holds for the rest of the chain's life: a repeat call with 1 does nothing, 0 after 1 is
+ *   MSDR_STATUS_ARGUMENT_ERROR, nothing changed, and so is a NULL chain.  It changes nothing until the chain is in phase-accumulator mode:
+ *   until then every call behaves as without it, refusals included.  With the switch on:
+ *     F32   msdr_chain_set_nco_channels is accepted on a chain created with MSDR_CHAIN_SYNCAM_PLL and / or with LMS channels on; the
+ *           auxiliary chain and its buffers are dropped, the per-channel PLL and LMS state records are kept.  In the mode, msdr_chain_set_anr
+ *           with channels on, set_mode to and from SYNCAM, set_input_rows, set_meter, set_iq_out (I/Q-only calls included),
+ *           set_complex_input, set_gain* / set_agc, set_decimation, set_biquad_coeffs_channels, set_taps_channels_f32 and
+ *           MSDR_CHAIN_OUT_I16 are accepted and combine in either order, as on Q15 chains.  Order per call: kernel (demodulator + pair
+ *           store) -> PLL on SYNCAM channels -> LMS on its channels -> CMSIS-order cascade (shared or per-channel rows) -> int16 conversion.
+ *     Q15   msdr_chain_set_decimation is accepted on a chain created with MSDR_CHAIN_SYNCAM_PLL and with LMS channels on, and
+ *           msdr_chain_set_anr while D > 1.  Order: kernel -> PLL -> LMS (anr_kernel) -> biquad nodes, all on n / D samples; a chain with
+ *           nodes still needs n / D even.  At D = 1 the pairs are bit for bit what the I / Q hand-over of a chain without the switch
+ *           carries, so no output changes by a bit.
+ *   The PLL pass runs in every audio call of such a chain that has a PLL while a channel is on SYNCAM, at every D; I/Q-only calls leave the
+ *   PLL and LMS states untouched; msdr_chain_reset clears both, msdr_chain_init_fir keeps them.  Graphs stay refused, as on every chain in
+ *   this mode.  Reporting: on fp32 chains flavour carries MSDR_FLAVOUR_BANK_POST exactly when the call ran the bank's PLL or LMS pass.
+ * msdr_chain_get_bank_post: the switch (0 on a chain that never set it).
+ * msdr_chain_get_pll_state: synchronises and returns fil_out, omega2, phzerror of one channel's loop, msdr_syncam_get_state's shape, on Q15
+ *   and F32 chains created with MSDR_CHAIN_SYNCAM_PLL, with or without the switch; a chain without a PLL is MSDR_STATUS_ARGUMENT_ERROR.
+ * msdr_syncam_constants_rate (host only): omega_min, omega_max, g1, g2 as msdr_syncam_constants evaluates them (Minimal-SDR.ino:636-641) with
+ *   SAMPLE_RATE replaced by sample_rate, under the same arithmetic conversions: bit-equal to msdr_syncam_constants at 24000.  With the
+ *   reference's constants a loop that runs at fs / D has its capture range and bandwidth shrunk by D (at D = 8: +-500 Hz, 50 Hz).
+ * msdr_chain_set_pll_rate: the rate the bank's PLL constants are evaluated for; 0 (the default) = the reference's constants, otherwise a
+ *   finite value > 0 (anything else: MSDR_STATUS_ARGUMENT_ERROR, nothing changed).  Accepted only with msdr_chain_set_bank_post on.  The
+ *   constants are an operand of the PLL kernel: stream-ordered, the state is kept, in force from the next call.  Nothing sets it
+ *   automatically: the caller passes fs / D, as the caller designs the biquads for fs / D.  msdr_chain_get_pll_rate: the value in force.
+ * msdr_chain_post_kernel: a static string, the PLL kernel of the last audio call -- "bank_pll_q15_kernel" / "bank_pll_f32_kernel",
+ *   "syncam_pll_kernel" (Q15 without the switch), "post_pll_f32_kernel" (fp32 through the auxiliary chain) -- or "" when none ran.
  * msdr_nco_step (host only): llround(f_hz / fs_hz * 2^32) mod 2^32; a negative frequency wraps (-6000 at 24000: 0xC0000000).
  * msdr_nco_table (host only): T[i] = (int16) lround(32767 sin(2 pi i / 1024)), i = 0 .. 1024, T[1024] = 0.
  * msdr_nco_q15 (host only; what the kernels compute): for each uint32 phase, i = phase >> 22, f = (phase >> 6) & 0xFFFF,
@@ -870,6 +910,13 @@ int msdr_chain_set_gain_channels(msdr_chain *chain, uint32_t first_channel, uint
 int msdr_chain_set_agc(msdr_chain *chain, const int32_t *agc_on, int32_t agc_on_all);   /* msdr_chain_set_anr's argument shape */
 #define MSDR_AGC_STATE_WORDS 32u
 int msdr_chain_get_agc(msdr_chain *chain, uint32_t channel, int32_t state[MSDR_AGC_STATE_WORDS]);
+int msdr_chain_set_bank_post(msdr_chain *chain, int on);                  /* off (default): PLL / LMS as on a chain without it */
+int msdr_chain_get_bank_post(msdr_chain *chain, int *on);
+int msdr_chain_get_pll_state(msdr_chain *chain, uint32_t channel, float state[3]);
+void msdr_syncam_constants_rate(double sample_rate, float c[4]);
+int msdr_chain_set_pll_rate(msdr_chain *chain, double sample_rate);       /* 0 (default): the reference's constants */
+int msdr_chain_get_pll_rate(msdr_chain *chain, double *sample_rate);
+const char *msdr_chain_post_kernel(msdr_chain *chain);
 int msdr_chain_set_taps(msdr_chain *chain, uint32_t tapset, const void *coeffs_i, const void *coeffs_q);
 int msdr_chain_set_taps_channels(msdr_chain *chain, uint32_t first_channel, uint32_t count,
                                  const q15_t *coeffs_i, const q15_t *coeffs_q);
@@ -954,6 +1001,8 @@ enum { MSDR_FLAVOUR_COMPLEX_IN = 0x800000u };
 /* And another: the demodulator kernel multiplied the pair by every receiver's gain -- the gain twin of a phase-accumulator kernel,
  * msdr_chain_set_gain on (always beside MSDR_FLAVOUR_NCO_PC). */
 enum { MSDR_FLAVOUR_GAIN = 0x1000000u };
+/* the call ran the bank's PLL or LMS pass behind the per-receiver kernel (msdr_chain_set_bank_post; always beside MSDR_FLAVOUR_NCO_PC). */
+enum { MSDR_FLAVOUR_BANK_POST = 0x2000000u };
 int msdr_chain_get_info(msdr_chain *chain, msdr_chain_info *info);
 /* The wave-stream kernels read the run geometry of a tap table (which chunks of the window each accumulator walks, which runs merge their first
  * and last step) from the table's header -- or, for the geometries the library instantiates, have it as compile-time constants: the same

@@ -2081,6 +2081,22 @@ extern "C" void msdr_syncam_constants(float c[4])
     c[2] = g1;
     c[3] = (float)(-(double)g1 + 2.0 * (1 - std::exp((double)e_arg) * (double)cosf(c_arg)));
 }
+// The same initialisers with SAMPLE_RATE replaced: the loop of a bank that runs its PLL at fs / D (msdr_chain_set_pll_rate).  The int in the
+// reference's expressions converts to double where it meets a double and to float where it meets a float; so does sample_rate here, which
+// makes the two functions bit-equal at 24000.
+extern "C" void msdr_syncam_constants_rate(double sample_rate, float c[4])
+{
+    if (!c) return;
+    const double PI_ = 3.1415926535897932384626433832795;
+    const float omegaN = 400.0, zeta = 0.45;
+    c[0] = (float)(2.0 * PI_ * -4000.0 / sample_rate);
+    c[1] = (float)(2.0 * PI_ * 4000.0 / sample_rate);
+    const float g1 = (float)(1.0 - std::exp(-2.0 * (double)omegaN * (double)zeta / sample_rate));
+    const float e_arg = -omegaN * zeta / (float)sample_rate;
+    const float c_arg = omegaN / (float)sample_rate * sqrtf((float)(1.0 - (double)(zeta * zeta)));
+    c[2] = g1;
+    c[3] = (float)(-(double)g1 + 2.0 * (1 - std::exp((double)e_arg) * (double)cosf(c_arg)));
+}
 extern "C" int msdr_syncam_create(msdr_ctx *ctx, uint32_t channels, msdr_syncam **out)
 {
     if (!out) return fail(MSDR_STATUS_ARGUMENT_ERROR, "out is null");
@@ -2542,6 +2558,19 @@ struct msdr_chain {
     // step kernel rewrites it on the stream).
     bool gain_on = false;
     int *d_agc = nullptr;
+    // msdr_chain_set_bank_post: once nco_active, the PLL demodulator and the LMS filter run behind the per-receiver kernel on the pairs its I/Q
+    // twin stored (msdr_bank_post.hiph), at fs / D, and never through the auxiliary chain.  The hand-over is the caller's d_iq where one is
+    // set, else d_bank_iq, [channels][call_iq_pitch] pairs grown on demand; call_iq is set by the msdr_chain_process call that needs it and
+    // read by pc_params_iq.  F32: d_bank_ident / d_bank_anr are post_anr_f32_kernel's index tables for "every channel, in place".
+    bool bank_post = false;
+    double pll_rate = 0.0;                // msdr_chain_set_pll_rate: 0 = the reference's constants
+    void *d_bank_iq = nullptr;
+    size_t bank_iq_bytes = 0;
+    void *call_iq = nullptr;
+    uint64_t call_iq_pitch = 0;
+    int *d_bank_ident = nullptr, *d_bank_anr = nullptr;
+    uint64_t bank_anr_gen = 0;            // the anr_gen d_bank_anr was made for
+    const char *post_kernel = "";         // msdr_chain_post_kernel: the PLL kernel of the last call
     msdr_chain_info info;
     // optional per-launch timing of the main kernel
     bool timing;
@@ -2557,6 +2586,8 @@ static bool chain_nodes_per_channel(const msdr_chain *c)
 {
     return (c->nodes[0] && c->nodes[0]->per_channel) || (c->nodes[1] && c->nodes[1]->per_channel);
 }
+// msdr_chain_set_bank_post in force: the switch is on and the chain is in phase-accumulator mode
+static bool chain_bank(const msdr_chain *c) { return c->bank_post && c->nco_active; }
 
 // ---- per-channel FIR coefficients: the host's copy of the table and its way to the device ----
 static void chain_pc_row_from(msdr_chain *c, uint32_t ch, const int16_t *ci, const int16_t *cq)
@@ -2636,6 +2667,7 @@ static void chain_free(msdr_chain *c)
     if (!c) return;
     chain_post_free(c);
     hipFree(c->d_post_pll_state); hipFree(c->d_post_anr_state); hipFree(c->d_aux_x); hipFree(c->d_aux_y); hipFree(c->d_post_scratch);
+    hipFree(c->d_bank_iq); hipFree(c->d_bank_ident); hipFree(c->d_bank_anr);
     hipFree(c->d_taps); hipFree(c->d_osc); hipFree(c->d_mode); hipFree(c->d_tapset);
     hipFree(c->d_hist[0]); hipFree(c->d_hist[1]); hipFree(c->d_bq); hipFree(c->d_bq_state);
     hipFree(c->d_ftaps); hipFree(c->d_fset); hipFree(c->d_bq_fold);
@@ -3507,6 +3539,18 @@ static bool chain_post_wanted(const msdr_chain *c, uint32_t ch, bool *pll, int *
     return *pll || *anr > 0;
 }
 
+// the per-channel PLL and LMS state records of an fp32 chain, made once and kept (the auxiliary chain's passes and msdr_chain_set_bank_post's share them)
+static int chain_post_states(msdr_chain *c)
+{
+    if (!c->d_post_pll_state) if (int rc = dzalloc(c->ctx, (size_t)c->channels * 4, &c->d_post_pll_state)) return rc;
+    if (!c->d_post_anr_state) {
+        std::vector<float> h((size_t)c->channels * kAnrStateFloats, 0.0f);
+        for (uint32_t ch = 0; ch < c->channels; ch++) { h[(size_t)ch * kAnrStateFloats] = 120.0f; h[(size_t)ch * kAnrStateFloats + 1] = 0.001f; }   // .ino:715,:718
+        if (int rc = upload(c->ctx, h, &c->d_post_anr_state)) return rc;
+    }
+    return 0;
+}
+
 // (re)builds the auxiliary chain and the index tables for the current modes / LMS switches; FIR history and oscillator position are
 // taken over from the main chain, PLL and LMS state are per CHANNEL and persist, the post cascade restarts
 static int chain_post_build_steps(msdr_chain *c)
@@ -3579,12 +3623,7 @@ static int chain_post_build_steps(msdr_chain *c)
     if (int rc = upload(c->ctx, post_pll, &c->d_post_pll)) return rc;
     if (int rc = upload(c->ctx, post_anr, &c->d_post_anr)) return rc;
     if (int rc = upload(c->ctx, virt_row, &c->d_virt_row)) return rc;
-    if (!c->d_post_pll_state) if (int rc = dzalloc(c->ctx, (size_t)c->channels * 4, &c->d_post_pll_state)) return rc;
-    if (!c->d_post_anr_state) {
-        std::vector<float> h((size_t)c->channels * kAnrStateFloats, 0.0f);
-        for (uint32_t ch = 0; ch < c->channels; ch++) { h[(size_t)ch * kAnrStateFloats] = 120.0f; h[(size_t)ch * kAnrStateFloats + 1] = 0.001f; }   // .ino:715,:718
-        if (int rc = upload(c->ctx, h, &c->d_post_anr_state)) return rc;
-    }
+    if (int rc = chain_post_states(c)) return rc;
     // the auxiliary chain continues the main chain's stream: same raw IF history (the newest samples both keep), same table position
     hipLaunchKernelGGL(post_hist_copy_kernel, dim3(4, (unsigned)virt_row.size()), dim3(256), 0, c->ctx->stream, (const int16_t *)c->d_hist[c->cur],
                        c->aux->d_hist[c->aux->cur], (const int *)c->d_virt_row, (int)c->hist_len, (int)c->aux->hist_len);
@@ -3649,6 +3688,60 @@ static int chain_post_run(msdr_chain *c, const int16_t *d_if, float *d_audio, ui
     hipLaunchKernelGGL(post_scatter_rows_kernel, dim3(gx, c->npost), dim3(256), 0, c->ctx->stream, (const float *)c->d_post_scratch, d_audio,
                        (const int *)c->d_post_ch, (long long)n);
     return launch_check("post_scatter_rows_kernel");
+}
+
+// ---- msdr_chain_set_bank_post: PLL and LMS behind the per-receiver kernel, on the pair hand-over (msdr_bank_post.hiph) -------------------------
+// this call's hand-over: the caller's msdr_chain_set_iq_out buffer, else the chain's own, pitch = n_out rounded up to 8 pairs, grown on demand
+static int chain_bank_pairs(msdr_chain *c, uint64_t n_out)
+{
+    c->call_iq = nullptr; c->call_iq_pitch = 0;
+    if (c->d_iq) return 0;
+    const uint64_t pitch = (n_out + 7) & ~(uint64_t)7;
+    const size_t bytes = (size_t)c->channels * pitch * (c->arith == MSDR_ARITH_F32 ? 8 : 4);
+    if (bytes > c->bank_iq_bytes) {
+        HIP_TRY(hipStreamSynchronize(c->ctx->stream));          // (a kernel in flight reads the old one)
+        void *buf = nullptr;
+        if (hipMalloc(&buf, bytes) != hipSuccess) { (void)hipGetLastError(); return fail(MSDR_STATUS_OUT_OF_MEMORY, "bank post: device allocation of %zu bytes for the pair hand-over failed; nothing enqueued", bytes); }
+        hipFree(c->d_bank_iq);
+        c->d_bank_iq = buf; c->bank_iq_bytes = bytes;
+    }
+    c->call_iq = c->d_bank_iq; c->call_iq_pitch = pitch;
+    return 0;
+}
+// behind the demodulator kernel of an audio call: the PLL on the SYNCAM channels' rows, then (F32; a Q15 chain keeps anr_kernel) the LMS filter
+// in place on its channels' rows -- post_anr_f32_kernel with the identity as its channel table
+static int chain_bank_run(msdr_chain *c, bool pll, bool anr, void *audio, uint64_t n_out)
+{
+    const bool f32 = c->arith == MSDR_ARITH_F32;
+    if (pll) {
+        float kc[4];
+        if (c->pll_rate > 0.0) msdr_syncam_constants_rate(c->pll_rate, kc);
+        else msdr_syncam_constants(kc);
+        BankPllParams q;
+        q.pairs = c->d_iq ? c->d_iq : c->call_iq; q.pair_pitch = (long long)(c->d_iq ? c->iq_pitch : c->call_iq_pitch);
+        q.audio = audio; q.n = (long long)n_out;
+        q.state = f32 ? c->d_post_pll_state : c->pll->d_state; q.chan_mode = c->d_mode; q.channels = (int)c->channels;
+        q.omega_min = kc[0]; q.omega_max = kc[1]; q.g1 = kc[2]; q.g2 = kc[3];
+        if (launch_bank_pll(c->ctx->stream, f32, q) != hipSuccess) return fail(MSDR_STATUS_HIP_ERROR, "bank_pll kernel launch failed");
+        c->post_kernel = f32 ? "bank_pll_f32_kernel" : "bank_pll_q15_kernel";
+    }
+    if (anr && f32) {
+        if (!c->d_bank_ident) {
+            std::vector<int> ident(c->channels);
+            for (uint32_t ch = 0; ch < c->channels; ch++) ident[ch] = (int)ch;
+            if (int rc = upload(c->ctx, ident, &c->d_bank_ident)) return rc;
+        }
+        if (!c->d_bank_anr || c->bank_anr_gen != c->anr_gen) {
+            HIP_TRY(hipStreamSynchronize(c->ctx->stream));          // (a kernel in flight reads the old table)
+            hipFree(c->d_bank_anr); c->d_bank_anr = nullptr;
+            if (int rc = upload(c->ctx, c->h_anr, &c->d_bank_anr)) return rc;
+            c->bank_anr_gen = c->anr_gen;
+        }
+        hipLaunchKernelGGL(post_anr_f32_kernel, dim3((c->channels + 63) / 64), dim3(64), 0, c->ctx->stream, (float *)audio, c->d_post_anr_state,
+                           (const int *)c->d_bank_ident, (const int *)c->d_bank_anr, (int)c->channels, (long long)n_out);
+        if (int rc = launch_check("post_anr_f32_kernel")) return rc;
+    }
+    return 0;
 }
 
 // ---- AGC(), one lane per receiver (Minimal-SDR.ino:479-513; the float operations are msdr_frontend.hiph's, which match orc_agc_block) -------------------
@@ -4061,7 +4154,7 @@ static int chain_prepare(msdr_chain *c, ChainDecision &d, const ChainTiles &t, c
     p.chan_mode = c->d_mode; p.chan_tapset = c->d_tapset; p.mixer = c->mixer; p.osc = c->d_osc; p.osc_len = (int)c->osc_len;
     p.phase0 = (int)c->phase; p.in_scale = c->in_scale; p.sqrt_kind = c->sqrt_kind;
     p.nstages = (int)c->nstages; p.bq = c->d_bq; p.bq_state = c->d_bq_state;
-    if (d.pll_active) {
+    if (d.pll_active && !chain_bank(c)) {          // (msdr_chain_set_bank_post: the pairs are the hand-over, msdr_chain_process sets it up)
         if (int rc = grow_device(c->ctx, &c->d_pll_q, &c->pll_q_cap, (size_t)c->channels * n_samples)) return rc;
         p.syncam_q = c->d_pll_q;
     }
@@ -4162,6 +4255,8 @@ template <typename Q>
 static void pc_params_iq(Q &q, const msdr_chain *c)
 {
     q.iq = (decltype(q.iq))c->d_iq; q.iq_pitch = (long long)c->iq_pitch;
+    // msdr_chain_set_bank_post: a call that needs the pairs for the PLL and has no buffer of the caller's stores them to the chain's own
+    if (!c->d_iq && c->call_iq) { q.iq = (decltype(q.iq))c->call_iq; q.iq_pitch = (long long)c->call_iq_pitch; }
 }
 static void pc_geometry_of(const PcLaunch &geo, ChainLaunch &r)
 {
@@ -4535,6 +4630,14 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     if (int rc = chain_prepare(c, d, t, d_if, d_audio, n_samples, p, r)) return rc;
     if (!audio) { p.out = nullptr; p.syncam_q = nullptr; }          // an I/Q-only call: the IQ instantiations skip demodulator and audio store
     void *const fout = p.out;                                    // where the fp32 passes of this call read and write the audio
+    // msdr_chain_set_bank_post: the PLL (chains that have one, while a channel is on SYNCAM) and the fp32 LMS filter run behind the kernel on
+    // the pairs its I/Q twin stores; an I/Q-only call has neither
+    const bool bank = chain_bank(c) && audio;
+    const bool bank_pll = bank && (f32 ? c->f32_pll && chain_summary(c).any_syncam : d.pll_active);
+    const bool bank_anr = bank && f32 && chain_summary(c).any_anr;
+    c->call_iq = nullptr; c->call_iq_pitch = 0;
+    if (bank_pll) if (int rc = chain_bank_pairs(c, n_out)) return rc;
+    if (bank && f32) if (int rc = chain_post_states(c)) return rc;
     if (c->dry_run) {            // msdr_chain_graph_create: everything a block-cadence call needs from the host is in place now; make no launch
         const char *why = chain_not_capturable(c, d, n_samples);
         return why ? fail(MSDR_STATUS_ARGUMENT_ERROR, "%s", why) : 0;
@@ -4565,11 +4668,18 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     if (e0) { HIP_TRY(hipEventRecord(e1, c->ctx->stream)); c->events.emplace_back(e0, e1); }
 
     // ---- the passes behind it: n_out samples per channel (n_samples / decimation; the two are equal without msdr_chain_set_decimation)
+    if (audio) c->post_kernel = "";
+    if (bank_pll || bank_anr) {          // msdr_chain_set_bank_post: PLL, then LMS, in front of cascade and nodes (Q15: the LMS filter is anr_kernel below)
+        if (int rc2 = chain_bank_run(c, bank_pll, bank_anr, f32 ? fout : d_audio, n_out)) return rc2;
+        if (f32) r.flavour |= MSDR_FLAVOUR_BANK_POST;
+    }
     if (c->seq_bq && d.path != kPathF32Pcb && audio) // F32, ill-conditioned cascade: arm_biquad_cascade_df1_f32 in CMSIS order, in place on the audio (chain_f32pcb_kernel ran it itself)
         { if (int rc2 = msdr_biquad_df1_f32_process(c->seq_bq, (const float *)fout, (float *)fout, (uint32_t)n_out)) return rc2; r.flavour |= MSDR_FLAVOUR_SEQ_CASCADE | (c->seq_bq->per_channel ? (uint32_t)MSDR_FLAVOUR_CASCADE_PC : 0u); }
 
-    if (d.pll_active && audio)          // SYNCAM channels: I (in d_audio) and Q (scratch) -> PLL demodulator -> audio, before the biquad nodes
+    if (d.pll_active && audio && !bank_pll) {          // SYNCAM channels: I (in d_audio) and Q (scratch) -> PLL demodulator -> audio, before the biquad nodes
         if (int rc2 = msdr_syncam_q15(c->pll, c->d_mode, (const q15_t *)d_audio, c->d_pll_q, (q15_t *)d_audio, (uint32_t)n_out)) return rc2;
+        c->post_kernel = "syncam_pll_kernel";
+    }
 
     if (d.anr_active && audio)          // LMS notch / noise reduction (.ino:702-770), then the biquad nodes
         if (int rc2 = msdr_anr_q15(c->anr, c->d_anr_on, c->anr_all, (q15_t *)d_audio, (uint32_t)n_out)) return rc2;
@@ -4586,7 +4696,11 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     // rows f2 / f3 inside the fp32 chain: PLL / LMS channels are redone behind the main kernel (before the history moves on: a rebuilt
     // auxiliary chain takes over the history and table position this call started from)
     // (no chain with a decimator has such channels: msdr_chain_set_nco_channels and msdr_chain_set_anr refuse them)
-    if (f32 && audio) if (int rc2 = chain_post_run(c, d_if, (float *)fout, n_samples)) return rc2;
+    // (msdr_chain_set_bank_post: such a chain ran both in front of its cascade, above, and has no auxiliary chain)
+    if (f32 && audio && !chain_bank(c)) {
+        if (int rc2 = chain_post_run(c, d_if, (float *)fout, n_samples)) return rc2;
+        if (c->f32_pll && c->npost > 0) c->post_kernel = "post_pll_f32_kernel";
+    }
     if (d.i16 == kI16ViaScratch && audio) {
         const long long total = (long long)c->channels * (long long)n_out;
         hipLaunchKernelGGL(f32_to_q15_kernel, dim3(grid_1d((total + 3) / 4)), dim3(256), 0, c->ctx->stream, (const float *)fout, (short *)d_audio, total);
@@ -5042,6 +5156,9 @@ static int chain_rebuild(msdr_chain *c, const ChainCfgStore &edited, void **stea
     n->d_iq = c->d_iq; n->iq_pitch = c->iq_pitch;          // (and so does msdr_chain_set_iq_out)
     n->cx_on = c->cx_on; n->cx_dir = c->cx_dir;          // (and msdr_chain_set_complex_input: the history above went over as pairs)
     n->gain_on = c->gain_on; std::swap(n->d_agc, c->d_agc);          // (and msdr_chain_set_gain with every receiver's record)
+    n->bank_post = c->bank_post; n->pll_rate = c->pll_rate; n->post_kernel = c->post_kernel;          // (and msdr_chain_set_bank_post with its buffers)
+    std::swap(n->d_bank_iq, c->d_bank_iq); n->bank_iq_bytes = c->bank_iq_bytes;
+    std::swap(n->d_bank_ident, c->d_bank_ident); std::swap(n->d_bank_anr, c->d_bank_anr); n->bank_anr_gen = c->bank_anr_gen;
     std::swap(*c, *n);
     if (steal_osc) { *steal_osc = n->d_osc; n->d_osc = nullptr; }
     chain_free(n);
@@ -5260,8 +5377,8 @@ extern "C" int msdr_chain_set_input_rows(msdr_chain *c, uint32_t n_inputs, const
     const bool f32 = c->arith == MSDR_ARITH_F32;
     if (f32) {
         // PLL / LMS channels of an fp32 chain run through an auxiliary chain that gathers its rows from d_if by channel (chain_post_run)
-        if (c->f32_pll) return fail(MSDR_STATUS_ARGUMENT_ERROR, "input rows: not on an fp32 chain created with MSDR_CHAIN_SYNCAM_PLL (its PLL channels run through an auxiliary chain that gathers d_if by channel); nothing changed");
-        for (int v : c->h_anr) if (v > 0) return fail(MSDR_STATUS_ARGUMENT_ERROR, "input rows: not while an LMS channel of an fp32 chain is on (such channels run through an auxiliary chain that gathers d_if by channel); nothing changed");
+        if (!chain_bank(c) && c->f32_pll) return fail(MSDR_STATUS_ARGUMENT_ERROR, "input rows: not on an fp32 chain created with MSDR_CHAIN_SYNCAM_PLL (its PLL channels run through an auxiliary chain that gathers d_if by channel); nothing changed");
+        for (int v : c->h_anr) if (!chain_bank(c) && v > 0) return fail(MSDR_STATUS_ARGUMENT_ERROR, "input rows: not while an LMS channel of an fp32 chain is on (such channels run through an auxiliary chain that gathers d_if by channel); nothing changed");
         if (!c->pc_active && f32pc_np((int)c->ntaps) > f32pc_max_taps(false))
             return fail(MSDR_STATUS_ARGUMENT_ERROR, "input rows: the per-channel kernel holds filters of up to %d taps (this chain has %u); nothing changed", f32pc_max_taps(false), c->ntaps);
     }
@@ -5293,8 +5410,8 @@ extern "C" int msdr_chain_set_meter(msdr_chain *c, void *d_meter)
         if (f32) {
             // PLL / LMS channels of an fp32 chain are redone behind the main kernel through an auxiliary chain (chain_post_run): what the
             // per-receiver kernel measured would not be what the audio came from
-            if (c->f32_pll) return fail(MSDR_STATUS_ARGUMENT_ERROR, "meter: not on an fp32 chain created with MSDR_CHAIN_SYNCAM_PLL (its PLL channels run through an auxiliary chain); nothing changed");
-            for (int v : c->h_anr) if (v > 0) return fail(MSDR_STATUS_ARGUMENT_ERROR, "meter: not while an LMS channel of an fp32 chain is on (such channels run through an auxiliary chain); nothing changed");
+            if (!chain_bank(c) && c->f32_pll) return fail(MSDR_STATUS_ARGUMENT_ERROR, "meter: not on an fp32 chain created with MSDR_CHAIN_SYNCAM_PLL (its PLL channels run through an auxiliary chain); nothing changed");
+            for (int v : c->h_anr) if (!chain_bank(c) && v > 0) return fail(MSDR_STATUS_ARGUMENT_ERROR, "meter: not while an LMS channel of an fp32 chain is on (such channels run through an auxiliary chain); nothing changed");
             if (!c->pc_active && f32pc_np((int)c->ntaps) > f32pc_max_taps(false))
                 return fail(MSDR_STATUS_ARGUMENT_ERROR, "meter: the per-channel kernel holds filters of up to %d taps (this chain has %u); nothing changed", f32pc_max_taps(false), c->ntaps);
         }
@@ -5468,7 +5585,7 @@ extern "C" int msdr_chain_set_nco_channels(msdr_chain *c, uint32_t first_channel
     if (first_channel >= c->channels || count > c->channels - first_channel)
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "channels %u .. %llu of %u", first_channel, (unsigned long long)first_channel + count - 1, c->channels);
     const bool f32 = c->arith == MSDR_ARITH_F32;
-    if (f32) {          // PLL / LMS channels of an fp32 chain run through an auxiliary chain that is built from the shared tables
+    if (f32 && !c->bank_post) {          // PLL / LMS channels of an fp32 chain run through an auxiliary chain that is built from the shared tables (msdr_chain_set_bank_post: behind the kernel)
         if (c->f32_pll) return fail(MSDR_STATUS_ARGUMENT_ERROR, "phase-accumulator oscillator: not on an fp32 chain created with MSDR_CHAIN_SYNCAM_PLL (its PLL channels run through an auxiliary chain with the shared tables); nothing changed");
         for (int v : c->h_anr) if (v > 0) return fail(MSDR_STATUS_ARGUMENT_ERROR, "phase-accumulator oscillator: not while an LMS channel of an fp32 chain is on (such channels run through an auxiliary chain with the shared tables); nothing changed");
     }
@@ -5510,6 +5627,11 @@ extern "C" int msdr_chain_set_nco_channels(msdr_chain *c, uint32_t first_channel
         c->d_nco_bank = bank; c->d_nco_tab = tab;
         c->h_nco_base.assign(c->channels, 0u); c->h_nco_step.assign(c->channels, 0u);
         c->nco_active = true;
+        if (f32 && c->bank_post) {          // msdr_chain_set_bank_post: the auxiliary chain and its buffers go, the per-channel PLL and LMS state records stay
+            chain_post_free(c); c->h_post_ch.clear(); c->post_mode_gen = 0; c->post_anr_gen = 0;
+            hipFree(c->d_aux_x); hipFree(c->d_aux_y); hipFree(c->d_post_scratch);
+            c->d_aux_x = nullptr; c->d_aux_y = nullptr; c->d_post_scratch = nullptr; c->post_cap_virt = 0; c->post_cap_post = 0;
+        }
     }
     for (uint32_t k = 0; k < count; k++) {
         const uint32_t ch = first_channel + k;
@@ -5546,13 +5668,64 @@ extern "C" int msdr_chain_set_decimation(msdr_chain *c, uint32_t D)
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "decimation %u: 1 .. %d (the window of one wave with one channel must fit 64 KB of LDS beside the sine table); nothing changed", D, chain_dec_max(f32));
     if (D > 1 && !chain_dec_fits(f32, c->pc_np, (int)D))
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "decimation %u: beside its window the kernel holds filters of up to %d taps (this chain has %u); nothing changed", D, chain_dec_max_taps(f32, (int)D), c->ntaps);
-    if (!f32 && D > 1) {          // (fp32 chains with the phase-accumulator oscillator have neither)
+    if (!f32 && D > 1 && !c->bank_post) {          // (fp32 chains with the phase-accumulator oscillator have neither; msdr_chain_set_bank_post: both run at fs / D)
         if (c->pll) return fail(MSDR_STATUS_ARGUMENT_ERROR, "decimation: not on a chain created with MSDR_CHAIN_SYNCAM_PLL (the PLL demodulator runs at the full rate); nothing changed");
         if (chain_anr_active(c)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "decimation: not while an LMS channel is on (msdr_chain_set_anr); nothing changed");
     }
     c->decim = D;
     return 0;
 }
+
+// PLL and LMS behind the per-receiver kernel (msdr_bank_post.hiph): a switch of the host's for the rest of the chain's life, made over a clear
+// history only (the rule of the first msdr_chain_set_nco_channels); it changes nothing until the chain is in phase-accumulator mode
+extern "C" int msdr_chain_set_bank_post(msdr_chain *c, int on)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (int rc = bind(c->ctx)) return rc;
+    if (!on) return c->bank_post ? fail(MSDR_STATUS_ARGUMENT_ERROR, "bank post: the switch holds for the rest of the chain's life; nothing changed") : 0;
+    if (c->bank_post) return 0;
+    if (c->mixer != MSDR_MIXER_NCO) return fail(MSDR_STATUS_ARGUMENT_ERROR, "bank post: this chain has the Fs/4 mixer, which never enters phase-accumulator mode (Minimal-SDR.ino:546-558); nothing changed");
+    if (!c->hist_clear)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "bank post: the switch needs a clear FIR history (before the first msdr_chain_process, or directly after msdr_chain_reset / msdr_chain_init_fir); nothing changed");
+    c->bank_post = true;
+    return 0;
+}
+extern "C" int msdr_chain_get_bank_post(msdr_chain *c, int *on)
+{
+    if (!c || !on) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
+    *on = c->bank_post ? 1 : 0;
+    return 0;
+}
+// the rate the bank's PLL constants are evaluated for (msdr_syncam_constants_rate); an operand of the next call's PLL kernel, so stream-ordered
+extern "C" int msdr_chain_set_pll_rate(msdr_chain *c, double sample_rate)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (!c->bank_post) return fail(MSDR_STATUS_ARGUMENT_ERROR, "PLL rate: only with msdr_chain_set_bank_post on; nothing changed");
+    if (sample_rate != 0.0 && !(std::isfinite(sample_rate) && sample_rate > 0.0))
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "PLL rate %g: 0 (the reference's constants) or a finite rate above 0; nothing changed", sample_rate);
+    c->pll_rate = sample_rate;
+    return 0;
+}
+extern "C" int msdr_chain_get_pll_rate(msdr_chain *c, double *sample_rate)
+{
+    if (!c || !sample_rate) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
+    *sample_rate = c->pll_rate;
+    return 0;
+}
+// fil_out, omega2, phzerror of one channel's loop (msdr_syncam_get_state's shape), whichever kernel steps it
+extern "C" int msdr_chain_get_pll_state(msdr_chain *c, uint32_t channel, float state[3])
+{
+    if (!c || !state) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
+    if (int rc = bind(c->ctx)) return rc;
+    if (!c->pll && !c->f32_pll) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has no PLL demodulator (MSDR_CHAIN_SYNCAM_PLL)");
+    if (channel >= c->channels) return fail(MSDR_STATUS_ARGUMENT_ERROR, "channel %u of %u", channel, c->channels);
+    if (c->pll) return msdr_syncam_get_state(c->pll, channel, state);
+    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+    state[0] = state[1] = state[2] = 0.0f;          // (the records are made by the first call that runs the loop)
+    if (c->d_post_pll_state) HIP_TRY(hipMemcpy(state, c->d_post_pll_state + (size_t)channel * 4, 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return 0;
+}
+extern "C" const char *msdr_chain_post_kernel(msdr_chain *c) { return c ? c->post_kernel : nullptr; }
 
 extern "C" int msdr_chain_get_decimation(msdr_chain *c, uint32_t *D)
 {
@@ -5840,8 +6013,8 @@ extern "C" int msdr_chain_set_biquad_coeffs_channels(msdr_chain *c, uint32_t fir
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "the fp32 cascade belongs to F32 chains (Q15: msdr_chain_set_node_coefficients_channels)");
     const int S = (int)c->h_bq_stages;
     if (S == 0) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain was created without a biquad cascade (numStages is fixed at creation, as in CMSIS)");
-    if (c->f32_pll) return fail(MSDR_STATUS_ARGUMENT_ERROR, "per-channel cascade coefficients: not on a chain created with MSDR_CHAIN_SYNCAM_PLL (its PLL channels run a post cascade of their own); nothing changed");
-    for (int v : c->h_anr) if (v > 0) return fail(MSDR_STATUS_ARGUMENT_ERROR, "per-channel cascade coefficients: not while an LMS channel is on (such channels run a post cascade of their own); nothing changed");
+    if (!chain_bank(c) && c->f32_pll) return fail(MSDR_STATUS_ARGUMENT_ERROR, "per-channel cascade coefficients: not on a chain created with MSDR_CHAIN_SYNCAM_PLL (its PLL channels run a post cascade of their own); nothing changed");
+    for (int v : c->h_anr) if (!chain_bank(c) && v > 0) return fail(MSDR_STATUS_ARGUMENT_ERROR, "per-channel cascade coefficients: not while an LMS channel is on (such channels run a post cascade of their own); nothing changed");
     if (count == 0) return 0;
     if (!coeffs) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null coefficient array");
     if (first_channel >= c->channels || count > c->channels - first_channel)
@@ -5865,7 +6038,7 @@ extern "C" int msdr_chain_set_anr(msdr_chain *c, const int32_t *anr_on, int32_t 
     if (c->arith != MSDR_ARITH_Q15) {
         // fp32 chain: the float flavour of the filter, between demodulator and cascade (chain_post_run)
         if (c->seq_bq && !c->h_bq_stages) return fail(MSDR_STATUS_ARGUMENT_ERROR, "internal: cascade coefficients not kept");
-        if ((c->seq_bq && c->seq_bq->per_channel) || c->opc_active || c->nco_active || c->n_inputs || c->d_meter) {      // (LMS channels run a post cascade with the chain's uniform coefficients, behind an auxiliary chain with the shared oscillator tables)
+        if (!chain_bank(c) && ((c->seq_bq && c->seq_bq->per_channel) || c->opc_active || c->nco_active || c->n_inputs || c->d_meter)) {      // (LMS channels run a post cascade with the chain's uniform coefficients, behind an auxiliary chain with the shared oscillator tables)
             bool any = anr_on ? false : anr_on_all > 0;
             if (anr_on) for (uint32_t ch = 0; ch < c->channels; ch++) any = any || anr_on[ch] > 0;
             if (any && c->n_inputs) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has an input map (msdr_chain_set_input_rows): no LMS channels (they run through an auxiliary chain that gathers its rows from d_if by channel); nothing changed");
@@ -5880,7 +6053,7 @@ extern "C" int msdr_chain_set_anr(msdr_chain *c, const int32_t *anr_on, int32_t 
         c->anr_gen++;
         return 0;
     }
-    if (c->decim > 1) {          // msdr_chain_set_decimation: the LMS filter belongs to the full rate
+    if (c->decim > 1 && !c->bank_post) {          // msdr_chain_set_decimation: the LMS filter belongs to the full rate (msdr_chain_set_bank_post: to fs / D)
         bool any = anr_on ? false : anr_on_all > 0;
         if (anr_on) for (uint32_t ch = 0; ch < c->channels; ch++) any = any || anr_on[ch] > 0;
         if (any) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain decimates (msdr_chain_set_decimation): no LMS channels; nothing changed");

@@ -16,6 +16,7 @@
 //                          (the baseband I/Q output, msdr_chain_iq.hiph, is a flavour of the four phase-accumulator kernels in their own units: chain_*_iq_kernel, chain_*_iq_meter_kernel)
 //   msdr_chain_f32pcb.hip  the fp32 chain with per-channel settings at block cadence, one launch per call: chain_f32pcb_kernel
 //   msdr_chain_q15pcb.hip  the Q15 chain with per-channel settings at block cadence, one launch per call: chain_q15pcb_kernel
+//   msdr_bank_post.hip     the PLL demodulator behind the down-converter bank, over the I/Q twins' pairs: bank_pll_q15_kernel, bank_pll_f32_kernel
 // Host-side geometry helpers (LDS sizes, table formats) live with the kernels' headers; the launch geometry of the per-receiver chain kernels
 // (PcLaunch, pc_geometry, kPcLdsCap) is msdr_pc_geometry.h, plain C++; the eight launchers of those kernels are calls of one body, pc_launch
 // (msdr_pc_launch.h).  Every launcher returns the HIP error of its launch.
@@ -129,4 +130,16 @@ hipError_t launch_chain_f32pcb(hipStream_t stream, bool fs4, PcbParams p, PcLaun
 // 64 KB of LDS (osc_len = 0: Fs/4).
 bool chain_q15pcb_lds(int n, int np, int osc_len, PcLaunch *geo);
 hipError_t launch_chain_q15pcb(hipStream_t stream, bool fs4, QpcbParams p, PcLaunch *geo);
+// ---- msdr_bank_post.hip ----
+// bank_pll_q15_kernel / bank_pll_f32_kernel (msdr_bank_post.hiph): the PLL demodulator of msdr_chain_set_bank_post over the pairs the I/Q twins
+// of the per-receiver kernels stored -- pairs [channels][pair_pitch] (one packed dword / one float2 each), audio [channels][n] (int16 / float),
+// state [channels][4].  Rows of channels whose mode is SYNCAM are rewritten, the others untouched.  The launcher refuses (hipErrorInvalidValue)
+// a null operand, n > pair_pitch and pairs that are not aligned to their size.
+struct BankPllParams {
+    const void *pairs; long long pair_pitch;
+    void *audio; long long n;
+    float *state; const int *chan_mode; int channels;
+    float omega_min, omega_max, g1, g2;          // msdr_syncam_constants' four, or msdr_syncam_constants_rate's
+};
+hipError_t launch_bank_pll(hipStream_t stream, bool f32, const BankPllParams &p);
 }  // namespace msdr

@@ -461,6 +461,13 @@ public:
     // receiver rx's record behind the last tick (msdr_chain_get_agc: multiplier, agc_idx, AGC_val bits, absmax, steps, 0, 0, agc_buffer[25]);
     // waits for the tick's kernels
     int readAgc(uint32_t rx, int32_t state[MSDR_AGC_STATE_WORDS]) { return chain ? msdr_chain_get_agc(chain, rx, state) : MSDR_STATUS_ARGUMENT_ERROR; }
+    // Synchronous AM and the LMS filter for the bank (msdr_chain_set_bank_post): BEFORE setNco() and the first tick; from setNco() on the PLL
+    // demodulator and the LMS filter run behind the per-receiver kernel on the stored pairs, at the bank's output rate.  For the node's life.
+    int setBankPost(bool on = true) { return chain ? msdr_chain_set_bank_post(chain, on ? 1 : 0) : MSDR_STATUS_ARGUMENT_ERROR; }
+    // the rate the PLL constants are evaluated for from the next tick on (msdr_chain_set_pll_rate): 0 = the reference's; after setBankPost()
+    int setPllRate(double sample_rate) { return chain ? msdr_chain_set_pll_rate(chain, sample_rate) : MSDR_STATUS_ARGUMENT_ERROR; }
+    // receiver rx's loop behind the last tick (msdr_chain_get_pll_state: fil_out, omega2, phzerror); waits for the tick's kernels
+    int readPllState(uint32_t rx, float state[3]) { return chain ? msdr_chain_get_pll_state(chain, rx, state) : MSDR_STATUS_ARGUMENT_ERROR; }
     virtual void update(void)
     {
         audio_block_t *in = receiveReadOnly(0);

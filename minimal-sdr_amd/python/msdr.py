@@ -38,6 +38,7 @@ FLAVOUR_METER = 0x200000
 FLAVOUR_IQ_OUT = 0x400000
 FLAVOUR_COMPLEX_IN = 0x800000
 FLAVOUR_GAIN = 0x1000000
+FLAVOUR_BANK_POST = 0x2000000
 AGC_STATE_WORDS = 32
 MAX_DECIMATION_Q15, MAX_DECIMATION_F32 = 60, 59
 FE_DCBLOCK, FE_AMP, FE_AGC, FE_ALL = 1, 2, 4, 7
@@ -130,6 +131,13 @@ def load_library(path=None):
                        ("msdr_chain_set_gain_channels", [_p, C.c_uint32, C.c_uint32, _p]),
                        ("msdr_chain_set_agc", [_p, _p, C.c_int32]),
                        ("msdr_chain_get_agc", [_p, C.c_uint32, _p]),
+                       ("msdr_chain_set_bank_post", [_p, C.c_int]),
+                       ("msdr_chain_get_bank_post", [_p, _p]),
+                       ("msdr_chain_get_pll_state", [_p, C.c_uint32, _p]),
+                       ("msdr_syncam_constants_rate", [C.c_double, _p]),
+                       ("msdr_chain_set_pll_rate", [_p, C.c_double]),
+                       ("msdr_chain_get_pll_rate", [_p, _p]),
+                       ("msdr_chain_post_kernel", [_p]),
                        ("msdr_nco_step", [C.c_double, C.c_double]),
                        ("msdr_nco_table", [_p]),
                        ("msdr_nco_q15", [_p, C.c_size_t, _p, _p]),
@@ -137,6 +145,8 @@ def load_library(path=None):
                        ("msdr_chain_get_cmsis_state", [_p, C.c_uint32, _p])):
             if hasattr(_lib, n):
                 getattr(_lib, n).argtypes = sig
+        if hasattr(_lib, "msdr_syncam_constants_rate"):
+            _lib.msdr_syncam_constants_rate.restype = None
         if hasattr(_lib, "msdr_meter_dbfs"):
             _lib.msdr_meter_dbfs.restype = C.c_double
         if hasattr(_lib, "msdr_nco_step"):
@@ -766,6 +776,14 @@ def syncam_constants():
     return c
 
 
+def syncam_constants_rate(sample_rate):
+    """omega_min, omega_max, g1, g2 of the PLL evaluated for `sample_rate` (msdr_syncam_constants_rate): syncam_constants() at 24000, bit for
+    bit; what Chain.set_pll_rate puts in force for a bank that runs its loop at fs / D"""
+    c = np.zeros(4, np.float32)
+    load_library().msdr_syncam_constants_rate(C.c_double(float(sample_rate)), _hp(c))
+    return c
+
+
 def amp_multiplier(n):
     lib = load_library()
     lib.msdr_amp_multiplier.restype = C.c_int32
@@ -1021,6 +1039,40 @@ class Chain(_Instance):
         _ck(self.ctx.lib.msdr_chain_get_agc(self.h, C.c_uint32(channel), _hp(w)))
         return {"multiplier": int(w[0]), "agc_idx": int(w[1]), "AGC_val": float(w[2:3].view(np.float32)[0]), "absmax": int(w[3]),
                 "steps": int(w[4]), "agc_buffer": w[7:32].copy(), "words": w}
+
+    def set_bank_post(self, on=True):
+        """Synchronous AM and the LMS filter for the bank: once the chain is in phase-accumulator mode (set_nco_channels), its PLL demodulator
+        and LMS filter run behind the per-receiver kernel on the pairs its I/Q twin stores, at fs / D, never through the auxiliary chain --
+        which lets an fp32 chain with CHAIN_SYNCAM_PLL / LMS channels enter that mode and a Q15 one decimate.  Over a clear FIR history only,
+        NCO mixer only, and for the rest of the chain's life (msdr_chain_set_bank_post)."""
+        _ck(self.ctx.lib.msdr_chain_set_bank_post(self.h, C.c_int(1 if on else 0)))
+
+    def bank_post(self):
+        """whether the switch is on (msdr_chain_get_bank_post)"""
+        on = C.c_int(0)
+        _ck(self.ctx.lib.msdr_chain_get_bank_post(self.h, C.byref(on)))
+        return bool(on.value)
+
+    def set_pll_rate(self, sample_rate):
+        """the rate the bank's PLL constants are evaluated for, from the next process() on: 0 = the reference's constants (the default), else
+        fs / D as the caller sees fit; state kept; with set_bank_post on only (msdr_chain_set_pll_rate)"""
+        _ck(self.ctx.lib.msdr_chain_set_pll_rate(self.h, C.c_double(float(sample_rate))))
+
+    def pll_rate(self):
+        """the rate in force, 0 = the reference's constants (msdr_chain_get_pll_rate)"""
+        r = C.c_double(0.0)
+        _ck(self.ctx.lib.msdr_chain_get_pll_rate(self.h, C.byref(r)))
+        return r.value
+
+    def pll_state(self, channel):
+        """fil_out, omega2, phzerror of the channel's PLL behind every call so far (synchronises; msdr_chain_get_pll_state)"""
+        st = np.zeros(3, np.float32)
+        _ck(self.ctx.lib.msdr_chain_get_pll_state(self.h, C.c_uint32(channel), _hp(st)))
+        return st
+
+    def post_kernel(self):
+        """msdr_chain_post_kernel: the PLL kernel of the last audio process() ("" where none ran)"""
+        return _kernel_name(self.ctx.lib.msdr_chain_post_kernel, self.h)
 
     def set_block_kernel(self, on):
         """F32: a block-cadence call of a chain in per-channel mode as ONE launch (chain_f32pcb_kernel: demodulator, CMSIS-order cascade, int16
