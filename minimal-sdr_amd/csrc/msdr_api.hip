@@ -233,18 +233,40 @@ __attribute__((visibility("hidden"))) int msdr_ptr_query(msdr_ctx *ctx, const vo
 __attribute__((visibility("hidden"))) unsigned msdr_free_generation(void) { return g_free_generation.load(std::memory_order_relaxed); }
 // msdr_cmsis.cpp's refusals: the text msdr_last_error() returns
 __attribute__((visibility("hidden"))) int msdr_cmsis_fail(int code, const char *text) { return fail(code, "%s", text); }
+// ------------------------------------------------------------------------------------------------
+// transfers: the ONLY functions of the host layer that call hipMemcpy* / hipMemset* (tests/test_host_transfers.py holds the line).
+// Every one is enqueued on ctx->stream, so it is ordered behind the clears, copies and kernels the stream already holds; the null stream
+// would not be (ctx->stream is non-blocking).  They return the HIP status: call sites wrap them in HIP_TRY or word their own refusal.
+// ------------------------------------------------------------------------------------------------
+static hipError_t waited(msdr_ctx *ctx, hipError_t e) { return e == hipSuccess ? hipStreamSynchronize(ctx->stream) : e; }
+// host -> device WITHOUT a wait.  Relied on: an asynchronous copy from PAGEABLE host memory returns once the runtime has staged the source
+// (the rule HIP shares with CUDA), so a local, a temporary or a caller's array may die when the call returns; pinned memory has no such
+// promise.  For the uploads of a process path (a wait would stall the host on every kernel queued in front) and for a run of small copies
+// of which only the last one waits.
+static hipError_t copy_in_nowait(msdr_ctx *ctx, void *d_dst, const void *src, size_t bytes) { return hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, ctx->stream); }
+// host -> device, waited for: ordered behind everything the stream holds, and `src` is free on return
+static hipError_t copy_in(msdr_ctx *ctx, void *d_dst, const void *src, size_t bytes) { return waited(ctx, copy_in_nowait(ctx, d_dst, src, bytes)); }
+// the same for `rows` words of `width` bytes, `dpitch` apart on the device and `spitch` apart on the host (one word column of a record table)
+static hipError_t copy_in_2d(msdr_ctx *ctx, void *d_dst, size_t dpitch, const void *src, size_t spitch, size_t width, size_t rows)
+{
+    return waited(ctx, hipMemcpy2DAsync(d_dst, dpitch, src, spitch, width, rows, hipMemcpyHostToDevice, ctx->stream));
+}
+// device -> host, waited for: reads what everything queued so far has written, and `dst` holds it on return
+static hipError_t copy_out(msdr_ctx *ctx, void *dst, const void *d_src, size_t bytes) { return waited(ctx, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream)); }
+// device -> device and byte fill, in stream order, not waited for
+static hipError_t copy_dev(msdr_ctx *ctx, void *d_dst, const void *d_src, size_t bytes) { return hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, ctx->stream); }
+static hipError_t fill_dev(msdr_ctx *ctx, void *d_dst, int value, size_t bytes) { return hipMemsetAsync(d_dst, value, bytes, ctx->stream); }
+
 extern "C" int msdr_memcpy_h2d(msdr_ctx *ctx, void *d_dst, const void *src, size_t bytes)
 {
     if (int rc = bind(ctx)) return rc;
-    HIP_TRY(hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(copy_in(ctx, d_dst, src, bytes));
     return 0;
 }
 extern "C" int msdr_memcpy_d2h(msdr_ctx *ctx, void *dst, const void *d_src, size_t bytes)
 {
     if (int rc = bind(ctx)) return rc;
-    HIP_TRY(hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(copy_out(ctx, dst, d_src, bytes));
     return 0;
 }
 // Not part of the C ABI (msdr_cmsis.cpp's host-array binding): a pinned host buffer the device reads and writes in place -- the shim's block
@@ -264,17 +286,17 @@ __attribute__((visibility("hidden"))) void msdr_mapped_free(msdr_ctx *ctx, void 
 extern "C" int msdr_memcpy_d2d(msdr_ctx *ctx, void *d_dst, const void *d_src, size_t bytes)
 {
     if (int rc = bind(ctx)) return rc;
-    HIP_TRY(hipMemcpyAsync(d_dst, d_src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(copy_dev(ctx, d_dst, d_src, bytes));
     return 0;
 }
 extern "C" int msdr_memset(msdr_ctx *ctx, void *d_dst, int value, size_t bytes)
 {
     if (int rc = bind(ctx)) return rc;
-    HIP_TRY(hipMemsetAsync(d_dst, value, bytes, ctx->stream));
+    HIP_TRY(fill_dev(ctx, d_dst, value, bytes));
     return 0;
 }
 
-// small RAII-free helper: device buffer filled from a host vector
+// small RAII-free helpers: a device buffer filled from a host vector (waited for: the vector is free on return) ...
 template <typename T>
 static int upload(msdr_ctx *ctx, const std::vector<T> &h, T **d)
 {
@@ -282,8 +304,7 @@ static int upload(msdr_ctx *ctx, const std::vector<T> &h, T **d)
     HIP_TRY(hipMalloc((void **)d, std::max<size_t>(h.size() * sizeof(T), 16)));
     if (!h.empty()) {
         // (a failing copy must not leave the buffer behind: callers treat a non-zero return as "nothing was allocated")
-        hipError_t e = hipMemcpyAsync(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        const hipError_t e = copy_in(ctx, *d, h.data(), h.size() * sizeof(T));
         if (e != hipSuccess) {
             (void)hipFree(*d); *d = nullptr;
             return fail(MSDR_STATUS_HIP_ERROR, "upload of %zu bytes failed: %s", h.size() * sizeof(T), hipGetErrorString(e));
@@ -291,13 +312,25 @@ static int upload(msdr_ctx *ctx, const std::vector<T> &h, T **d)
     }
     return 0;
 }
+// ... one that is a copy of `bytes` of host memory (waited for) or of device memory (in stream order).  It returns the HIP status, leaves
+// nothing behind on failure and words no refusal: the setters that make everything that can fail before anything changes word their own.
+static hipError_t device_copy_of(msdr_ctx *ctx, const void *src, size_t bytes, bool from_host, void **d)
+{
+    *d = nullptr;
+    hipError_t e = hipMalloc(d, std::max<size_t>(bytes, 16));
+    if (e == hipSuccess) e = from_host ? copy_in(ctx, *d, src, bytes) : copy_dev(ctx, *d, src, bytes);
+    if (e != hipSuccess) { (void)hipGetLastError(); (void)hipFree(*d); *d = nullptr; }
+    return e;
+}
+// ... and a zeroed one.  The clear is enqueued on ctx->stream and NOT waited for: whatever touches the buffer next through the stream (a
+// kernel, any helper above) sees zeros; nothing else may touch it.
 template <typename T>
 static int dzalloc(msdr_ctx *ctx, size_t count, T **d)
 {
     *d = nullptr;
     size_t bytes = std::max<size_t>(count * sizeof(T), 16);
     HIP_TRY(hipMalloc((void **)d, bytes));
-    const hipError_t e = hipMemsetAsync(*d, 0, bytes, ctx->stream);
+    const hipError_t e = fill_dev(ctx, *d, 0, bytes);
     if (e != hipSuccess) {
         (void)hipFree(*d); *d = nullptr;
         return fail(MSDR_STATUS_HIP_ERROR, "clearing %zu bytes failed: %s", bytes, hipGetErrorString(e));
@@ -907,8 +940,8 @@ static int fir_reset(Inst *S)
     if (!S) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null instance");
     if (int rc = bind(S->ctx)) return rc;
     size_t bytes = (size_t)S->channels * S->hist_len * sizeof(*S->d_hist[0]);
-    HIP_TRY(hipMemsetAsync(S->d_hist[0], 0, bytes, S->ctx->stream));
-    HIP_TRY(hipMemsetAsync(S->d_hist[1], 0, bytes, S->ctx->stream));
+    HIP_TRY(fill_dev(S->ctx, S->d_hist[0], 0, bytes));
+    HIP_TRY(fill_dev(S->ctx, S->d_hist[1], 0, bytes));
     return 0;
 }
 template <typename Inst>
@@ -989,14 +1022,8 @@ static int fir_q15_block_tiles(msdr_fir_q15 *S, int n)
             }
         }
     }
-    if (tab.size() > S->btiles_cap) {
-        HIP_TRY(hipStreamSynchronize(S->ctx->stream));
-        hipFree(S->d_btiles); S->d_btiles = nullptr; S->btiles_cap = 0;
-        if (int rc = dzalloc(S->ctx, tab.size(), &S->d_btiles)) return rc;
-        S->btiles_cap = tab.size();
-    }
-    HIP_TRY(hipMemcpyAsync(S->d_btiles, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, S->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(S->ctx->stream));
+    if (int rc = grow_device(S->ctx, &S->d_btiles, &S->btiles_cap, tab.size())) return rc;
+    HIP_TRY(copy_in(S->ctx, S->d_btiles, tab.data(), tab.size() * sizeof(int)));
     S->bt_n = (uint32_t)n; S->bt_wgs = wgs; S->bt_nw = nw; S->bt_tpw = tpw;
     return 0;
 }
@@ -1097,8 +1124,7 @@ extern "C" int msdr_fir_q15_set_coeffs(msdr_fir_q15 *S, const q15_t *pCoeffs)
         if (int rc = bind(S->ctx)) return rc;
         std::vector<int16_t> t((size_t)S->channels * S->pc_np, 0);
         for (uint32_t ch = 0; ch < S->channels; ch++) memcpy(t.data() + (size_t)ch * S->pc_np + (S->pc_np - S->ntaps), pCoeffs, S->ntaps * sizeof(int16_t));
-        HIP_TRY(hipStreamSynchronize(S->ctx->stream));
-        HIP_TRY(hipMemcpy(S->d_pc_taps, t.data(), t.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+        HIP_TRY(copy_in(S->ctx, S->d_pc_taps, t.data(), t.size() * sizeof(int16_t)));
         return 0;
     }
     msdr_fir_q15 *old = nullptr;
@@ -1121,7 +1147,7 @@ extern "C" int msdr_fir_q15_set_coeffs_channels(msdr_fir_q15 *S, uint32_t first_
     if (!S->per_channel) {          // every channel starts from the shared coefficients (d_taps: int32, front-padded to ntaps_pad)
         const int np = pc_np((int)S->ntaps);
         std::vector<int32_t> shared(S->ntaps_pad);
-        HIP_TRY(hipMemcpy(shared.data(), S->d_taps, shared.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+        HIP_TRY(copy_out(S->ctx, shared.data(), S->d_taps, shared.size() * sizeof(int32_t)));
         std::vector<int16_t> t((size_t)S->channels * np, 0);
         for (uint32_t ch = 0; ch < S->channels; ch++)
             for (uint32_t k = 0; k < S->ntaps; k++) t[(size_t)ch * np + (np - S->ntaps) + k] = (int16_t)shared[S->ntaps_pad - S->ntaps + k];
@@ -1130,7 +1156,7 @@ extern "C" int msdr_fir_q15_set_coeffs_channels(msdr_fir_q15 *S, uint32_t first_
     }
     std::vector<int16_t> rows((size_t)count * S->pc_np, 0);
     for (uint32_t i = 0; i < count; i++) memcpy(rows.data() + (size_t)i * S->pc_np + (S->pc_np - S->ntaps), pCoeffs + (size_t)i * S->ntaps, S->ntaps * sizeof(int16_t));
-    HIP_TRY(hipMemcpy(S->d_pc_taps + (size_t)first_channel * S->pc_np, rows.data(), rows.size() * sizeof(int16_t), hipMemcpyHostToDevice));
+    HIP_TRY(copy_in(S->ctx, S->d_pc_taps + (size_t)first_channel * S->pc_np, rows.data(), rows.size() * sizeof(int16_t)));
     return 0;
 }
 
@@ -1145,13 +1171,12 @@ static int fir_f32_upload_header(msdr_fir_f32 *S)
         if (std::ldexp(1.0, k - 1) == (double)S->input_range) k--;    // an exact power of two
         h.fixed_k = std::max(-100, std::min(100, 15 - k));
     }
-    HIP_TRY(hipMemcpyAsync(S->d_fm_tab, &h, sizeof h, hipMemcpyHostToDevice, S->ctx->stream));
+    HIP_TRY(copy_in(S->ctx, S->d_fm_tab, &h, sizeof h));
     if (S->d_tr_tab) {
         F32TrHeader t;
         t.ns = S->tr_ns; t.ex = S->fm_ex; t.fixed_k = h.fixed_k; t.use_fixed = h.use_fixed; t.skip1 = S->tr_skip1;
-        HIP_TRY(hipMemcpyAsync(S->d_tr_tab, &t, sizeof t, hipMemcpyHostToDevice, S->ctx->stream));
+        HIP_TRY(copy_in(S->ctx, S->d_tr_tab, &t, sizeof t));
     }
-    HIP_TRY(hipStreamSynchronize(S->ctx->stream));
     return 0;
 }
 extern "C" int msdr_fir_f32_create(msdr_ctx *ctx, uint16_t numTaps, const float32_t *pCoeffs, uint32_t channels, msdr_fir_f32 **out)
@@ -1306,8 +1331,7 @@ extern "C" int msdr_fir_f32_set_coeffs(msdr_fir_f32 *S, const float32_t *pCoeffs
         if (int rc = bind(S->ctx)) return rc;
         std::vector<float> t((size_t)S->channels * S->pc_np, 0.0f);
         for (uint32_t ch = 0; ch < S->channels; ch++) memcpy(t.data() + (size_t)ch * S->pc_np + (S->pc_np - S->ntaps), pCoeffs, S->ntaps * sizeof(float));
-        HIP_TRY(hipStreamSynchronize(S->ctx->stream));
-        HIP_TRY(hipMemcpy(S->d_pc_taps, t.data(), t.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(copy_in(S->ctx, S->d_pc_taps, t.data(), t.size() * sizeof(float)));
         return 0;
     }
     msdr_fir_f32 *old = nullptr;
@@ -1336,7 +1360,7 @@ extern "C" int msdr_fir_f32_set_coeffs_channels(msdr_fir_f32 *S, uint32_t first_
     if (!S->per_channel) {          // every channel starts from the shared coefficients (d_taps: front-padded to ntaps_pad)
         const int np = f32pc_np((int)S->ntaps);
         std::vector<float> shared(S->ntaps_pad);
-        HIP_TRY(hipMemcpy(shared.data(), S->d_taps, shared.size() * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(copy_out(S->ctx, shared.data(), S->d_taps, shared.size() * sizeof(float)));
         std::vector<float> t((size_t)S->channels * np, 0.0f);
         for (uint32_t ch = 0; ch < S->channels; ch++)
             for (uint32_t k = 0; k < S->ntaps; k++) t[(size_t)ch * np + (np - S->ntaps) + k] = shared[S->ntaps_pad - S->ntaps + k];
@@ -1345,7 +1369,7 @@ extern "C" int msdr_fir_f32_set_coeffs_channels(msdr_fir_f32 *S, uint32_t first_
     }
     std::vector<float> rows((size_t)count * S->pc_np, 0.0f);
     for (uint32_t i = 0; i < count; i++) memcpy(rows.data() + (size_t)i * S->pc_np + (S->pc_np - S->ntaps), pCoeffs + (size_t)i * S->ntaps, S->ntaps * sizeof(float));
-    HIP_TRY(hipMemcpy(S->d_pc_taps + (size_t)first_channel * S->pc_np, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(copy_in(S->ctx, S->d_pc_taps + (size_t)first_channel * S->pc_np, rows.data(), rows.size() * sizeof(float)));
     return 0;
 }
 // which kernel msdr_fir_f32_process launches for this instance (benchmarks / tests)
@@ -1438,7 +1462,7 @@ extern "C" int msdr_biquad_df1_f32_process(msdr_biquad_df1_f32 *S, const float32
     if (blockSize == 0) return 0;
     if (!d_src || !d_dst) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null buffer");
     if (S->stages == 0) {      // empty cascade: pass-through
-        if (d_src != d_dst) HIP_TRY(hipMemcpyAsync(d_dst, d_src, (size_t)S->channels * blockSize * sizeof(float), hipMemcpyDeviceToDevice, S->ctx->stream));
+        if (d_src != d_dst) HIP_TRY(copy_dev(S->ctx, d_dst, d_src, (size_t)S->channels * blockSize * sizeof(float)));
         return 0;
     }
     if (S->sequential) {
@@ -1518,8 +1542,8 @@ extern "C" int msdr_biquad_df1_f32_reset(msdr_biquad_df1_f32 *S)
 {
     if (!S) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null instance");
     if (int rc = bind(S->ctx)) return rc;
-    HIP_TRY(hipMemsetAsync(S->d_state, 0, (size_t)S->channels * kBqStateFloats * sizeof(float), S->ctx->stream));
-    HIP_TRY(hipMemsetAsync(S->d_state_alt, 0, (size_t)S->channels * kBqStateFloats * sizeof(float), S->ctx->stream));
+    HIP_TRY(fill_dev(S->ctx, S->d_state, 0, (size_t)S->channels * kBqStateFloats * sizeof(float)));
+    HIP_TRY(fill_dev(S->ctx, S->d_state_alt, 0, (size_t)S->channels * kBqStateFloats * sizeof(float)));
     return 0;
 }
 extern "C" int msdr_biquad_df1_f32_destroy(msdr_biquad_df1_f32 *S)
@@ -1565,8 +1589,7 @@ static int biquad_df1_read_cmsis(msdr_biquad_df1_f32 *S, const cstate::Bridge &b
 {
     const int St = (int)S->stages, ny = 2 * St + 2;
     std::vector<float> st((size_t)S->channels * kBqStateFloats);
-    HIP_TRY(hipStreamSynchronize(S->ctx->stream));
-    HIP_TRY(hipMemcpy(st.data(), S->d_state, st.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(copy_out(S->ctx, st.data(), S->d_state, st.size() * sizeof(float)));
     Y.assign((size_t)S->channels * ny, 0.0); D.assign((size_t)S->channels * 8, 0.0);
     for (uint32_t ch = 0; ch < S->channels; ch++) {
         const float *r = st.data() + (size_t)ch * kBqStateFloats;
@@ -1594,7 +1617,7 @@ static int biquad_df1_write_cmsis(msdr_biquad_df1_f32 *S, const cstate::Bridge &
             br.cmsis_to_lib(y, d, r + 8);
         }
     }
-    HIP_TRY(hipMemcpy(S->d_state, st.data(), st.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(copy_in(S->ctx, S->d_state, st.data(), st.size() * sizeof(float)));
     return 0;
 }
 extern "C" int msdr_biquad_df1_f32_get_cmsis_state(msdr_biquad_df1_f32 *S, uint32_t channel, float32_t *pState)
@@ -1603,8 +1626,7 @@ extern "C" int msdr_biquad_df1_f32_get_cmsis_state(msdr_biquad_df1_f32 *S, uint3
     if (int rc = bind(S->ctx)) return rc;
     if (S->stages == 0) return 0;
     float r[kBqStateFloats];
-    HIP_TRY(hipStreamSynchronize(S->ctx->stream));
-    HIP_TRY(hipMemcpy(r, S->d_state + (size_t)channel * kBqStateFloats, sizeof r, hipMemcpyDeviceToHost));
+    HIP_TRY(copy_out(S->ctx, r, S->d_state + (size_t)channel * kBqStateFloats, sizeof r));
     if (S->sequential) { memcpy(pState, r, (size_t)4 * S->stages * sizeof(float)); return 0; }
     return msdr_biquad_df1_f32_state_to_cmsis((uint8_t)S->stages, S->h_coeffs.data(), r, pState);
 }
@@ -1616,9 +1638,8 @@ extern "C" int msdr_biquad_df1_f32_set_coeffs(msdr_biquad_df1_f32 *S, const floa
     if (S->per_channel) {
         // the instance runs biquad_df1_seq_pc_kernel for life: set_coeffs keeps writing ALL channels, i.e. every row of the table; the state is
         // pState itself and stays as it is (as msdr_fir_f32_set_coeffs does on a per-channel FIR)
-        HIP_TRY(hipStreamSynchronize(S->ctx->stream));
         for (uint32_t ch = 0; ch < S->channels; ch++) memcpy(S->h_pc_coeffs.data() + (size_t)ch * kSbqTabFloats, pCoeffs, 5 * S->stages * sizeof(float));
-        HIP_TRY(hipMemcpy(S->d_pc_coeffs, S->h_pc_coeffs.data(), S->h_pc_coeffs.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(copy_in(S->ctx, S->d_pc_coeffs, S->h_pc_coeffs.data(), S->h_pc_coeffs.size() * sizeof(float)));
         S->h_coeffs.assign(pCoeffs, pCoeffs + 5 * S->stages);
         S->pole_radius = max_pole_radius(pCoeffs, (int)S->stages);
         S->h_pc_radius.assign(S->channels, S->pole_radius);
@@ -1682,8 +1703,8 @@ extern "C" int msdr_biquad_df1_f32_set_coeffs_channels(msdr_biquad_df1_f32 *S, u
     }
     S->pc_radius_max = *std::max_element(S->h_pc_radius.begin(), S->h_pc_radius.end());
     S->pc_radius_min = *std::min_element(S->h_pc_radius.begin(), S->h_pc_radius.end());
-    HIP_TRY(hipMemcpy(S->d_pc_coeffs + (size_t)first_channel * kSbqTabFloats, S->h_pc_coeffs.data() + (size_t)first_channel * kSbqTabFloats,
-                      (size_t)count * kSbqTabFloats * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(copy_in(S->ctx, S->d_pc_coeffs + (size_t)first_channel * kSbqTabFloats, S->h_pc_coeffs.data() + (size_t)first_channel * kSbqTabFloats,
+                    (size_t)count * kSbqTabFloats * sizeof(float)));
     return 0;
 }
 
@@ -1894,8 +1915,8 @@ static int freqconv_common(msdr_ctx *ctx, T *d_i, T *d_q, const T *osc_i, const 
         ctx->scratch_bytes = std::max<size_t>(need, 4096);
     }
     T *di = (T *)ctx->scratch, *dq = di + osc_len;
-    HIP_TRY(hipMemcpyAsync(di, osc_i, osc_len * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(dq, osc_q, osc_len * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(copy_in_nowait(ctx, di, osc_i, osc_len * sizeof(T)));
+    HIP_TRY(copy_in_nowait(ctx, dq, osc_q, osc_len * sizeof(T)));
     hipLaunchKernelGGL(kernel, dim3(grid_1d(total)), dim3(256), 0, ctx->stream, d_i, d_q, (const T *)di, (const T *)dq,
                        (int)osc_len, dir ? 1 : 0, total, (int)blockSize);
     return launch_check(name);
@@ -1948,11 +1969,10 @@ struct msdr_frontend {
 
 static int fe_edit(msdr_frontend *fe, const std::function<void(uint32_t, int *)> &f)
 {
-    HIP_TRY(hipStreamSynchronize(fe->ctx->stream));
     std::vector<int> h((size_t)fe->channels * kFeStateInts);
-    HIP_TRY(hipMemcpy(h.data(), fe->d_state, h.size() * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(copy_out(fe->ctx, h.data(), fe->d_state, h.size() * sizeof(int)));
     for (uint32_t ch = 0; ch < fe->channels; ch++) f(ch, h.data() + (size_t)ch * kFeStateInts);
-    HIP_TRY(hipMemcpy(fe->d_state, h.data(), h.size() * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(copy_in(fe->ctx, fe->d_state, h.data(), h.size() * sizeof(int)));
     return 0;
 }
 
@@ -2034,8 +2054,7 @@ extern "C" int msdr_frontend_get_state(msdr_frontend *fe, uint32_t channel, int3
     if (!fe || !state) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
     if (int rc = bind(fe->ctx)) return rc;
     if (channel >= fe->channels) return fail(MSDR_STATUS_ARGUMENT_ERROR, "channel out of range");
-    HIP_TRY(hipStreamSynchronize(fe->ctx->stream));
-    HIP_TRY(hipMemcpy(state, fe->d_state + (size_t)channel * kFeStateInts, kFeStateInts * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(copy_out(fe->ctx, state, fe->d_state + (size_t)channel * kFeStateInts, kFeStateInts * sizeof(int)));
     return 0;
 }
 extern "C" int msdr_frontend_destroy(msdr_frontend *fe)
@@ -2128,7 +2147,7 @@ extern "C" int msdr_syncam_reset(msdr_syncam *S)
 {
     if (!S) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null instance");
     if (int rc = bind(S->ctx)) return rc;
-    HIP_TRY(hipMemsetAsync(S->d_state, 0, (size_t)S->channels * 4 * sizeof(float), S->ctx->stream));
+    HIP_TRY(fill_dev(S->ctx, S->d_state, 0, (size_t)S->channels * 4 * sizeof(float)));
     return 0;
 }
 extern "C" int msdr_syncam_get_state(msdr_syncam *S, uint32_t channel, float state[3])
@@ -2136,8 +2155,7 @@ extern "C" int msdr_syncam_get_state(msdr_syncam *S, uint32_t channel, float sta
     if (!S || !state) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
     if (int rc = bind(S->ctx)) return rc;
     if (channel >= S->channels) return fail(MSDR_STATUS_ARGUMENT_ERROR, "channel out of range");
-    HIP_TRY(hipStreamSynchronize(S->ctx->stream));
-    HIP_TRY(hipMemcpy(state, S->d_state + (size_t)channel * 4, 3 * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(copy_out(S->ctx, state, S->d_state + (size_t)channel * 4, 3 * sizeof(float)));
     return 0;
 }
 extern "C" int msdr_syncam_destroy(msdr_syncam *S)
@@ -2158,12 +2176,12 @@ struct msdr_anr {
     uint32_t channels;
     float *d_state;        // [channels][kAnrStateFloats]
 };
-static int anr_init_state(msdr_anr *A)
+// every channel's LMS record as the sketch's globals start (also the records of an fp32 chain's post passes)
+static int anr_init_state(msdr_ctx *ctx, uint32_t channels, float *d_state)
 {
-    std::vector<float> h((size_t)A->channels * kAnrStateFloats, 0.0f);
-    for (uint32_t ch = 0; ch < A->channels; ch++) { h[(size_t)ch * kAnrStateFloats] = 120.0f; h[(size_t)ch * kAnrStateFloats + 1] = 0.001f; }   // .ino:715,:718
-    HIP_TRY(hipMemcpyAsync(A->d_state, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice, A->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(A->ctx->stream));
+    std::vector<float> h((size_t)channels * kAnrStateFloats, 0.0f);
+    for (uint32_t ch = 0; ch < channels; ch++) { h[(size_t)ch * kAnrStateFloats] = 120.0f; h[(size_t)ch * kAnrStateFloats + 1] = 0.001f; }   // .ino:715,:718
+    HIP_TRY(copy_in(ctx, d_state, h.data(), h.size() * sizeof(float)));
     return 0;
 }
 extern "C" int msdr_anr_create(msdr_ctx *ctx, uint32_t channels, msdr_anr **out)
@@ -2177,7 +2195,7 @@ extern "C" int msdr_anr_create(msdr_ctx *ctx, uint32_t channels, msdr_anr **out)
     if (!A) return fail(MSDR_STATUS_OUT_OF_MEMORY, "host allocation failed");
     A->ctx = ctx; A->channels = channels; A->d_state = nullptr;
     if (int rc = dzalloc(ctx, (size_t)channels * kAnrStateFloats, &A->d_state)) { delete A; return rc; }
-    if (int rc = anr_init_state(A)) { hipFree(A->d_state); delete A; return rc; }
+    if (int rc = anr_init_state(ctx, channels, A->d_state)) { hipFree(A->d_state); delete A; return rc; }
     *out = A;
     return 0;
 }
@@ -2196,15 +2214,14 @@ extern "C" int msdr_anr_reset(msdr_anr *A)
 {
     if (!A) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null instance");
     if (int rc = bind(A->ctx)) return rc;
-    return anr_init_state(A);
+    return anr_init_state(A->ctx, A->channels, A->d_state);
 }
 extern "C" int msdr_anr_get_state(msdr_anr *A, uint32_t channel, float state[MSDR_ANR_STATE_FLOATS])
 {
     if (!A || !state) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
     if (int rc = bind(A->ctx)) return rc;
     if (channel >= A->channels) return fail(MSDR_STATUS_ARGUMENT_ERROR, "channel out of range");
-    HIP_TRY(hipStreamSynchronize(A->ctx->stream));
-    HIP_TRY(hipMemcpy(state, A->d_state + (size_t)channel * kAnrStateFloats, kAnrStateFloats * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(copy_out(A->ctx, state, A->d_state + (size_t)channel * kAnrStateFloats, kAnrStateFloats * sizeof(float)));
     return 0;
 }
 extern "C" int msdr_anr_destroy(msdr_anr *A)
@@ -2628,27 +2645,25 @@ static void chain_pc_row_shared(msdr_chain *c, uint32_t ch)       // the rows of
     if (c->arith == MSDR_ARITH_F32) { chain_pcf_row_from(c, ch, (const float *)c->store.ci[ts].data(), (const float *)c->store.cq[ts].data()); return; }
     chain_pc_row_from(c, ch, (const int16_t *)c->store.ci[ts].data(), (const int16_t *)c->store.cq[ts].data());
 }
-// rows first .. first + count - 1 to the device; the stream is drained first (a kernel in flight reads the table)
+// rows first .. first + count - 1 to the device, in stream order: behind the kernels in flight that read the table, in place on return
 static int chain_pc_upload(msdr_chain *c, uint32_t first, uint32_t count)
 {
-    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
     const size_t row = (size_t)2 * c->pc_np;
     if (c->arith == MSDR_ARITH_F32) {
-        HIP_TRY(hipMemcpy(c->d_pcf_taps + first * row, c->h_pcf_taps.data() + first * row, count * row * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(copy_in(c->ctx, c->d_pcf_taps + first * row, c->h_pcf_taps.data() + first * row, count * row * sizeof(float)));
         c->post_mode_gen = 0;          // PLL / LMS channels: the auxiliary chain is made again with these rows (chain_post_build_steps)
         return 0;
     }
-    HIP_TRY(hipMemcpy(c->d_pc_taps + first * row, c->h_pc_taps.data() + first * row, count * row * sizeof(int16_t), hipMemcpyHostToDevice));
+    HIP_TRY(copy_in(c->ctx, c->d_pc_taps + first * row, c->h_pc_taps.data() + first * row, count * row * sizeof(int16_t)));
     return 0;
 }
 
-// pairs first .. first + count - 1 of the phase-accumulator oscillator's bank to the device; the stream is drained first (a kernel in flight reads it)
+// pairs first .. first + count - 1 of the phase-accumulator oscillator's bank to the device, in stream order (a kernel in flight reads the bank)
 static int chain_nco_upload(msdr_chain *c, uint32_t first, uint32_t count)
 {
-    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
     std::vector<uint32_t> pairs((size_t)2 * count);
     for (uint32_t k = 0; k < count; k++) { pairs[2 * k] = c->h_nco_base[first + k]; pairs[2 * k + 1] = c->h_nco_step[first + k]; }
-    HIP_TRY(hipMemcpy(c->d_nco_bank + (size_t)2 * first, pairs.data(), pairs.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(copy_in(c->ctx, c->d_nco_bank + (size_t)2 * first, pairs.data(), pairs.size() * sizeof(uint32_t)));
     return 0;
 }
 
@@ -3544,9 +3559,8 @@ static int chain_post_states(msdr_chain *c)
 {
     if (!c->d_post_pll_state) if (int rc = dzalloc(c->ctx, (size_t)c->channels * 4, &c->d_post_pll_state)) return rc;
     if (!c->d_post_anr_state) {
-        std::vector<float> h((size_t)c->channels * kAnrStateFloats, 0.0f);
-        for (uint32_t ch = 0; ch < c->channels; ch++) { h[(size_t)ch * kAnrStateFloats] = 120.0f; h[(size_t)ch * kAnrStateFloats + 1] = 0.001f; }   // .ino:715,:718
-        if (int rc = upload(c->ctx, h, &c->d_post_anr_state)) return rc;
+        if (int rc = dzalloc(c->ctx, (size_t)c->channels * kAnrStateFloats, &c->d_post_anr_state)) return rc;
+        if (int rc = anr_init_state(c->ctx, c->channels, c->d_post_anr_state)) { hipFree(c->d_post_anr_state); c->d_post_anr_state = nullptr; return rc; }
     }
     return 0;
 }
@@ -3561,7 +3575,7 @@ static int chain_post_build_steps(msdr_chain *c)
     const std::vector<int> old_ch = c->h_post_ch;
     if (c->post_bq && !old_ch.empty()) {
         old_bq.resize(old_ch.size() * kBqStateFloats);
-        HIP_TRY(hipMemcpy(old_bq.data(), c->post_bq->d_state, old_bq.size() * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(copy_out(c->ctx, old_bq.data(), c->post_bq->d_state, old_bq.size() * sizeof(float)));
     }
     chain_post_free(c);
     c->h_post_ch.clear();
@@ -3605,7 +3619,7 @@ static int chain_post_build_steps(msdr_chain *c)
         msdr_chain::OscPending q{nullptr, o.elapsed};
         const size_t bytes = (size_t)c->osc_len * 2 * sizeof(float);
         HIP_TRY(hipMalloc(&q.d_tab, bytes));
-        HIP_TRY(hipMemcpy(q.d_tab, o.d_tab, bytes, hipMemcpyDeviceToDevice));
+        HIP_TRY(copy_dev(c->ctx, q.d_tab, o.d_tab, bytes));          // (the uploads below wait for it)
         c->aux->osc_pending.push_back(q); c->aux->force_generic = true;
     }
     if (c->h_bq_stages) {
@@ -3615,7 +3629,7 @@ static int chain_post_build_steps(msdr_chain *c)
             for (size_t pn = 0; pn < post_ch.size(); pn++)
                 for (size_t po = 0; po < old_ch.size(); po++)
                     if (old_ch[po] == post_ch[pn]) { memcpy(&st[pn * kBqStateFloats], &old_bq[po * kBqStateFloats], kBqStateFloats * sizeof(float)); break; }
-            HIP_TRY(hipMemcpy(c->post_bq->d_state, st.data(), st.size() * sizeof(float), hipMemcpyHostToDevice));
+            HIP_TRY(copy_in(c->ctx, c->post_bq->d_state, st.data(), st.size() * sizeof(float)));
         }
     }
     if (int rc = upload(c->ctx, post_ch, &c->d_post_ch)) return rc;
@@ -3876,8 +3890,7 @@ static int chain_block_tiles(msdr_chain *c, int n_, const std::function<int(uint
         }
     }
     if (int rc = grow_device(c->ctx, &c->d_btiles, &c->btiles_cap, tab.size())) return rc;
-    HIP_TRY(hipMemcpyAsync(c->d_btiles, tab.data(), tab.size() * sizeof(int), hipMemcpyHostToDevice, c->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(c->ctx->stream));        // `tab` is a local
+    HIP_TRY(copy_in(c->ctx, c->d_btiles, tab.data(), tab.size() * sizeof(int)));        // `tab` is a local
     c->btiles_mode_gen = c->mode_gen; c->btiles_n = (long long)n_;
     return 0;
 }
@@ -4113,8 +4126,7 @@ static int chain_mfw_units(msdr_chain *c, const ChainTiles &t)
     while ((units.size() / 2) % nw) { units.push_back(-1); units.push_back(0); }
     if (order.empty() || !env_of(order.back())) ssb_units = units.size() / 2;                               // no envelope tables at all
     if (int rc = grow_device(c->ctx, &c->d_units, &c->units_cap, units.size())) return rc;
-    HIP_TRY(hipMemcpyAsync(c->d_units, units.data(), units.size() * sizeof(int), hipMemcpyHostToDevice, c->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(c->ctx->stream));        // `units` is a local
+    HIP_TRY(copy_in(c->ctx, c->d_units, units.data(), units.size() * sizeof(int)));        // `units` is a local
     c->units_mode_gen = c->mode_gen; c->units_tiles = t.tiles; c->units_wgs = (uint32_t)(units.size() / 2 / nw);
     c->units_wgs_ssb = (uint32_t)(ssb_units / nw);
     return 0;
@@ -4137,8 +4149,7 @@ static int chain_qm_order(msdr_chain *c)
             c->qm_group_count[gi] = (uint32_t)order.size() - c->qm_group_start[gi];
         }
     if (!c->d_qm_order) HIP_TRY(hipMalloc((void **)&c->d_qm_order, (size_t)c->channels * sizeof(int)));
-    HIP_TRY(hipMemcpyAsync(c->d_qm_order, order.data(), order.size() * sizeof(int), hipMemcpyHostToDevice, c->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+    HIP_TRY(copy_in(c->ctx, c->d_qm_order, order.data(), order.size() * sizeof(int)));
     c->qm_order_gen = c->mode_gen;
     return 0;
 }
@@ -4166,8 +4177,7 @@ static int chain_prepare(msdr_chain *c, ChainDecision &d, const ChainTiles &t, c
             oh.tab[oh.n] = o.d_tab; oh.sw[oh.n] = -o.elapsed; oh.stride[oh.n] = o.stride; oh.n++;
         }
         if (!c->d_osc_hist) HIP_TRY(hipMalloc((void **)&c->d_osc_hist, sizeof(OscHistory)));
-        HIP_TRY(hipMemcpyAsync(c->d_osc_hist, &oh, sizeof oh, hipMemcpyHostToDevice, c->ctx->stream));
-        HIP_TRY(hipStreamSynchronize(c->ctx->stream));                  // (`oh` is a local; this path runs for one history length after a table change)
+        HIP_TRY(copy_in(c->ctx, c->d_osc_hist, &oh, sizeof oh));                  // (`oh` is a local; this path runs for one history length after a table change)
         p.osc_hist = c->d_osc_hist;
     }
     if (d.i16 == kI16InKernel && path_mfw(d.path)) p.dbg |= kChainOutI16;       // (chain_f32pcb_kernel: PcbParams.out_i16)
@@ -4913,10 +4923,10 @@ extern "C" int msdr_chain_reset(msdr_chain *c)
     if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
     if (int rc = bind(c->ctx)) return rc;
     size_t hb = (size_t)2 * c->channels * c->hist_len * sizeof(int16_t);          // (the whole buffer: pairs under msdr_chain_set_complex_input)
-    HIP_TRY(hipMemsetAsync(c->d_hist[0], 0, hb, c->ctx->stream));
-    HIP_TRY(hipMemsetAsync(c->d_hist[1], 0, hb, c->ctx->stream));
-    if (c->d_bq_state_alt) HIP_TRY(hipMemsetAsync(c->d_bq_state_alt, 0, (size_t)c->channels * kBqStateFloats * sizeof(float), c->ctx->stream));
-    if (c->d_bq_state) HIP_TRY(hipMemsetAsync(c->d_bq_state, 0, (size_t)c->channels * kBqStateFloats * sizeof(float), c->ctx->stream));
+    HIP_TRY(fill_dev(c->ctx, c->d_hist[0], 0, hb));
+    HIP_TRY(fill_dev(c->ctx, c->d_hist[1], 0, hb));
+    if (c->d_bq_state_alt) HIP_TRY(fill_dev(c->ctx, c->d_bq_state_alt, 0, (size_t)c->channels * kBqStateFloats * sizeof(float)));
+    if (c->d_bq_state) HIP_TRY(fill_dev(c->ctx, c->d_bq_state, 0, (size_t)c->channels * kBqStateFloats * sizeof(float)));
     // (a full clear for tests and stream restarts; the reference's init_FIR() is msdr_chain_init_fir(): FIR state only.  The
     //  Teensy biquad NODES keep their history here too, as the reference never clears it: filter_biquad.cpp:95-97.)
     if (c->pll) if (int rc = msdr_syncam_reset(c->pll)) return rc;
@@ -4924,10 +4934,8 @@ extern "C" int msdr_chain_reset(msdr_chain *c)
     if (c->seq_bq) if (int rc = msdr_biquad_df1_f32_reset(c->seq_bq)) return rc;
     if (c->aux) { HIP_TRY(hipStreamSynchronize(c->ctx->stream)); chain_post_free(c); c->h_post_ch.clear(); c->post_mode_gen = 0; }      // rebuilt from the cleared state
     if (c->d_post_pll_state) {
-        HIP_TRY(hipMemsetAsync(c->d_post_pll_state, 0, (size_t)c->channels * 4 * sizeof(float), c->ctx->stream));
-        std::vector<float> h((size_t)c->channels * kAnrStateFloats, 0.0f);
-        for (uint32_t ch = 0; ch < c->channels; ch++) { h[(size_t)ch * kAnrStateFloats] = 120.0f; h[(size_t)ch * kAnrStateFloats + 1] = 0.001f; }
-        HIP_TRY(hipMemcpy(c->d_post_anr_state, h.data(), h.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(fill_dev(c->ctx, c->d_post_pll_state, 0, (size_t)c->channels * 4 * sizeof(float)));
+        if (int rc = anr_init_state(c->ctx, c->channels, c->d_post_anr_state)) return rc;
     }
     if (!c->osc_pending.empty() || c->force_generic) {          // no sample of an earlier oscillator table is left in a cleared history
         HIP_TRY(hipStreamSynchronize(c->ctx->stream));
@@ -5000,11 +5008,10 @@ extern "C" int msdr_chain_init_fir(msdr_chain *c)
     if (any_folded && c->d_bq_state) {
         // a folded channel's numerator history lives in the raw IF history that is about to be cleared: hand it over as
         // first-sample corrections, exactly as a retune does (msdr_chain_set_mode)
-        HIP_TRY(hipStreamSynchronize(c->ctx->stream));
         std::vector<int16_t> hist((size_t)c->channels * c->hist_len);
         std::vector<float> st((size_t)c->channels * kBqStateFloats);
-        HIP_TRY(hipMemcpy(hist.data(), c->d_hist[c->cur], hist.size() * sizeof(int16_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(st.data(), c->d_bq_state, st.size() * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(copy_out(c->ctx, hist.data(), c->d_hist[c->cur], hist.size() * sizeof(int16_t)));
+        HIP_TRY(copy_out(c->ctx, st.data(), c->d_bq_state, st.size() * sizeof(float)));
         const double zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (uint32_t ch = 0; ch < c->channels; ch++) {
             if (!chain_mode_folded(c, c->h_mode[ch])) continue;
@@ -5012,12 +5019,12 @@ extern "C" int msdr_chain_init_fir(msdr_chain *c)
             chain_true_history(c, ch, hist.data() + (size_t)ch * c->hist_len, st.data() + (size_t)ch * kBqStateFloats, D);
             chain_folded_correction(c, D, zero, st.data() + (size_t)ch * kBqStateFloats);
         }
-        HIP_TRY(hipMemcpy(c->d_bq_state, st.data(), st.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(copy_in(c->ctx, c->d_bq_state, st.data(), st.size() * sizeof(float)));
     }
     if (c->aux) if (int rc = msdr_chain_init_fir(c->aux)) return rc;             // the PLL / LMS channels' filters with it
     const size_t hb = (size_t)2 * c->channels * c->hist_len * sizeof(int16_t);          // (the whole buffer: pairs under msdr_chain_set_complex_input)
-    HIP_TRY(hipMemsetAsync(c->d_hist[0], 0, hb, c->ctx->stream));
-    HIP_TRY(hipMemsetAsync(c->d_hist[1], 0, hb, c->ctx->stream));
+    HIP_TRY(fill_dev(c->ctx, c->d_hist[0], 0, hb));
+    HIP_TRY(fill_dev(c->ctx, c->d_hist[1], 0, hb));
     c->hist_clear = true;
     return 0;
 }
@@ -5034,11 +5041,10 @@ extern "C" int msdr_chain_set_mode(msdr_chain *c, uint32_t channel, int32_t mode
     {
         const int old_mode = c->h_mode[channel], old_ts = c->h_tapset[channel];
         if ((chain_mode_folded(c, old_mode) || chain_mode_folded(c, mode)) && (old_mode != mode || old_ts != tapset)) {
-            HIP_TRY(hipStreamSynchronize(c->ctx->stream));
             std::vector<int16_t> hist(c->hist_len);
             float st[kBqStateFloats];
-            HIP_TRY(hipMemcpy(hist.data(), c->d_hist[c->cur] + (size_t)channel * c->hist_len, hist.size() * sizeof(int16_t), hipMemcpyDeviceToHost));
-            HIP_TRY(hipMemcpy(st, c->d_bq_state + (size_t)channel * kBqStateFloats, sizeof st, hipMemcpyDeviceToHost));
+            HIP_TRY(copy_out(c->ctx, hist.data(), c->d_hist[c->cur] + (size_t)channel * c->hist_len, hist.size() * sizeof(int16_t)));
+            HIP_TRY(copy_out(c->ctx, st, c->d_bq_state + (size_t)channel * kBqStateFloats, sizeof st));
             double D[8];
             chain_true_history(c, channel, hist.data(), st, D);
             float out[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -5047,17 +5053,16 @@ extern "C" int msdr_chain_set_mode(msdr_chain *c, uint32_t channel, int32_t mode
                 chain_ssb_history(c, hist.data(), mode, tapset, Dn);
                 chain_folded_correction(c, D, Dn, out);
             } else for (int k = 0; k < 8; k++) out[k] = (float)D[k];
-            HIP_TRY(hipMemcpy(c->d_bq_state + (size_t)channel * kBqStateFloats, out, sizeof out, hipMemcpyHostToDevice));
+            HIP_TRY(copy_in(c->ctx, c->d_bq_state + (size_t)channel * kBqStateFloats, out, sizeof out));
         }
     }
     c->h_mode[channel] = mode; c->h_tapset[channel] = tapset; c->mode_gen++;
     if (c->d_fset) {
         const int fs = tapset * 3 + (mode == MSDR_MODE_LSB ? 0 : mode == MSDR_MODE_USB ? 1 : 2);
-        HIP_TRY(hipMemcpyAsync(c->d_fset + channel, &fs, sizeof(int), hipMemcpyHostToDevice, c->ctx->stream));
+        HIP_TRY(copy_in_nowait(c->ctx, c->d_fset + channel, &fs, sizeof(int)));
     }
-    HIP_TRY(hipMemcpyAsync(c->d_mode + channel, &mode, sizeof(int), hipMemcpyHostToDevice, c->ctx->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_tapset + channel, &tapset, sizeof(int), hipMemcpyHostToDevice, c->ctx->stream));
-    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
+    HIP_TRY(copy_in_nowait(c->ctx, c->d_mode + channel, &mode, sizeof(int)));
+    HIP_TRY(copy_in(c->ctx, c->d_tapset + channel, &tapset, sizeof(int)));
     if (c->pc_active) {          // back on a shared tap set: the channel's own taps are dropped, its rows become a copy of that set's
         c->h_pc_own[channel] = 0;
         chain_pc_row_shared(c, channel);
@@ -5183,8 +5188,8 @@ static int chain_leave_generic(msdr_chain *c)
     if (!any || !c->d_bq_state) return 0;
     std::vector<int16_t> hist((size_t)c->channels * c->hist_len);
     std::vector<float> st((size_t)c->channels * kBqStateFloats);
-    HIP_TRY(hipMemcpy(hist.data(), c->d_hist[c->cur], hist.size() * sizeof(int16_t), hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(st.data(), c->d_bq_state, st.size() * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_TRY(copy_out(c->ctx, hist.data(), c->d_hist[c->cur], hist.size() * sizeof(int16_t)));
+    HIP_TRY(copy_out(c->ctx, st.data(), c->d_bq_state, st.size() * sizeof(float)));
     for (uint32_t ch = 0; ch < c->channels; ch++) {
         if (!chain_mode_folded(c, c->h_mode[ch])) continue;
         float *r = st.data() + (size_t)ch * kBqStateFloats;
@@ -5194,7 +5199,7 @@ static int chain_leave_generic(msdr_chain *c)
         chain_folded_correction(c, D, Dn, r);
         memcpy(c->dh_cache[ch].v, D, sizeof D); c->dh_gen[ch] = c->gen;
     }
-    HIP_TRY(hipMemcpy(c->d_bq_state, st.data(), st.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(copy_in(c->ctx, c->d_bq_state, st.data(), st.size() * sizeof(float)));
     return 0;
 }
 
@@ -5210,10 +5215,9 @@ static int chain_rebuild_keep_folded(msdr_chain *c, const ChainCfgStore &edited,
     std::vector<float> st;
     std::vector<double> Dall;
     if (!fix.empty()) {
-        HIP_TRY(hipStreamSynchronize(c->ctx->stream));
         hist.resize((size_t)c->channels * c->hist_len); st.resize((size_t)c->channels * kBqStateFloats); Dall.resize((size_t)c->channels * 8);
-        HIP_TRY(hipMemcpy(hist.data(), c->d_hist[c->cur], hist.size() * sizeof(int16_t), hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(st.data(), c->d_bq_state, st.size() * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(copy_out(c->ctx, hist.data(), c->d_hist[c->cur], hist.size() * sizeof(int16_t)));
+        HIP_TRY(copy_out(c->ctx, st.data(), c->d_bq_state, st.size() * sizeof(float)));
         for (uint32_t ch : fix) chain_true_history(c, ch, hist.data() + (size_t)ch * c->hist_len, st.data() + (size_t)ch * kBqStateFloats, Dall.data() + (size_t)ch * 8);
     }
     void *old_osc = nullptr;
@@ -5234,7 +5238,7 @@ static int chain_rebuild_keep_folded(msdr_chain *c, const ChainCfgStore &edited,
     if (!fix.empty() && c->d_bq_state) {
         if (hist.size() != (size_t)c->channels * c->hist_len) {
             hist.resize((size_t)c->channels * c->hist_len);
-            HIP_TRY(hipMemcpy(hist.data(), c->d_hist[c->cur], hist.size() * sizeof(int16_t), hipMemcpyDeviceToHost));
+            HIP_TRY(copy_out(c->ctx, hist.data(), c->d_hist[c->cur], hist.size() * sizeof(int16_t)));
         }
         for (uint32_t ch : fix) {
             float *r = st.data() + (size_t)ch * kBqStateFloats;
@@ -5244,7 +5248,7 @@ static int chain_rebuild_keep_folded(msdr_chain *c, const ChainCfgStore &edited,
                 chain_ssb_history(c, hist.data() + (size_t)ch * c->hist_len, c->h_mode[ch], c->h_tapset[ch], Dn);
                 chain_folded_correction(c, D, Dn, r);
             } else for (int k = 0; k < 8; k++) r[k] = (float)D[k];       // (the rebuilt chain does not fold this mode any more)
-            HIP_TRY(hipMemcpy(c->d_bq_state + (size_t)ch * kBqStateFloats, r, 8 * sizeof(float), hipMemcpyHostToDevice));
+            HIP_TRY(copy_in(c->ctx, c->d_bq_state + (size_t)ch * kBqStateFloats, r, 8 * sizeof(float)));
         }
     }
     return 0;
@@ -5382,14 +5386,13 @@ extern "C" int msdr_chain_set_input_rows(msdr_chain *c, uint32_t n_inputs, const
         if (!c->pc_active && f32pc_np((int)c->ntaps) > f32pc_max_taps(false))
             return fail(MSDR_STATUS_ARGUMENT_ERROR, "input rows: the per-channel kernel holds filters of up to %d taps (this chain has %u); nothing changed", f32pc_max_taps(false), c->ntaps);
     }
-    HIP_TRY(hipStreamSynchronize(c->ctx->stream));          // (a kernel in flight reads the table)
     if (!c->d_in_row) if (int rc = dzalloc(c->ctx, (size_t)c->channels, &c->d_in_row)) return rc;
     const bool taps_first = !c->pc_active;                  // the per-channel kernel family, entered as the other per-channel setters enter it
     if (int rc = chain_pc_activate(c)) return rc;
     if (taps_first) if (int rc = chain_pc_upload(c, 0, c->channels)) return rc;
     if (n_inputs > 0) {
         std::vector<int> rows(input_row, input_row + c->channels);
-        HIP_TRY(hipMemcpy(c->d_in_row, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice));
+        HIP_TRY(copy_in(c->ctx, c->d_in_row, rows.data(), rows.size() * sizeof(int)));
     }
     c->n_inputs = n_inputs;
     c->in_row_epoch++;
@@ -5472,26 +5475,27 @@ static int chain_osc_rows(msdr_chain *c, uint32_t first, uint32_t count, const v
     chain_osc_pairs(c, rows.data(), count, osc_i, osc_q, src_stride);
     HIP_TRY(hipStreamSynchronize(c->ctx->stream));
     void *bank = nullptr, *snap = nullptr;
-    if (first_call && hipMalloc(&bank, (size_t)c->channels * row_bytes) != hipSuccess) { (void)hipGetLastError(); return fail(MSDR_STATUS_OUT_OF_MEMORY, "device allocation of the oscillator bank failed"); }
+    if (first_call) {          // the bank, filled from the stored shared tables
+        std::vector<char> all((size_t)c->channels * row_bytes);
+        chain_osc_pairs(c, all.data(), c->channels, c->store.osc_i.data(), c->store.osc_q.data(), 0);
+        const hipError_t e = device_copy_of(c->ctx, all.data(), all.size(), true, &bank);
+        if (e == hipErrorOutOfMemory) return fail(MSDR_STATUS_OUT_OF_MEMORY, "device allocation of the oscillator bank failed");
+        if (e != hipSuccess) return fail(MSDR_STATUS_HIP_ERROR, "upload of the oscillator bank failed");
+    }
     // a table that was replaced before any sample arrived under it mixed nothing: it is not a generation (chain_rebuild_keep_folded)
     const bool new_gen = c->osc_pending.empty() || c->osc_pending.back().elapsed != 0;
     if (new_gen) {
         const size_t nb = first_call ? row_bytes : (size_t)c->channels * row_bytes;
-        if (hipMalloc(&snap, nb) != hipSuccess || hipMemcpy(snap, first_call ? c->d_osc : c->d_osc_bank, nb, hipMemcpyDeviceToDevice) != hipSuccess) {
-            (void)hipGetLastError(); hipFree(bank); hipFree(snap);
+        if (device_copy_of(c->ctx, first_call ? c->d_osc : c->d_osc_bank, nb, false, &snap) != hipSuccess) {
+            hipFree(bank);
             return fail(MSDR_STATUS_OUT_OF_MEMORY, "device copy of the oscillator tables in force (one pending generation: channels x osc_len x 8 bytes) failed");
         }
     }
     const bool taps_first = !c->pc_active;
     if (int rc = chain_pc_activate(c)) { hipFree(bank); hipFree(snap); return rc; }
     if (taps_first) if (int rc = chain_pc_upload(c, 0, c->channels)) { hipFree(bank); hipFree(snap); return rc; }
-    if (first_call) {
-        std::vector<char> all((size_t)c->channels * row_bytes);
-        chain_osc_pairs(c, all.data(), c->channels, c->store.osc_i.data(), c->store.osc_q.data(), 0);
-        if (hipMemcpy(bank, all.data(), all.size(), hipMemcpyHostToDevice) != hipSuccess) { (void)hipGetLastError(); hipFree(bank); hipFree(snap); return fail(MSDR_STATUS_HIP_ERROR, "upload of the oscillator bank failed"); }
-        c->d_osc_bank = bank; c->opc_active = true;
-    }
-    HIP_TRY(hipMemcpy((char *)c->d_osc_bank + (size_t)first * row_bytes, rows.data(), rows.size(), hipMemcpyHostToDevice));
+    if (first_call) { c->d_osc_bank = bank; c->opc_active = true; }
+    HIP_TRY(copy_in(c->ctx, (char *)c->d_osc_bank + (size_t)first * row_bytes, rows.data(), rows.size()));
     if (new_gen) {
         if (c->osc_pending.size() >= (size_t)kOscHistMax) { hipFree(c->osc_pending.front().d_tab); c->osc_pending.erase(c->osc_pending.begin()); }
         c->osc_pending.push_back(msdr_chain::OscPending{snap, 0, first_call ? 0 : (int)L});
@@ -5606,18 +5610,15 @@ extern "C" int msdr_chain_set_nco_channels(msdr_chain *c, uint32_t first_channel
     if (first_call) {
         uint32_t packed[kNcoTabLen];
         nco_pack(nco_host_table(), packed);
-        if (hipMalloc((void **)&bank, bank_bytes) != hipSuccess || hipMalloc((void **)&tab, sizeof packed) != hipSuccess ||
-            hipMemcpy(tab, packed, sizeof packed, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipGetLastError(); hipFree(bank); hipFree(tab);
+        if (hipMalloc((void **)&bank, bank_bytes) != hipSuccess || device_copy_of(c->ctx, packed, sizeof packed, true, (void **)&tab) != hipSuccess) {
+            (void)hipGetLastError(); hipFree(bank);
             return fail(MSDR_STATUS_OUT_OF_MEMORY, "device allocation of the oscillator bank failed");
         }
     }
     // a bank that was replaced before any sample arrived under it mixed nothing: it is not a generation; nor does a clear history hold a sample of it
     const bool new_gen = !first_call && !c->hist_clear && (c->osc_pending.empty() || c->osc_pending.back().elapsed != 0);
-    if (new_gen && (hipMalloc(&snap, bank_bytes) != hipSuccess || hipMemcpy(snap, c->d_nco_bank, bank_bytes, hipMemcpyDeviceToDevice) != hipSuccess)) {
-        (void)hipGetLastError(); hipFree(snap);
+    if (new_gen && device_copy_of(c->ctx, c->d_nco_bank, bank_bytes, false, &snap) != hipSuccess)
         return fail(MSDR_STATUS_OUT_OF_MEMORY, "device copy of the oscillator bank in force (one pending generation: channels x 8 bytes) failed");
-    }
     if (first_call) {
         const bool taps_first = !c->pc_active;
         if (int rc = chain_pc_activate(c)) { hipFree(bank); hipFree(tab); return rc; }
@@ -5720,9 +5721,8 @@ extern "C" int msdr_chain_get_pll_state(msdr_chain *c, uint32_t channel, float s
     if (!c->pll && !c->f32_pll) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has no PLL demodulator (MSDR_CHAIN_SYNCAM_PLL)");
     if (channel >= c->channels) return fail(MSDR_STATUS_ARGUMENT_ERROR, "channel %u of %u", channel, c->channels);
     if (c->pll) return msdr_syncam_get_state(c->pll, channel, state);
-    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
     state[0] = state[1] = state[2] = 0.0f;          // (the records are made by the first call that runs the loop)
-    if (c->d_post_pll_state) HIP_TRY(hipMemcpy(state, c->d_post_pll_state + (size_t)channel * 4, 3 * sizeof(float), hipMemcpyDeviceToHost));
+    if (c->d_post_pll_state) HIP_TRY(copy_out(c->ctx, state, c->d_post_pll_state + (size_t)channel * 4, 3 * sizeof(float)));
     return 0;
 }
 extern "C" const char *msdr_chain_post_kernel(msdr_chain *c) { return c ? c->post_kernel : nullptr; }
@@ -5842,10 +5842,9 @@ extern "C" int msdr_chain_set_gain_channels(msdr_chain *c, uint32_t first_channe
         if (c->arith == MSDR_ARITH_F32) memcpy(&words[k], &g, sizeof(int)); else words[k] = fe_multiplier(v);
         memcpy(&words[count + k], &v, sizeof(int));
     }
-    HIP_TRY(hipStreamSynchronize(c->ctx->stream));          // (the step kernel of a call in flight rewrites the same words)
     int *first = c->d_agc + (size_t)first_channel * kGainWords;
-    HIP_TRY(hipMemcpy2D(first + kGainMult, kGainWords * sizeof(int), words.data(), sizeof(int), sizeof(int), count, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy2D(first + kGainVal, kGainWords * sizeof(int), words.data() + count, sizeof(int), sizeof(int), count, hipMemcpyHostToDevice));
+    HIP_TRY(copy_in_2d(c->ctx, first + kGainMult, kGainWords * sizeof(int), words.data(), sizeof(int), sizeof(int), count));
+    HIP_TRY(copy_in_2d(c->ctx, first + kGainVal, kGainWords * sizeof(int), words.data() + count, sizeof(int), sizeof(int), count));
     return 0;
 }
 
@@ -5859,8 +5858,7 @@ extern "C" int msdr_chain_set_agc(msdr_chain *c, const int32_t *agc_on, int32_t 
     if (int rc = chain_agc_ensure(c)) return rc;
     std::vector<int> h(c->channels, (int)agc_on_all);
     if (agc_on) for (uint32_t ch = 0; ch < c->channels; ch++) h[ch] = (int)agc_on[ch];
-    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
-    HIP_TRY(hipMemcpy2D(c->d_agc + kGainOn, kGainWords * sizeof(int), h.data(), sizeof(int), sizeof(int), c->channels, hipMemcpyHostToDevice));
+    HIP_TRY(copy_in_2d(c->ctx, c->d_agc + kGainOn, kGainWords * sizeof(int), h.data(), sizeof(int), sizeof(int), c->channels));
     return 0;
 }
 
@@ -5872,8 +5870,7 @@ extern "C" int msdr_chain_get_agc(msdr_chain *c, uint32_t channel, int32_t state
     if (int rc = bind(c->ctx)) return rc;
     if (!c->nco_active || !c->d_agc) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain has no gain state (msdr_chain_set_gain / msdr_chain_set_gain_channels / msdr_chain_set_agc)");
     if (channel >= c->channels) return fail(MSDR_STATUS_ARGUMENT_ERROR, "channel %u of %u", channel, c->channels);
-    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
-    HIP_TRY(hipMemcpy(state, c->d_agc + (size_t)channel * kGainWords, kGainWords * sizeof(int), hipMemcpyDeviceToHost));
+    HIP_TRY(copy_out(c->ctx, state, c->d_agc + (size_t)channel * kGainWords, kGainWords * sizeof(int)));
     state[kGainOn] = 0; state[kGainPeak] = 0;
     return 0;
 }
@@ -5931,11 +5928,10 @@ static int chain_set_biquad_coeffs_impl(msdr_chain *c, const float32_t *coeffs, 
     }
     cstate::Bridge br;
     br.build(c->h_bq.data(), coeffs, S);
-    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
     // ---- every channel's state in CMSIS terms, and the cascade's true input history ----
     std::vector<double> Y((size_t)c->channels * ny, 0.0), D((size_t)c->channels * 8, 0.0);
     std::vector<int16_t> hist((size_t)c->channels * c->hist_len);
-    HIP_TRY(hipMemcpy(hist.data(), c->d_hist[c->cur], hist.size() * sizeof(int16_t), hipMemcpyDeviceToHost));
+    HIP_TRY(copy_out(c->ctx, hist.data(), c->d_hist[c->cur], hist.size() * sizeof(int16_t)));
     if (c->seq_bq) {
         // (a stage object that runs block-parallel keeps its state in the coefficient-dependent basis too: the same refusal applies --
         //  build_to() leaves its matrices zero on failure, and reading through them would silently zero the filter's state)
@@ -5944,7 +5940,7 @@ static int chain_set_biquad_coeffs_impl(msdr_chain *c, const float32_t *coeffs, 
     } else {
         if (!br.ok_to) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the running cascade's block-parallel state has no unique CMSIS state (a numerator shares a root with an earlier denominator)");
         std::vector<float> st((size_t)c->channels * kBqStateFloats);
-        HIP_TRY(hipMemcpy(st.data(), c->d_bq_state, st.size() * sizeof(float), hipMemcpyDeviceToHost));
+        HIP_TRY(copy_out(c->ctx, st.data(), c->d_bq_state, st.size() * sizeof(float)));
         for (uint32_t ch = 0; ch < c->channels; ch++) {
             double *d = D.data() + (size_t)ch * 8;
             chain_true_history(c, ch, hist.data() + (size_t)ch * c->hist_len, st.data() + (size_t)ch * kBqStateFloats, d);
@@ -5979,7 +5975,7 @@ static int chain_set_biquad_coeffs_impl(msdr_chain *c, const float32_t *coeffs, 
     if (old_seq) msdr_biquad_df1_f32_destroy(old_seq);
     if (hist.size() != (size_t)c->channels * c->hist_len) {      // (the history length follows the cascade's place: read the carried-over copy)
         hist.resize((size_t)c->channels * c->hist_len);
-        HIP_TRY(hipMemcpy(hist.data(), c->d_hist[c->cur], hist.size() * sizeof(int16_t), hipMemcpyDeviceToHost));
+        HIP_TRY(copy_out(c->ctx, hist.data(), c->d_hist[c->cur], hist.size() * sizeof(int16_t)));
     }
     if (c->seq_bq) {
         if (int rc = biquad_df1_write_cmsis(c->seq_bq, br, Y, D)) return rc;
@@ -5996,7 +5992,7 @@ static int chain_set_biquad_coeffs_impl(msdr_chain *c, const float32_t *coeffs, 
             } else for (int k = 0; k < 2 * S; k++) r[k] = (float)d[k];
             memcpy(c->dh_cache[ch].v, d, 8 * sizeof(double)); c->dh_gen[ch] = c->gen;
         }
-        HIP_TRY(hipMemcpy(c->d_bq_state, st.data(), st.size() * sizeof(float), hipMemcpyHostToDevice));
+        HIP_TRY(copy_in(c->ctx, c->d_bq_state, st.data(), st.size() * sizeof(float)));
     }
     // the post channels' own cascade (rows f2 / f3 inside the fp32 chain)
     if (c->post_bq) if (int rc = msdr_biquad_df1_f32_set_coeffs(c->post_bq, coeffs)) return rc;
@@ -6102,8 +6098,7 @@ extern "C" int msdr_chain_get_fir_history(msdr_chain *c, uint32_t channel, int16
     if (!hist) return 0;
     const uint32_t per = c->cx_on ? 2u : 1u;          // msdr_chain_set_complex_input: pairs {I, Q}, interleaved
     if (capacity < per * c->hist_len) return fail(MSDR_STATUS_ARGUMENT_ERROR, "the history holds %u int16, room for %u given", per * c->hist_len, capacity);
-    HIP_TRY(hipStreamSynchronize(c->ctx->stream));
-    HIP_TRY(hipMemcpy(hist, c->d_hist[c->cur] + (size_t)per * channel * c->hist_len, (size_t)per * c->hist_len * sizeof(int16_t), hipMemcpyDeviceToHost));
+    HIP_TRY(copy_out(c->ctx, hist, c->d_hist[c->cur] + (size_t)per * channel * c->hist_len, (size_t)per * c->hist_len * sizeof(int16_t)));
     return 0;
 }
 extern "C" int msdr_chain_get_cmsis_state(msdr_chain *c, uint32_t channel, float32_t *pState)

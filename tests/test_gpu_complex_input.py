@@ -203,8 +203,7 @@ def test_ten_receivers_on_one_antenna_row(ctx, orc, golden):
     si, sq = Bank(steps, phases).advance(n)
     xi, xq = (rng.integers(-30000, 30001, (1, n)).astype(I16) for _ in range(2))
     chain = cx_chain(ctx, ch, ti, tq, steps, phases, modes, 0)
-    for _ in range(2):          # (set twice, as tools/pc_kernels_digest.py's set_map explains)
-        chain.set_input_rows(np.zeros(ch, np.int32), 1)
+    chain.set_input_rows(np.zeros(ch, np.int32), 1)
     audio, pairs, _ = cx_run(ctx, chain, interleave(xi, xq), B, ch=ch, pdtype=I16)
     want = refs(orc, np.repeat(xi, ch, 0), np.repeat(xq, ch, 0), si, sq, 0, modes, ti, tq)
     same(audio, pairs, want, np.arange(n), "antenna")

@@ -61,11 +61,7 @@ def taps(rng, rows, nt, f32):
 
 
 def set_map(chain):
-    """The map, set twice.  The first msdr_chain_set_input_rows of a chain allocates the table and clears it on the chain's stream, then uploads
-    the rows with a blocking copy that does not wait for that clear: on the first chain of a process the clear has been seen to land after
-    the upload (rows read as 0).  The second call waits for the stream before it uploads."""
-    for _ in range(2):
-        chain.set_input_rows(np.array(MAP))
+    chain.set_input_rows(np.array(MAP))
 
 
 def record(obj, channels, calls, out_dtype, in_dtype=np.int16):
