@@ -370,6 +370,22 @@ int msdr_anr_destroy(msdr_anr *A);
  *   msdr_rfft128_tables    host side, no device: the constant tables the transform uses, regenerated from their documented
  *                              formulas -- twiddleCoef_64_q15[96] | realCoefAQ15 pairs at stride 64 [128] | realCoefBQ15 ditto [128]
  *                              (arm_common_tables.c:12914, arm_rfft_init_q15.c:44-56, :1086-1098).
+ *   msdr_cfft64_q15 / msdr_cfft64_f32   a receiver's panadapter line: nfft batched 64-point complex forward transforms (bank_cfft64_q15_kernel /
+ *                              bank_cfft64_f32_kernel, msdr_bank_spectrum.hiph).  Transform f reads 64 pairs {I, Q} at
+ *                              d_pairs + 2 * f * stride_pairs (64 <= stride_pairs <= 2^40, else MSDR_STATUS_ARGUMENT_ERROR; d_pairs 4-byte
+ *                              aligned for Q15, 8-byte for F32) and
+ *                              writes d_bins[f][64] pairs {re, im} in natural bin order (bin k = k fs' / 64, k >= 32 the negative
+ *                              frequencies) and / or d_power[f][64] in display order: column x = re^2 + im^2 of bin (x + 32) & 63, so
+ *                              column 32 is the tuned frequency.  Either output may be NULL (both, or a misaligned operand -- the
+ *                              outputs are written in 16-byte slots: MSDR_STATUS_ARGUMENT_ERROR); nfft == 0 does nothing; stream-ordered,
+ *                              never synchronises.  Q15 is arm_cfft_q15 of length 64, forward, with bit reversal (arm_cfft_radix4_q15.c's
+ *                              Cortex-M4 branch, then arm_bitreversal_16: what arm_rfft_q15 runs in front of its split stage), bit-exact,
+ *                              scale 1 / 64; its power is the exact integer in a uint32_t (at most 2^31).  F32 bins are
+ *                              (1 / 64) sum_m z[m] exp(-2 pi i k m / 64) in fp32 (twiddles rounded once from double; no atomics:
+ *                              bit-identical from run to run), power re^2 + im^2 in fp32.
+ *   msdr_spectrum_dbfs     host only: 10 log10(power / (full_scale^2 / 4)), -HUGE_VAL for power <= 0 -- msdr_meter_dbfs's convention
+ *                              (full_scale = 32768 for Q15, 32768 * in_scale for F32): a full-scale real carrier on a bin centre behind a
+ *                              unity-gain channel filter reads 0 dBFS in its bin.
  */
 void msdr_rfft128_tables(int16_t tables[352]);
 int msdr_rfft_q15_init_check(uint32_t fftLenReal, uint32_t ifftFlagR, uint32_t bitReverseFlag);
@@ -380,6 +396,10 @@ int msdr_spectrum_create(msdr_ctx *ctx, uint32_t channels, msdr_spectrum **out);
 int msdr_spectrum_set_on(msdr_spectrum *S, int spectrum_on);
 int msdr_spectrum_show(msdr_spectrum *S, const q15_t *d_data, uint64_t channel_stride, q15_t *d_fft_out, uint8_t *d_columns, int *drawn);
 int msdr_spectrum_destroy(msdr_spectrum *S);
+#define MSDR_SPECTRUM_BINS 64
+int msdr_cfft64_q15(msdr_ctx *ctx, const q15_t *d_pairs, uint64_t stride_pairs, q15_t *d_bins, uint32_t *d_power, uint32_t nfft);
+int msdr_cfft64_f32(msdr_ctx *ctx, const float *d_pairs, uint64_t stride_pairs, float *d_bins, float *d_power, uint32_t nfft);
+double msdr_spectrum_dbfs(double power, double full_scale);
 
 /* Stateless per-block stages. */
 /* what AudioOutputAnalog::isr writes to the 12-bit DAC, output_dac.cpp:139-151: (sample + 32768) >> 4;
@@ -871,6 +891,31 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   The PLL pass runs in every audio call of such a chain that has a PLL while a channel is on SYNCAM, at every D; I/Q-only calls leave the
  *   PLL and LMS states untouched; msdr_chain_reset clears both, msdr_chain_init_fir keeps them.  Graphs stay refused, as on every chain in
  *   this mode.  Reporting: on fp32 chains flavour carries MSDR_FLAVOUR_BANK_POST exactly when the call ran the bank's PLL or LMS pass.
+ * msdr_chain_set_spectrum: a panadapter line per receiver.  While on, every successful msdr_chain_process keeps the most recent 64 pairs of
+ *   each receiver -- the pairs of msdr_chain_set_iq_out's definition, gained when gain is on, at fs / D -- in a tail [channels][64] of the
+ *   chain's own: the tail becomes the last 64 of (old tail ++ this call's n_out pairs) before anything is drawn, so a call with n_out >= 64
+ *   transforms its own last 64 outputs and a bank at block cadence with D = 8 the last four ticks.  On the calls showSpectrum's cadence
+ *   picks (UI.cpp:534-535: `if (--counter > 0) return; counter = every;`, the counter starting at 0, so the first call draws; every == 0
+ *   means 25, the reference's value, every == 1 every call) the 64-point transform of every tail (msdr_cfft64_q15 / msdr_cfft64_f32,
+ *   their arithmetic and layouts) overwrites all `channels` rows of d_bins [channels][64] pairs {re, im} and / or d_power [channels][64]
+ *   (uint32_t for Q15, float for F32), device memory of the caller's, 16-byte aligned; a call that does not draw writes neither.  One NULL:
+ *   only the other is written; both NULL: off (the default).  The pairs come from the caller's d_iq where one is set and else from the
+ *   chain's own per-call pair buffer (msdr_chain_set_bank_post's), for which the main launch picks its I/Q twin; I/Q-only calls feed the
+ *   window like any other.  One small launch per call while on (bank_cfft64_q15_kernel / bank_cfft64_f32_kernel: the tail moves in place,
+ *   the drawing calls transform), stream-ordered, never synchronising.  A msdr_chain_process that returns an error (MSDR_STATUS_LENGTH_ERROR
+ *   included) moves neither tail nor counter nor the count of spectra drawn and writes nothing.  Off -> on clears tail, counter and count; a
+ *   call while on with other pointers or another `every` keeps all three (the new `every` loads at the next reload); msdr_chain_reset clears
+ *   tail and counter, msdr_chain_init_fir keeps both.  Scope: chains in phase-accumulator mode (msdr_chain_set_decimation's rule), Q15 and
+ *   F32; a NULL chain, a chain not in the mode, a misaligned buffer and every > 2^31 - 1 (the counter is showSpectrum's int) are
+ *   MSDR_STATUS_ARGUMENT_ERROR, nothing changed.  The setting
+ *   survives everything the meter pointer survives and combines, in either order, with set_iq_out, set_meter, set_decimation,
+ *   set_input_rows, set_complex_input, set_gain / AGC, set_bank_post and the tap, NCO, node, cascade and mode setters;
+ *   msdr_chain_set_block_kernel[_q15] stays accepted and such calls run the unfused launches; graphs stay refused, as on every chain in this
+ *   mode.  Reporting: msdr_chain_get_info().kernel keeps its names; on fp32 chains flavour carries MSDR_FLAVOUR_SPECTRUM exactly while on.
+ *   Orientation: the transform takes the pair as z = I + jQ, and on a real-input chain that z turns clockwise for a carrier ABOVE the tuned
+ *   frequency: such a carrier falls LEFT of column 32 (46.875 Hz per column at fs / D = 3000).
+ * msdr_chain_get_spectrum: the pointers and `every` in force (0 reads back as 25) and the spectra drawn since the switch went on -- a host
+ *   count, nothing synchronises; every output may be NULL.
  * msdr_chain_get_bank_post: the switch (0 on a chain that never set it).
  * msdr_chain_get_pll_state: synchronises and returns fil_out, omega2, phzerror of one channel's loop, msdr_syncam_get_state's shape, on Q15
  *   and F32 chains created with MSDR_CHAIN_SYNCAM_PLL, with or without the switch; a chain without a PLL is MSDR_STATUS_ARGUMENT_ERROR.
@@ -913,6 +958,8 @@ int msdr_chain_get_agc(msdr_chain *chain, uint32_t channel, int32_t state[MSDR_A
 int msdr_chain_set_bank_post(msdr_chain *chain, int on);                  /* off (default): PLL / LMS as on a chain without it */
 int msdr_chain_get_bank_post(msdr_chain *chain, int *on);
 int msdr_chain_get_pll_state(msdr_chain *chain, uint32_t channel, float state[3]);
+int msdr_chain_set_spectrum(msdr_chain *chain, void *d_bins, void *d_power, uint32_t every);   /* both NULL = off (default) */
+int msdr_chain_get_spectrum(msdr_chain *chain, void **d_bins, void **d_power, uint32_t *every, uint64_t *drawn);
 void msdr_syncam_constants_rate(double sample_rate, float c[4]);
 int msdr_chain_set_pll_rate(msdr_chain *chain, double sample_rate);       /* 0 (default): the reference's constants */
 int msdr_chain_get_pll_rate(msdr_chain *chain, double *sample_rate);
@@ -1003,6 +1050,8 @@ enum { MSDR_FLAVOUR_COMPLEX_IN = 0x800000u };
 enum { MSDR_FLAVOUR_GAIN = 0x1000000u };
 /* the call ran the bank's PLL or LMS pass behind the per-receiver kernel (msdr_chain_set_bank_post; always beside MSDR_FLAVOUR_NCO_PC). */
 enum { MSDR_FLAVOUR_BANK_POST = 0x2000000u };
+/* the per-receiver spectrum display is on (msdr_chain_set_spectrum; always beside MSDR_FLAVOUR_NCO_PC). */
+enum { MSDR_FLAVOUR_SPECTRUM = 0x4000000u };
 int msdr_chain_get_info(msdr_chain *chain, msdr_chain_info *info);
 /* The wave-stream kernels read the run geometry of a tap table (which chunks of the window each accumulator walks, which runs merge their first
  * and last step) from the table's header -- or, for the geometries the library instantiates, have it as compile-time constants: the same

@@ -11,6 +11,7 @@
 #include "msdr_chain_mfw.hiph"
 #include "msdr_frontend.hiph"
 #include "msdr_spectrum.hiph"
+#include "msdr_bank_spectrum.hiph"
 #include "msdr_chain_q15mf.hiph"
 #include "msdr_fir_f32mf.hiph"
 #include "msdr_fir_f32tr.hiph"
@@ -79,6 +80,7 @@ struct msdr_ctx {
     void *scratch;          // small device buffer reused for per-call host tables (oscillator tables)
     size_t scratch_bytes;
     int16_t *d_fft_tables;  // twiddle / split tables of the 128-point q15 real FFT, created on first use
+    float *d_cfft_tw = nullptr;   // W^t, t = 0 .. 47, as pairs {cos, -sin}: the fp32 64-point complex FFT's twiddles, created on first use
     // msdr_ctx_enable_kernel_timing: HIP events on `stream` around the MAIN kernel of the stage mirrors (msdr_fir_*_process)
     bool timing = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> events;
@@ -162,6 +164,7 @@ extern "C" int msdr_ctx_destroy(msdr_ctx *ctx)
     (void)hipStreamSynchronize(ctx->stream);
     if (ctx->scratch) (void)hipFree(ctx->scratch);
     if (ctx->d_fft_tables) (void)hipFree(ctx->d_fft_tables);
+    if (ctx->d_cfft_tw) (void)hipFree(ctx->d_cfft_tw);
     for (auto &e : ctx->events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     if (ctx->owns_stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
@@ -2291,6 +2294,62 @@ extern "C" int msdr_rfft128_q15_inplace(msdr_ctx *ctx, q15_t *d_src, uint64_t sr
     return rfft128_common(ctx, d_src, src_stride, d_fft_out, d_columns, nfft, true);
 }
 
+// ---- the batched 64-point complex transform (msdr_bank_spectrum.hiph): a receiver's panadapter line ----
+// the twiddles of the arithmetic: twiddleCoef_64_q15, the head of the 128-point real FFT's tables (Q15), or W^t rounded once from double (F32)
+static int cfft64_twiddles(msdr_ctx *ctx, bool f32, const void **tw)
+{
+    if (f32) {
+        if (!ctx->d_cfft_tw) {
+            std::vector<float> h(2 * kCfftTwiddles);
+            for (int t = 0; t < kCfftTwiddles; t++) {
+                const double a = 2.0 * 3.14159265358979323846264338327950288 * (double)t / 64.0;
+                h[2 * t] = (float)std::cos(a); h[2 * t + 1] = (float)-std::sin(a);
+            }
+            if (int rc = upload(ctx, h, &ctx->d_cfft_tw)) return rc;
+        }
+        *tw = ctx->d_cfft_tw;
+        return 0;
+    }
+    if (!ctx->d_fft_tables) {
+        std::vector<int16_t> h(kFftTableShorts);
+        msdr::design::fft128_tables(h.data());
+        if (int rc = upload(ctx, h, &ctx->d_fft_tables)) return rc;
+    }
+    *tw = ctx->d_fft_tables;
+    return 0;
+}
+static int cfft64_common(msdr_ctx *ctx, bool f32, const void *d_pairs, uint64_t stride_pairs, void *d_bins, void *d_power, uint32_t nfft)
+{
+    if (int rc = bind(ctx)) return rc;
+    if (nfft == 0) return 0;
+    if (!d_pairs) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null buffer");
+    if (!d_bins && !d_power) return fail(MSDR_STATUS_ARGUMENT_ERROR, "cfft64: both outputs are NULL; nothing enqueued");
+    if ((reinterpret_cast<uintptr_t>(d_pairs) & (f32 ? 7 : 3)) || (reinterpret_cast<uintptr_t>(d_bins) & 15) || (reinterpret_cast<uintptr_t>(d_power) & 15))
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "cfft64: d_pairs must be %d-byte aligned (whole pairs), d_bins and d_power 16-byte aligned; nothing enqueued", f32 ? 8 : 4);
+    if (stride_pairs < (uint64_t)kCfftBins || stride_pairs > (1ull << 40)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "cfft64: stride_pairs %llu: a transform reads 64 pairs; nothing enqueued", (unsigned long long)stride_pairs);
+    BankSpecParams q;
+    memset(&q, 0, sizeof q);
+    if (int rc = cfft64_twiddles(ctx, f32, &q.tw)) return rc;
+    q.pairs = d_pairs; q.pitch = (long long)stride_pairs; q.tail = nullptr; q.n_new = kCfftBins; q.bins = d_bins; q.power = d_power;
+    q.nfft = (long long)nfft; q.draw = 1;
+    if (launch_bank_cfft64(ctx->stream, f32, q) != hipSuccess) return fail(MSDR_STATUS_HIP_ERROR, "bank_cfft64 kernel launch failed");
+    return 0;
+}
+extern "C" int msdr_cfft64_q15(msdr_ctx *ctx, const q15_t *d_pairs, uint64_t stride_pairs, q15_t *d_bins, uint32_t *d_power, uint32_t nfft)
+{
+    return cfft64_common(ctx, false, d_pairs, stride_pairs, d_bins, d_power, nfft);
+}
+extern "C" int msdr_cfft64_f32(msdr_ctx *ctx, const float *d_pairs, uint64_t stride_pairs, float *d_bins, float *d_power, uint32_t nfft)
+{
+    return cfft64_common(ctx, true, d_pairs, stride_pairs, d_bins, d_power, nfft);
+}
+// 0 dBFS: msdr_meter_dbfs's -- a full-scale real carrier on a bin centre behind a unity-gain channel filter, |X[k]|^2 = A^2 / 4
+extern "C" double msdr_spectrum_dbfs(double power, double full_scale)
+{
+    if (!(power > 0.0)) return -HUGE_VAL;
+    return 10.0 * std::log10(power / (full_scale * full_scale / 4.0));
+}
+
 struct msdr_spectrum {
     msdr_ctx *ctx;
     uint32_t channels;
@@ -2588,6 +2647,14 @@ struct msdr_chain {
     int *d_bank_ident = nullptr, *d_bank_anr = nullptr;
     uint64_t bank_anr_gen = 0;            // the anr_gen d_bank_anr was made for
     const char *post_kernel = "";         // msdr_chain_post_kernel: the PLL kernel of the last call
+    // msdr_chain_set_spectrum (chains with nco_active only): while spec_bins or spec_power is set, one bank_cfft64 launch behind every call
+    // moves d_spec_tail -- [channels][64] pairs, the chain's own, the most recent 64 of every receiver -- over the call's pairs (the caller's
+    // d_iq, else the call_iq buffer above) and, on the calls showSpectrum's counter picks, transforms it into the caller's buffers
+    void *spec_bins = nullptr, *spec_power = nullptr;
+    uint32_t spec_every = 0;              // 0 = 25
+    int spec_counter = 0;                 // spectrumCounter (UI.cpp:122: starts at 0, so the first call draws)
+    uint64_t spec_drawn = 0;
+    void *d_spec_tail = nullptr;
     msdr_chain_info info;
     // optional per-launch timing of the main kernel
     bool timing;
@@ -2605,6 +2672,8 @@ static bool chain_nodes_per_channel(const msdr_chain *c)
 }
 // msdr_chain_set_bank_post in force: the switch is on and the chain is in phase-accumulator mode
 static bool chain_bank(const msdr_chain *c) { return c->bank_post && c->nco_active; }
+// msdr_chain_set_spectrum in force
+static bool chain_spectrum(const msdr_chain *c) { return (c->spec_bins || c->spec_power) && c->nco_active; }
 
 // ---- per-channel FIR coefficients: the host's copy of the table and its way to the device ----
 static void chain_pc_row_from(msdr_chain *c, uint32_t ch, const int16_t *ci, const int16_t *cq)
@@ -2696,7 +2765,7 @@ static void chain_free(msdr_chain *c)
     hipFree(c->d_anr_on);
     for (auto &e : c->events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (auto &o : c->osc_pending) hipFree(o.d_tab);
-    hipFree(c->d_f32_scratch); hipFree(c->d_osc_hist); hipFree(c->d_btiles); hipFree(c->d_pc_taps); hipFree(c->d_pcf_taps); hipFree(c->d_osc_bank); hipFree(c->d_in_row); hipFree(c->d_meter_part); hipFree(c->d_agc);
+    hipFree(c->d_f32_scratch); hipFree(c->d_osc_hist); hipFree(c->d_btiles); hipFree(c->d_pc_taps); hipFree(c->d_pcf_taps); hipFree(c->d_osc_bank); hipFree(c->d_in_row); hipFree(c->d_meter_part); hipFree(c->d_agc); hipFree(c->d_spec_tail);
     hipFree(c->d_nco_bank); hipFree(c->d_nco_tab);
     delete c;
 }
@@ -3722,6 +3791,21 @@ static int chain_bank_pairs(msdr_chain *c, uint64_t n_out)
     c->call_iq = c->d_bank_iq; c->call_iq_pitch = pitch;
     return 0;
 }
+// msdr_chain_set_spectrum, behind everything of the call that can fail: one launch -- the tail becomes the last 64 of (tail ++ the call's n_out
+// pairs), in place, and on a drawing call every row's transform overwrites the caller's buffers
+static int chain_spectrum_run(msdr_chain *c, uint64_t n_out)
+{
+    const bool f32 = c->arith == MSDR_ARITH_F32;
+    const bool draw = --c->spec_counter <= 0;          // showSpectrum: if (--spectrumCounter > 0) return; spectrumCounter = every;
+    BankSpecParams q;
+    memset(&q, 0, sizeof q);
+    if (int rc = cfft64_twiddles(c->ctx, f32, &q.tw)) { c->spec_counter++; return rc; }
+    q.pairs = c->d_iq ? c->d_iq : c->call_iq; q.pitch = (long long)(c->d_iq ? c->iq_pitch : c->call_iq_pitch);
+    q.tail = c->d_spec_tail; q.n_new = (long long)n_out; q.bins = c->spec_bins; q.power = c->spec_power; q.nfft = (long long)c->channels; q.draw = draw ? 1 : 0;
+    if (launch_bank_cfft64(c->ctx->stream, f32, q) != hipSuccess) { c->spec_counter++; return fail(MSDR_STATUS_HIP_ERROR, "bank_cfft64 kernel launch failed"); }
+    if (draw) { c->spec_counter = (int)(c->spec_every ? c->spec_every : 25u); c->spec_drawn++; }
+    return 0;
+}
 // behind the demodulator kernel of an audio call: the PLL on the SYNCAM channels' rows, then (F32; a Q15 chain keeps anr_kernel) the LMS filter
 // in place on its channels' rows -- post_anr_f32_kernel with the identity as its channel table
 static int chain_bank_run(msdr_chain *c, bool pll, bool anr, void *audio, uint64_t n_out)
@@ -4646,7 +4730,8 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     const bool bank_pll = bank && (f32 ? c->f32_pll && chain_summary(c).any_syncam : d.pll_active);
     const bool bank_anr = bank && f32 && chain_summary(c).any_anr;
     c->call_iq = nullptr; c->call_iq_pitch = 0;
-    if (bank_pll) if (int rc = chain_bank_pairs(c, n_out)) return rc;
+    const bool spectrum = chain_spectrum(c);          // msdr_chain_set_spectrum: the pairs are the window's source, in audio and I/Q-only calls alike
+    if (bank_pll || spectrum) if (int rc = chain_bank_pairs(c, n_out)) return rc;
     if (bank && f32) if (int rc = chain_post_states(c)) return rc;
     if (c->dry_run) {            // msdr_chain_graph_create: everything a block-cadence call needs from the host is in place now; make no launch
         const char *why = chain_not_capturable(c, d, n_samples);
@@ -4754,6 +4839,11 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     if (c->nco_active && c->gain_on) {
         hipLaunchKernelGGL(agc_step_kernel, dim3((c->channels + 63) / 64), dim3(64), 0, c->ctx->stream, c->d_agc, (int)c->channels, f32 ? 1 : 0, c->in_scale);
         if (int rc2 = launch_check("agc_step_kernel")) return rc2;
+    }
+    // msdr_chain_set_spectrum: the tail moves over this call's pairs and, on the calls showSpectrum's counter picks (UI.cpp:534-535), is drawn
+    if (spectrum) {
+        if (int rc2 = chain_spectrum_run(c, n_out)) return rc2;
+        if (f32) r.flavour |= MSDR_FLAVOUR_SPECTRUM;
     }
 
     // ---- info
@@ -4936,6 +5026,10 @@ extern "C" int msdr_chain_reset(msdr_chain *c)
     if (c->d_post_pll_state) {
         HIP_TRY(fill_dev(c->ctx, c->d_post_pll_state, 0, (size_t)c->channels * 4 * sizeof(float)));
         if (int rc = anr_init_state(c->ctx, c->channels, c->d_post_anr_state)) return rc;
+    }
+    if (c->d_spec_tail) {          // msdr_chain_set_spectrum: the window and showSpectrum's counter start over (with the other clears, in front of the host's own state)
+        HIP_TRY(fill_dev(c->ctx, c->d_spec_tail, 0, (size_t)c->channels * kCfftBins * (c->arith == MSDR_ARITH_F32 ? 8 : 4)));
+        c->spec_counter = 0;
     }
     if (!c->osc_pending.empty() || c->force_generic) {          // no sample of an earlier oscillator table is left in a cleared history
         HIP_TRY(hipStreamSynchronize(c->ctx->stream));
@@ -5164,6 +5258,8 @@ static int chain_rebuild(msdr_chain *c, const ChainCfgStore &edited, void **stea
     n->bank_post = c->bank_post; n->pll_rate = c->pll_rate; n->post_kernel = c->post_kernel;          // (and msdr_chain_set_bank_post with its buffers)
     std::swap(n->d_bank_iq, c->d_bank_iq); n->bank_iq_bytes = c->bank_iq_bytes;
     std::swap(n->d_bank_ident, c->d_bank_ident); std::swap(n->d_bank_anr, c->d_bank_anr); n->bank_anr_gen = c->bank_anr_gen;
+    n->spec_bins = c->spec_bins; n->spec_power = c->spec_power; n->spec_every = c->spec_every; n->spec_counter = c->spec_counter;          // (and msdr_chain_set_spectrum with its tail)
+    n->spec_drawn = c->spec_drawn; std::swap(n->d_spec_tail, c->d_spec_tail);
     std::swap(*c, *n);
     if (steal_osc) { *steal_osc = n->d_osc; n->d_osc = nullptr; }
     chain_free(n);
@@ -5754,6 +5850,41 @@ extern "C" int msdr_chain_get_iq_out(msdr_chain *c, void **d_iq, uint64_t *pitch
     if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
     if (d_iq) *d_iq = c->d_iq;
     if (pitch) *pitch = c->iq_pitch;
+    return 0;
+}
+
+// A panadapter line per receiver: from the next call on one bank_cfft64 launch behind every call keeps the most recent 64 pairs of each receiver
+// in a tail of the chain's own and, on showSpectrum's cadence, transforms it into the caller's buffers (msdr_bank_spectrum.hiph).  A switch of
+// the host's under msdr_chain_set_decimation's scope rule.  Everything that can fail happens before anything changes.
+extern "C" int msdr_chain_set_spectrum(msdr_chain *c, void *d_bins, void *d_power, uint32_t every)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (int rc = bind(c->ctx)) return rc;
+    if (!c->nco_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "spectrum: only on a chain with the phase-accumulator oscillator (msdr_chain_set_nco_channels); nothing changed");
+    if ((reinterpret_cast<uintptr_t>(d_bins) & 15) || (reinterpret_cast<uintptr_t>(d_power) & 15))
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "spectrum: d_bins and d_power are written in 16-byte slots: they must be 16-byte aligned; nothing changed");
+    if (every > 0x7fffffffu) return fail(MSDR_STATUS_ARGUMENT_ERROR, "spectrum: every %u; nothing changed", every);
+    const bool was_on = c->spec_bins || c->spec_power, on = d_bins || d_power;
+    if (on && !was_on) {          // off -> on: the window, showSpectrum's counter and the count start over
+        const size_t bytes = (size_t)c->channels * kCfftBins * (c->arith == MSDR_ARITH_F32 ? 8 : 4);
+        if (!c->d_spec_tail && hipMalloc(&c->d_spec_tail, bytes) != hipSuccess) {
+            (void)hipGetLastError(); c->d_spec_tail = nullptr;
+            return fail(MSDR_STATUS_OUT_OF_MEMORY, "spectrum: device allocation of %zu bytes for the tail failed; nothing changed", bytes);
+        }
+        HIP_TRY(fill_dev(c->ctx, c->d_spec_tail, 0, bytes));
+        c->spec_counter = 0; c->spec_drawn = 0;
+    }
+    c->spec_bins = d_bins; c->spec_power = d_power; c->spec_every = every;
+    return 0;
+}
+
+extern "C" int msdr_chain_get_spectrum(msdr_chain *c, void **d_bins, void **d_power, uint32_t *every, uint64_t *drawn)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (d_bins) *d_bins = c->spec_bins;
+    if (d_power) *d_power = c->spec_power;
+    if (every) *every = c->spec_every ? c->spec_every : 25u;
+    if (drawn) *drawn = c->spec_drawn;
     return 0;
 }
 

@@ -276,14 +276,15 @@ private:
 class AudioSDRDemodulator : public AudioStream {
 public:
     // (two input ports, as AudioEffectFreqConv has: port 1 is the Q block of a complex stream under setComplexInput, released unread otherwise)
-    AudioSDRDemodulator(void) : AudioStream(2, inputQueueArray), chain(nullptr), num_taps(0), d_meter(nullptr), d_iq(nullptr), d_cx(nullptr), f32(false), in_scale(0.0f) {}
-    ~AudioSDRDemodulator() { if (chain) msdr_chain_destroy(chain); freeMeter(); freeIq(); freeCx(); }
+    AudioSDRDemodulator(void) : AudioStream(2, inputQueueArray), chain(nullptr), num_taps(0), d_meter(nullptr), d_iq(nullptr), d_cx(nullptr), d_spec(nullptr), f32(false), in_scale(0.0f) {}
+    ~AudioSDRDemodulator() { if (chain) msdr_chain_destroy(chain); freeMeter(); freeIq(); freeCx(); freeSpec(); }
     int begin(const msdr_chain_config &cfg)
     {
         if (chain) { msdr_chain_destroy(chain); chain = nullptr; }
         freeMeter();
         freeIq();
         freeCx();
+        freeSpec();
         f32 = cfg.arith == MSDR_ARITH_F32; in_scale = cfg.in_scale != 0.0f ? cfg.in_scale : 1.0f / 32768.0f;
         const bool i16_audio = cfg.arith == MSDR_ARITH_Q15 || (cfg.arith == MSDR_ARITH_F32 && (cfg.flags & MSDR_CHAIN_OUT_I16));
         if (!i16_audio || cfg.channels != AudioGPU.channels()) return MSDR_STATUS_ARGUMENT_ERROR;
@@ -364,6 +365,11 @@ public:
         const uint32_t step = msdr_nco_step(f_hz, fs_hz);
         return msdr_chain_set_nco_channels(chain, channel, 1, &step, nullptr);
     }
+    // the bank's output rate (msdr_chain_set_decimation; after setNco): every tick still consumes AUDIO_BLOCK_SAMPLES per receiver.  NOTE for
+    // what is wired behind this node: with D > 1 the block it transmits is no longer full -- its first channels() * AUDIO_BLOCK_SAMPLES / D
+    // samples are the tick's outputs as [channels()][AUDIO_BLOCK_SAMPLES / D], densely, and the rest of the block is not written.  No node of
+    // this runtime knows D; connect only consumers of the caller's that do (readIq, readLevels, readSpectrum follow D by themselves)
+    int setDecimation(uint32_t D) { return chain ? msdr_chain_set_decimation(chain, D) : MSDR_STATUS_ARGUMENT_ERROR; }
     // one queue_adc feeds the bank (msdr_chain_set_input_rows): receiver c hears row rows[c] of the incoming block.  The block stays
     // [AudioGPU.channels()][AUDIO_BLOCK_SAMPLES]; with a map in force the node reads only its first n_inputs rows (so n_inputs <= channels()).
     // n_inputs == 0: every receiver hears its own row again
@@ -395,11 +401,13 @@ public:
         if (!chain || !d_meter || !dbfs) return MSDR_STATUS_ARGUMENT_ERROR;
         const uint32_t ch = AudioGPU.channels();
         std::vector<uint64_t> raw(ch);
+        uint32_t D = 1;          // (setDecimation: the tick's sums run over AUDIO_BLOCK_SAMPLES / D outputs)
+        if (int rc = msdr_chain_get_decimation(chain, &D)) return rc;
         if (int rc = msdr_memcpy_d2h(AudioGPU.context(), raw.data(), d_meter, (size_t)ch * 8)) return rc;
         for (uint32_t c = 0; c < ch; c++) {
             double s;
             if (f32) memcpy(&s, &raw[c], 8); else s = (double)raw[c];          // (F32 chains write doubles, Q15 chains exact integers)
-            dbfs[c] = msdr_meter_dbfs(s, AUDIO_BLOCK_SAMPLES, f32 ? 32768.0 * (double)in_scale : 32768.0);
+            dbfs[c] = msdr_meter_dbfs(s, AUDIO_BLOCK_SAMPLES / D, f32 ? 32768.0 * (double)in_scale : 32768.0);
         }
         return 0;
     }
@@ -434,6 +442,34 @@ public:
         if (int rc = msdr_memcpy_d2h(AudioGPU.context(), pairs, d_iq, iqBytes())) return rc;
         if (n_out) *n_out = AUDIO_BLOCK_SAMPLES / D;
         return 0;
+    }
+    // the bank's panadapter (msdr_chain_set_spectrum; "Spectrum display optional" on the sketch's to-do list, Minimal-SDR.ino:48-51, once per
+    // receiver): every tick keeps each receiver's most recent 64 pairs behind its channel filter and, on showSpectrum's cadence (the first tick,
+    // then every `every`-th; 0 = 25, UI.cpp:534-535), transforms them; the node owns the device buffer, [channels()][MSDR_SPECTRUM_BINS] powers
+    // in display order (column 32 = the tuned frequency; uint32_t on Q15 chains, float on F32).  After setNco() only.  A repeated
+    // setSpectrum(true, every) changes the cadence alone; setSpectrum(false) switches the display off and frees the buffer.
+    int setSpectrum(bool on, uint32_t every = 0)
+    {
+        if (!chain) return MSDR_STATUS_ARGUMENT_ERROR;
+        if (on) {
+            void *p = d_spec;
+            if (!p) if (int rc = msdr_malloc(AudioGPU.context(), specBytes(), &p)) return rc;
+            if (int rc = msdr_chain_set_spectrum(chain, nullptr, p, every)) { if (!d_spec) msdr_free(AudioGPU.context(), p); return rc; }
+            d_spec = p;
+        } else if (d_spec) {
+            if (int rc = msdr_chain_set_spectrum(chain, nullptr, nullptr, 0)) return rc;
+            freeSpec();
+        }
+        return 0;
+    }
+    // the last spectrum drawn: `power` takes the whole buffer, [channels()][MSDR_SPECTRUM_BINS] entries of 4 bytes (msdr_spectrum_dbfs turns one
+    // into dBFS), *drawn the spectra drawn since setSpectrum(true) -- unchanged since the last look means the buffer is, too.  Copies the
+    // buffer back, so this one waits for the tick's kernels.  drawn may be nullptr.
+    int readSpectrum(void *power, uint64_t *drawn)
+    {
+        if (!chain || !d_spec || !power) return MSDR_STATUS_ARGUMENT_ERROR;
+        if (int rc = msdr_memcpy_d2h(AudioGPU.context(), power, d_spec, specBytes())) return rc;
+        return msdr_chain_get_spectrum(chain, nullptr, nullptr, nullptr, drawn);
     }
     // a complex antenna stream (msdr_chain_set_complex_input; AudioEffectFreqConv's two ports in front of every receiver's filters): while on, port 0
     // carries I and port 1 carries Q of the tick -- a missing Q block counts as zeros -- and the node interleaves them into the block of pairs
@@ -499,6 +535,12 @@ private:
         if (d_iq) msdr_free(AudioGPU.context(), d_iq);
         d_iq = nullptr;
     }
+    size_t specBytes(void) const { return (size_t)AudioGPU.channels() * MSDR_SPECTRUM_BINS * 4; }
+    void freeSpec(void)
+    {
+        if (d_spec) msdr_free(AudioGPU.context(), d_spec);
+        d_spec = nullptr;
+    }
     void freeCx(void)
     {
         if (d_cx) msdr_free(AudioGPU.context(), d_cx);
@@ -520,6 +562,7 @@ private:
     void *d_meter;              // setMeter(true): [channels()] 8-byte sums, the node's own
     void *d_iq;                 // setIqOut(true): [channels()][AUDIO_BLOCK_SAMPLES] pairs {I, Q}, the node's own
     void *d_cx;                 // setComplexInput(true, dir): [channels()][AUDIO_BLOCK_SAMPLES] pairs {I, Q} of the tick, the node's own
+    void *d_spec;               // setSpectrum(true): [channels()][MSDR_SPECTRUM_BINS] powers in display order, the node's own
     std::vector<int16_t> h_i, h_q, h_pairs;          // ... and the host side of the interleave
     bool f32;                   // the chain's arithmetic and int16 -> float scale, for readLevels and the size of a pair
     float in_scale;

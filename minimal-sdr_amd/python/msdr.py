@@ -39,6 +39,8 @@ FLAVOUR_IQ_OUT = 0x400000
 FLAVOUR_COMPLEX_IN = 0x800000
 FLAVOUR_GAIN = 0x1000000
 FLAVOUR_BANK_POST = 0x2000000
+FLAVOUR_SPECTRUM = 0x4000000
+SPECTRUM_BINS = 64
 AGC_STATE_WORDS = 32
 MAX_DECIMATION_Q15, MAX_DECIMATION_F32 = 60, 59
 FE_DCBLOCK, FE_AMP, FE_AGC, FE_ALL = 1, 2, 4, 7
@@ -138,6 +140,11 @@ def load_library(path=None):
                        ("msdr_chain_set_pll_rate", [_p, C.c_double]),
                        ("msdr_chain_get_pll_rate", [_p, _p]),
                        ("msdr_chain_post_kernel", [_p]),
+                       ("msdr_cfft64_q15", [_p, _p, C.c_uint64, _p, _p, C.c_uint32]),
+                       ("msdr_cfft64_f32", [_p, _p, C.c_uint64, _p, _p, C.c_uint32]),
+                       ("msdr_chain_set_spectrum", [_p, _p, _p, C.c_uint32]),
+                       ("msdr_chain_get_spectrum", [_p, _p, _p, _p, _p]),
+                       ("msdr_spectrum_dbfs", [C.c_double, C.c_double]),
                        ("msdr_nco_step", [C.c_double, C.c_double]),
                        ("msdr_nco_table", [_p]),
                        ("msdr_nco_q15", [_p, C.c_size_t, _p, _p]),
@@ -149,6 +156,8 @@ def load_library(path=None):
             _lib.msdr_syncam_constants_rate.restype = None
         if hasattr(_lib, "msdr_meter_dbfs"):
             _lib.msdr_meter_dbfs.restype = C.c_double
+        if hasattr(_lib, "msdr_spectrum_dbfs"):
+            _lib.msdr_spectrum_dbfs.restype = C.c_double
         if hasattr(_lib, "msdr_nco_step"):
             _lib.msdr_nco_step.restype = C.c_uint32
             _lib.msdr_nco_table.restype = None
@@ -328,6 +337,21 @@ class Context:
         ms, n = C.c_double(0), C.c_uint64(0)
         _ck(self.lib.msdr_ctx_get_kernel_time(self.h, C.byref(ms), C.byref(n), int(reset)))
         return ms.value, n.value
+
+    # the batched 64-point complex forward transform: transform f reads 64 pairs {I, Q} at d_pairs + f * stride_pairs pairs and writes
+    # d_bins[f][64] pairs {re, im} (natural bin order) and / or d_power[f][64] (display order: column x = bin (x + 32) & 63); buffers are
+    # DeviceArray / DeviceView / addresses, either output may be None
+    def _cfft64(self, name, d_pairs, stride_pairs, nfft, d_bins, d_power):
+        ptr = lambda b: None if b is None else int(getattr(b, "ptr", b))
+        _ck(getattr(self.lib, name)(self.h, _p(ptr(d_pairs)), C.c_uint64(int(stride_pairs)), _p(ptr(d_bins)), _p(ptr(d_power)), C.c_uint32(int(nfft))))
+
+    def cfft64_q15(self, d_pairs, stride_pairs, nfft, d_bins=None, d_power=None):
+        """arm_cfft_q15 of length 64, forward, with bit reversal, bit-exact; power is the exact uint32 (msdr_cfft64_q15)"""
+        self._cfft64("msdr_cfft64_q15", d_pairs, stride_pairs, nfft, d_bins, d_power)
+
+    def cfft64_f32(self, d_pairs, stride_pairs, nfft, d_bins=None, d_power=None):
+        """(1 / 64) sum_m z[m] exp(-2 pi i k m / 64) in fp32 (msdr_cfft64_f32)"""
+        self._cfft64("msdr_cfft64_f32", d_pairs, stride_pairs, nfft, d_bins, d_power)
 
     def mix_fs4_q15(self, d_x, d_i, d_q, channels, n):
         _ck(self.lib.msdr_mix_fs4_q15(self.h, _p(d_x.ptr), _p(d_i.ptr), _p(d_q.ptr), C.c_uint32(channels), C.c_uint32(n)))
@@ -580,6 +604,12 @@ def _nco_words(what, a, count):
     if t.min() < 0 or t.max() > 0xFFFFFFFF:
         raise ValueError("%s: a word outside uint32" % what)
     return np.ascontiguousarray(t, np.uint32)
+
+
+def spectrum_dbfs(power, full_scale=32768.0):
+    """msdr_spectrum_dbfs: 10 log10(power / (full_scale^2 / 4)) -- an entry of Chain.set_spectrum()'s power rows in dB relative to a full-scale
+    real carrier on a bin centre behind a unity-gain channel filter; -inf for power <= 0.  full_scale: 32768 for Q15, 32768 * in_scale for F32."""
+    return float(load_library().msdr_spectrum_dbfs(float(power), float(full_scale)))
 
 
 def meter_dbfs(sum_sq, n_out, full_scale=32768.0):
@@ -976,6 +1006,23 @@ class Chain(_Instance):
         p = _p()
         _ck(self.ctx.lib.msdr_chain_get_meter(self.h, C.byref(p)))
         return p.value
+
+    def set_spectrum(self, d_bins, d_power, every=0):
+        """A panadapter line per receiver: while on, every process() keeps each receiver's most recent 64 pairs behind its channel filter (at
+        fs / D) and, on showSpectrum's cadence (the first call, then every `every`-th; 0 = 25), overwrites d_bins[channels][64] pairs
+        {re, im} (int16 / float32, natural bin order) and / or d_power[channels][64] (uint32 / float32, column 32 = the tuned frequency) with
+        their 64-point transform -- 16-byte aligned device buffers (DeviceArray / DeviceView / address); one None: only the other is written,
+        both None: off.  Chains with set_nco_channels only (msdr_chain_set_spectrum)."""
+        ptr = lambda b: None if b is None else int(getattr(b, "ptr", b))
+        _ck(self.ctx.lib.msdr_chain_set_spectrum(self.h, _p(ptr(d_bins)), _p(ptr(d_power)), C.c_uint32(int(every))))
+        self._spectrum = (d_bins, d_power)          # (the buffers stay the caller's; this keeps DeviceArrays alive while the kernel writes them)
+
+    def spectrum(self):
+        """(address of the bins buffer or None, address of the power buffer or None, every, spectra drawn since the switch went on)
+        (msdr_chain_get_spectrum)"""
+        b, p, every, drawn = _p(), _p(), C.c_uint32(0), C.c_uint64(0)
+        _ck(self.ctx.lib.msdr_chain_get_spectrum(self.h, C.byref(b), C.byref(p), C.byref(every), C.byref(drawn)))
+        return b.value, p.value, every.value, drawn.value
 
     def set_iq_out(self, d_iq, pitch=0):
         """Baseband I/Q output: from the next process() on every call overwrites pairs 0 .. n_out - 1 of every row of d_iq[channels][pitch] -- a
