@@ -750,6 +750,35 @@ int msdr_chain_set_mode(msdr_chain *chain, uint32_t channel, int32_t mode, int32
  *   mode; msdr_chain_set_block_kernel[_q15] is accepted and such calls run the unfused launches.  The setting survives everything the
  *   oscillator bank survives: msdr_chain_reset and init_fir, the tap, node, cascade and NCO setters, msdr_chain_set_input_rows.
  * msdr_chain_get_decimation: the factor in force (1 on every chain that never set one).
+ * msdr_chain_set_prefilter / msdr_chain_set_prefilter_f32: two-stage decimation, the way every down-converter reaches a narrow channel from
+ *   a wideband input.  A chain-wide prefilter -- ONE real row taps[0 .. num_taps) in CMSIS order, the same for the I and the Q stream of
+ *   every receiver -- decimates the mixed stream by D1, and the receiver's own channel pair runs on those intermediates at fs / D1 and
+ *   decimates by D2 = msdr_chain_set_decimation's factor (which may be 1):
+ *       u[j] = FIR_p over the mixed stream, taken at input sample j * D1 + D1 - 1 (arm_fir_decimate's convention)
+ *              Q15: arm_fir_fast_q15's arithmetic (wrapping 32-bit accumulator, >> 15, saturated to int16); F32: arm_fir_f32's
+ *       output m = the channel pair over u, taken at intermediate sample m * D2 + D2 - 1 -> demodulator, as the one-stage chain has it
+ *   Everything behind the accumulators (meter, pairs, gain, demodulator, PLL / LMS of msdr_chain_set_bank_post, spectrum tail, nodes,
+ *   cascade, int16 conversion) sees n_out = n_samples / (D1 * D2) samples at the rate fs / (D1 * D2); n_samples % (D1 * D2) != 0 is
+ *   MSDR_STATUS_LENGTH_ERROR, nothing enqueued, no state moved.  The caller designs the channel taps for fs / D1 and node and cascade
+ *   filters for fs / (D1 * D2).
+ *   NO NEW STATE: the chain keeps raw IF history only, (np2 - 1) * D1 + np1 - 1 samples of it (np: the tap counts rounded up to 8 (Q15) /
+ *   4 (F32)); the intermediates that a tile or a call shares with the one before it are recomputed from raw samples, so a Q15 chain is
+ *   bit-exact however the stream is cut into calls.  For that reason the prefilter is set, changed or turned off (D1 == 1 or
+ *   num_taps == 0) only over a CLEAR FIR history -- before the first msdr_chain_process, or directly after msdr_chain_reset /
+ *   msdr_chain_init_fir: the rule of the first msdr_chain_set_nco_channels; at any other time ARGUMENT_ERROR, nothing changed.  The live
+ *   setters (per-channel taps, NCO generations -- now over the longer history --, msdr_chain_set_decimation, mode, nodes, cascade, gain,
+ *   meter, I/Q output, spectrum, bank post) keep working as they do at D > 1; a live change of the channel taps is the in-place pCoeffs
+ *   rewrite of a stage-2 CMSIS instance, whose state is those same intermediates.
+ *   Values: D1 in {2, 4, 8, 16, 32}; Q15 tap counts even (arm_fir_init_q15 refuses odd ones).  ARGUMENT_ERROR, nothing changed: a chain
+ *   not in phase-accumulator mode, the other arithmetic's setter, a NULL row, non-finite taps, a history that is not clear, complex input
+ *   on (msdr_chain_set_complex_input(on) while a prefilter is set is refused too), and a (D1, num_taps, chain taps, D2) whose smallest
+ *   geometry -- one wave, one channel, 128 outputs: the window 128 D2 + np2 intermediates, a stage-1 chunk of 64 max(1, 16 / D1) D1 + np1
+ *   mixed samples, both per stream, the tap rows, the 4 KB sine table and the prefilter row -- does not fit 64 KB of LDS;
+ *   msdr_chain_set_decimation checks the same rule while a prefilter is set.
+ *   Reporting: msdr_chain_get_info().kernel begins chain_q15pcn2_kernel / chain_f32pcn2_kernel, `tile` is the launch's tile in FINAL
+ *   outputs, and on fp32 chains flavour carries MSDR_FLAVOUR_PREFILTER beside DECIMATED, NCO_PC and TAPS_PC.  Graphs stay refused;
+ *   msdr_chain_set_block_kernel[_q15] is accepted and such calls run the unfused launches.  The setting survives what the decimation survives.
+ * msdr_chain_get_prefilter: D1 and num_taps in force (1 and 0 while off); either pointer may be NULL.
  * msdr_chain_set_meter: the S-meter of the bank (the reference's to-do list begins with it, Minimal-SDR.ino:48-50) -- the power of every
  *   channel behind its channel filter and before its demodulator, measured inside the per-receiver kernels at no extra pass over memory.
  *   For a call of msdr_chain_process with n_out = n_samples / D outputs per channel
@@ -942,6 +971,9 @@ int msdr_chain_get_nco(msdr_chain *chain, uint32_t channel, uint32_t *step, uint
 enum { MSDR_MAX_DECIMATION_Q15 = 60, MSDR_MAX_DECIMATION_F32 = 59 };
 int msdr_chain_set_decimation(msdr_chain *chain, uint32_t D);   /* 1 = off (default) */
 int msdr_chain_get_decimation(msdr_chain *chain, uint32_t *D);
+int msdr_chain_set_prefilter(msdr_chain *chain, uint32_t D1, uint32_t num_taps, const int16_t *taps);     /* Q15; D1 == 1 or num_taps == 0: off (default) */
+int msdr_chain_set_prefilter_f32(msdr_chain *chain, uint32_t D1, uint32_t num_taps, const float *taps);   /* F32 */
+int msdr_chain_get_prefilter(msdr_chain *chain, uint32_t *D1, uint32_t *num_taps);                         /* either may be NULL */
 int msdr_chain_set_meter(msdr_chain *chain, void *d_meter);   /* NULL = off (default) */
 int msdr_chain_get_meter(msdr_chain *chain, void **d_meter);
 double msdr_meter_dbfs(double sum_sq, uint64_t n_out, double full_scale);
@@ -1052,6 +1084,9 @@ enum { MSDR_FLAVOUR_GAIN = 0x1000000u };
 enum { MSDR_FLAVOUR_BANK_POST = 0x2000000u };
 /* the per-receiver spectrum display is on (msdr_chain_set_spectrum; always beside MSDR_FLAVOUR_NCO_PC). */
 enum { MSDR_FLAVOUR_SPECTRUM = 0x4000000u };
+/* the demodulator kernel ran a chain-wide prefilter in front of the channel pair -- chain_f32pcn2_kernel, msdr_chain_set_prefilter_f32
+ * (always beside MSDR_FLAVOUR_DECIMATED and MSDR_FLAVOUR_NCO_PC). */
+enum { MSDR_FLAVOUR_PREFILTER = 0x8000000u };
 int msdr_chain_get_info(msdr_chain *chain, msdr_chain_info *info);
 /* The wave-stream kernels read the run geometry of a tap table (which chunks of the window each accumulator walks, which runs merge their first
  * and last step) from the table's header -- or, for the geometries the library instantiates, have it as compile-time constants: the same

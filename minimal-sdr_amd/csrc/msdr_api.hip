@@ -2597,6 +2597,14 @@ struct msdr_chain {
     // (msdr_chain_decpc.hiph) -- d_audio is [channels][n_samples / D] and every pass behind the demodulator sees n_samples / D samples.  Host
     // state alone: the history is raw IF at the full rate, node and cascade states carry on at the new rate.
     uint32_t decim = 1;
+    // msdr_chain_set_prefilter[_f32]: while pre_d1 > 1 chain_q15pcn2_kernel / chain_f32pcn2_kernel run (msdr_chain_pre.hiph) -- the row d_pre
+    // of pre_np taps (pre_ntaps front-padded with zeros) decimates the mixed stream by pre_d1 in front of the channel pair, which decimates by
+    // decim -- and every pass behind the demodulator sees n_samples / (pre_d1 * decim) samples.  No state beyond the raw history, which the
+    // setter grows to chain_pre_hist_len (and which stays that long when the prefilter is turned off: the one-stage kernels read its newest end).
+    uint32_t pre_d1 = 1, pre_ntaps = 0;
+    uint32_t pre_hist = 0;                // the longest history a prefilter of this chain asked for (0: never one): every rebuild keeps it
+    int pre_np = 0;
+    void *d_pre = nullptr;                // [pre_np] int16 (Q15) / float (F32)
     // msdr_chain_set_block_kernel (F32): a block-cadence call of the chain in per-channel mode runs chain_f32pcb_kernel (msdr_chain_f32pcb.hiph) --
     // demodulator, CMSIS-order cascade, int16 conversion and the next history in ONE launch -- where msdr_chain_process finds the conditions met;
     // every other call runs the unfused launches over the same history, table position and cascade state.  Off by default.
@@ -2700,6 +2708,12 @@ static const char kPcfnKernelName[] = "chain_f32pcn_kernel (per-channel taps, ph
 // ... and of the same chains under msdr_chain_set_decimation
 static const char kPcndKernelName[] = "chain_q15pcnd_kernel (per-channel taps, NCO, decimator)";
 static const char kPcfndKernelName[] = "chain_f32pcnd_kernel (per-channel taps, NCO, decimator)";
+// ... and behind a chain-wide prefilter (msdr_chain_set_prefilter)
+static const char kPcn2KernelName[] = "chain_q15pcn2_kernel (per-channel taps, NCO, prefilter, decimator)";
+static const char kPcfn2KernelName[] = "chain_f32pcn2_kernel (per-channel taps, NCO, prefilter, decimator)";
+// msdr_chain_set_prefilter in force, and the factor between the input rate and the rate of everything behind the demodulator kernel
+static bool chain_pre(const msdr_chain *c) { return c->nco_active && c->pre_d1 > 1; }
+static uint64_t chain_rate_div(const msdr_chain *c) { return (uint64_t)c->decim * (chain_pre(c) ? c->pre_d1 : 1u); }
 static void chain_pcf_row_from(msdr_chain *c, uint32_t ch, const float *ci, const float *cq)
 {
     float *row = c->h_pcf_taps.data() + (size_t)ch * 2 * c->pc_np;
@@ -2766,7 +2780,7 @@ static void chain_free(msdr_chain *c)
     for (auto &e : c->events) { hipEventDestroy(e.first); hipEventDestroy(e.second); }
     for (auto &o : c->osc_pending) hipFree(o.d_tab);
     hipFree(c->d_f32_scratch); hipFree(c->d_osc_hist); hipFree(c->d_btiles); hipFree(c->d_pc_taps); hipFree(c->d_pcf_taps); hipFree(c->d_osc_bank); hipFree(c->d_in_row); hipFree(c->d_meter_part); hipFree(c->d_agc); hipFree(c->d_spec_tail);
-    hipFree(c->d_nco_bank); hipFree(c->d_nco_tab);
+    hipFree(c->d_nco_bank); hipFree(c->d_nco_tab); hipFree(c->d_pre);
     delete c;
 }
 
@@ -4266,7 +4280,7 @@ static int chain_prepare(msdr_chain *c, ChainDecision &d, const ChainTiles &t, c
     }
     if (d.i16 == kI16InKernel && path_mfw(d.path)) p.dbg |= kChainOutI16;       // (chain_f32pcb_kernel: PcbParams.out_i16)
     if (d.i16 == kI16ViaScratch) {
-        if (int rc = grow_device(c->ctx, &c->d_f32_scratch, &c->f32_scratch_floats, (size_t)c->channels * (n_samples / c->decim))) return rc;      // (the audio: n / D per channel)
+        if (int rc = grow_device(c->ctx, &c->d_f32_scratch, &c->f32_scratch_floats, (size_t)c->channels * (n_samples / chain_rate_div(c)))) return rc;      // (the audio: n / D per channel)
         p.out = c->d_f32_scratch;                                    // where the fp32 passes of this call read and write the audio
     }
     p.mf_tab = c->d_mf_tab; p.mf_stride = c->mf_stride; p.mf_halo = c->mf_halo; p.mf_bsteps = c->mf_bsteps; p.mf_xsteps = c->mf_xsteps; p.bq_mf = c->d_bq_mf; p.bq_mf32 = c->d_bq_mf32;
@@ -4386,6 +4400,16 @@ static int chain_launch_f32pc(msdr_chain *c, const ChainDecision &, const ChainP
     pc_params_meter(q, c);
     pc_params_iq(q, c);
     PcLaunch geo;
+    if (chain_pre(c)) {          // msdr_chain_set_prefilter_f32: p.out is [channels][n / (D1 D2)]
+        Pcfn2Params q2;
+        memset(&q2, 0, sizeof q2);
+        static_cast<PcfnParams &>(q2) = q;
+        q2.sin_tab = c->d_nco_tab; q2.t0 = (unsigned)c->nco_T; q2.dec = (int)c->decim; q2.agc = c->gain_on ? c->d_agc : nullptr;
+        q2.pre_taps = c->d_pre; q2.pre_np = c->pre_np; q2.pre_dec = (int)c->pre_d1;
+        if (launch_chain_f32pcn2(c->ctx->stream, c->ctx->num_cus, (int)c->time_segments, q2, &geo) != hipSuccess)
+            return fail(MSDR_STATUS_HIP_ERROR, "chain_f32pcn2_kernel launch failed");
+        r.kname = kPcfn2KernelName; r.flavour |= MSDR_FLAVOUR_NCO_PC | MSDR_FLAVOUR_DECIMATED | MSDR_FLAVOUR_PREFILTER;
+    } else
     if (c->nco_active && c->decim > 1) {          // msdr_chain_set_decimation: p.out is [channels][n / D]
         PcfndCxParams qd;          // (msdr_chain_set_complex_input: the twin's block is the real kernel's and the direction)
         static_cast<PcfnParams &>(qd) = q;
@@ -4605,6 +4629,16 @@ static int chain_launch_q15pc(msdr_chain *c, const ChainDecision &, const ChainP
     pc_params_meter(q, c);
     pc_params_iq(q, c);
     PcLaunch geo;
+    if (chain_pre(c)) {          // msdr_chain_set_prefilter: p.out is [channels][n / (D1 D2)]
+        Pcn2Params q2;
+        memset(&q2, 0, sizeof q2);
+        static_cast<PcnParams &>(q2) = q;
+        q2.sin_tab = c->d_nco_tab; q2.t0 = (unsigned)c->nco_T; q2.dec = (int)c->decim; q2.agc = c->gain_on ? c->d_agc : nullptr;
+        q2.pre_taps = c->d_pre; q2.pre_np = c->pre_np; q2.pre_dec = (int)c->pre_d1;
+        if (launch_chain_q15pcn2(c->ctx->stream, c->ctx->num_cus, q2, &geo) != hipSuccess)
+            return fail(MSDR_STATUS_HIP_ERROR, "chain_q15pcn2_kernel launch failed");
+        r.kname = kPcn2KernelName;
+    } else
     if (c->nco_active && c->decim > 1) {          // msdr_chain_set_decimation: p.out is [channels][n / D]
         PcndCxParams qd;          // (msdr_chain_set_complex_input: the twin's block is the real kernel's and the direction)
         static_cast<PcnParams &>(qd) = q;
@@ -4710,7 +4744,10 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     // demodulator kernel sees n_out samples
     if (n_samples % c->decim)
         return fail(MSDR_STATUS_LENGTH_ERROR, "decimation %u: n_samples (%llu) must be a multiple of it; nothing enqueued", c->decim, (unsigned long long)n_samples);
-    const uint64_t n_out = n_samples / c->decim;
+    // msdr_chain_set_prefilter: whole groups of D1 * D2 samples, for the same reason
+    if (n_samples % chain_rate_div(c))
+        return fail(MSDR_STATUS_LENGTH_ERROR, "prefilter by %u and decimation %u: n_samples (%llu) must be a multiple of their product; nothing enqueued", c->pre_d1, c->decim, (unsigned long long)n_samples);
+    const uint64_t n_out = n_samples / chain_rate_div(c);
     if (!f32 && c->nnodes && (n_out & 1u))
         return fail(MSDR_STATUS_LENGTH_ERROR, "AudioFilterBiquad processes sample pairs: n_samples / decimation (%llu) must be even; nothing enqueued", (unsigned long long)n_out);
     if (c->d_iq && n_out > c->iq_pitch)
@@ -5181,6 +5218,19 @@ __global__ void hist_resize_kernel(const T *__restrict__ src, T *__restrict__ ds
     }
 }
 
+// msdr_chain_set_prefilter: a CLEAR history (all zeros) made hist_len samples long -- new zeroed buffers, nothing to carry
+static int chain_hist_grow(msdr_chain *c, uint32_t hist_len)
+{
+    int16_t *h0 = nullptr, *h1 = nullptr;
+    int rc = dzalloc(c->ctx, (size_t)2 * c->channels * hist_len, &h0);
+    if (!rc) rc = dzalloc(c->ctx, (size_t)2 * c->channels * hist_len, &h1);
+    if (rc) { hipFree(h0); hipFree(h1); return rc; }
+    HIP_TRY(hipStreamSynchronize(c->ctx->stream));          // (launches that read the old buffers)
+    hipFree(c->d_hist[0]); hipFree(c->d_hist[1]);
+    c->d_hist[0] = h0; c->d_hist[1] = h1; c->cur = 0; c->hist_len = hist_len;
+    return 0;
+}
+
 // extra_floor_d / extra_floor_sig: what the caller KNOWS it will hand the rebuilt chain (numerator history / section states, in units of
 // in_scale): msdr_chain_set_biquad_coeffs converts the running cascade's state into the new cascade's basis, and neither chain's own bounds
 // say how large that comes out (tests/debug/fuzz_live.py seed 5342 case 38296: a resonant cascade that ran in CMSIS order behind the kernel,
@@ -5205,6 +5255,10 @@ static int chain_rebuild(msdr_chain *c, const ChainCfgStore &edited, void **stea
     if (n->channels != c->channels || n->osc_len != c->osc_len || n->ntaps != c->ntaps) {
         chain_free(n);
         return fail(MSDR_STATUS_SIZE_MISMATCH, "internal: a live update changed the chain's geometry");
+    }
+    // msdr_chain_set_prefilter grew the raw history beyond what the configuration asks for: the rebuilt chain keeps that length
+    if (c->nco_active && c->pre_hist && n->hist_len < c->hist_len) {
+        if (int rc2 = chain_hist_grow(n, c->hist_len)) { chain_free(n); return rc2; }
     }
     // FIR history and table position
     if (n->hist_len == c->hist_len) { std::swap(n->d_hist[0], c->d_hist[0]); std::swap(n->d_hist[1], c->d_hist[1]); n->cur = c->cur; }
@@ -5252,6 +5306,7 @@ static int chain_rebuild(msdr_chain *c, const ChainCfgStore &edited, void **stea
     n->nco_active = c->nco_active; std::swap(n->d_nco_bank, c->d_nco_bank); std::swap(n->d_nco_tab, c->d_nco_tab);
     n->h_nco_base.swap(c->h_nco_base); n->h_nco_step.swap(c->h_nco_step); n->nco_T = c->nco_T; n->hist_clear = c->hist_clear;
     n->decim = c->decim;          // (msdr_chain_set_decimation holds through every rebuild)
+    n->pre_d1 = c->pre_d1; n->pre_ntaps = c->pre_ntaps; n->pre_np = c->pre_np; n->pre_hist = c->pre_hist; std::swap(n->d_pre, c->d_pre);          // (and msdr_chain_set_prefilter with its row)
     n->d_iq = c->d_iq; n->iq_pitch = c->iq_pitch;          // (and so does msdr_chain_set_iq_out)
     n->cx_on = c->cx_on; n->cx_dir = c->cx_dir;          // (and msdr_chain_set_complex_input: the history above went over as pairs)
     n->gain_on = c->gain_on; std::swap(n->d_agc, c->d_agc);          // (and msdr_chain_set_gain with every receiver's record)
@@ -5765,6 +5820,8 @@ extern "C" int msdr_chain_set_decimation(msdr_chain *c, uint32_t D)
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "decimation %u: 1 .. %d (the window of one wave with one channel must fit 64 KB of LDS beside the sine table); nothing changed", D, chain_dec_max(f32));
     if (D > 1 && !chain_dec_fits(f32, c->pc_np, (int)D))
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "decimation %u: beside its window the kernel holds filters of up to %d taps (this chain has %u); nothing changed", D, chain_dec_max_taps(f32, (int)D), c->ntaps);
+    if (chain_pre(c) && !chain_pre_fits(f32, c->pre_np, (int)c->pre_d1, c->pc_np, (int)D))          // msdr_chain_set_prefilter: the two-stage kernel's rule
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "decimation %u behind the prefilter (D1 %u, %u taps) with %u channel taps: the smallest geometry does not fit 64 KB of LDS; nothing changed", D, c->pre_d1, c->pre_ntaps, c->ntaps);
     if (!f32 && D > 1 && !c->bank_post) {          // (fp32 chains with the phase-accumulator oscillator have neither; msdr_chain_set_bank_post: both run at fs / D)
         if (c->pll) return fail(MSDR_STATUS_ARGUMENT_ERROR, "decimation: not on a chain created with MSDR_CHAIN_SYNCAM_PLL (the PLL demodulator runs at the full rate); nothing changed");
         if (chain_anr_active(c)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "decimation: not while an LMS channel is on (msdr_chain_set_anr); nothing changed");
@@ -5827,6 +5884,59 @@ extern "C" int msdr_chain_get_decimation(msdr_chain *c, uint32_t *D)
 {
     if (!c || !D) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
     *D = c->decim;
+    return 0;
+}
+
+// Two-stage decimation: a chain-wide prefilter in front of every receiver's channel pair (msdr_chain_pre.hiph).  The chain keeps raw IF history
+// only and a tile recomputes the intermediates it shares with the one before it, so the row is set, changed or turned off over a CLEAR history
+// alone (the rule of the first msdr_chain_set_nco_channels), where the history is grown to what the two stages reach back.  Everything that can
+// fail happens before anything changes.
+template <typename T>
+static int chain_set_prefilter(msdr_chain *c, bool f32_call, uint32_t D1, uint32_t num_taps, const T *taps)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (int rc = bind(c->ctx)) return rc;
+    if (!c->nco_active) return fail(MSDR_STATUS_ARGUMENT_ERROR, "prefilter: only on a chain with the phase-accumulator oscillator (msdr_chain_set_nco_channels); nothing changed");
+    const bool f32 = c->arith == MSDR_ARITH_F32;
+    if (f32 != f32_call) return fail(MSDR_STATUS_ARGUMENT_ERROR, "prefilter: %s on a %s chain; nothing changed", f32_call ? "msdr_chain_set_prefilter_f32" : "msdr_chain_set_prefilter", f32 ? "F32" : "Q15");
+    const bool off = D1 == 1 || num_taps == 0;
+    if (off && c->pre_d1 == 1) return 0;
+    if (!c->hist_clear)
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "prefilter: the row is set, changed or turned off over a clear FIR history only (before the first msdr_chain_process, or directly after msdr_chain_reset / msdr_chain_init_fir); nothing changed");
+    if (off) { c->pre_d1 = 1; c->pre_ntaps = 0; c->pre_np = 0; return 0; }
+    if (D1 != 2 && D1 != 4 && D1 != 8 && D1 != 16 && D1 != 32) return fail(MSDR_STATUS_ARGUMENT_ERROR, "prefilter: D1 %u: 2, 4, 8, 16 or 32 (1: off); nothing changed", D1);
+    if (!taps) return fail(MSDR_STATUS_ARGUMENT_ERROR, "prefilter: null taps; nothing changed");
+    if (num_taps > 65536u) return fail(MSDR_STATUS_ARGUMENT_ERROR, "prefilter: %u taps; nothing changed", num_taps);
+    if (!f32 && (num_taps & 1u)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "prefilter: %u taps: arm_fir_init_q15 takes even counts only; nothing changed", num_taps);
+    if constexpr (std::is_floating_point<T>::value)
+        for (uint32_t k = 0; k < num_taps; k++) if (!std::isfinite(taps[k])) return fail(MSDR_STATUS_ARGUMENT_ERROR, "prefilter: tap %u is not finite; nothing changed", k);
+    if (c->cx_on) return fail(MSDR_STATUS_ARGUMENT_ERROR, "prefilter: not on a chain with complex input (msdr_chain_set_complex_input); nothing changed");
+    if (!f32 && !c->bank_post) {          // (msdr_chain_set_decimation's rule: both run at the full rate unless msdr_chain_set_bank_post is on)
+        if (c->pll) return fail(MSDR_STATUS_ARGUMENT_ERROR, "prefilter: not on a chain created with MSDR_CHAIN_SYNCAM_PLL (the PLL demodulator runs at the full rate); nothing changed");
+        if (chain_anr_active(c)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "prefilter: not while an LMS channel is on (msdr_chain_set_anr); nothing changed");
+    }
+    const int q = f32 ? 4 : 8, np1 = (int)((num_taps + q - 1) / q * q);
+    if (!chain_pre_fits(f32, np1, (int)D1, c->pc_np, (int)c->decim))
+        return fail(MSDR_STATUS_ARGUMENT_ERROR, "prefilter: D1 %u with %u taps in front of %u channel taps and decimation %u: the smallest geometry does not fit 64 KB of LDS; nothing changed", D1, num_taps, c->ntaps, c->decim);
+    std::vector<T> row((size_t)np1, (T)0);          // zero taps in FRONT: they meet older samples
+    memcpy(row.data() + (np1 - (int)num_taps), taps, num_taps * sizeof(T));
+    T *d_row = nullptr;
+    if (int rc = upload(c->ctx, row, &d_row)) return rc;
+    const uint32_t need = (uint32_t)chain_pre_hist_len(np1, (int)D1, c->pc_np);
+    if (need > c->hist_len) { if (int rc = chain_hist_grow(c, need)) { hipFree(d_row); return rc; } }
+    c->pre_hist = std::max(c->pre_hist, c->hist_len);
+    HIP_TRY(hipStreamSynchronize(c->ctx->stream));          // (launches that read the old row)
+    hipFree(c->d_pre);
+    c->d_pre = d_row; c->pre_d1 = D1; c->pre_ntaps = num_taps; c->pre_np = np1;
+    return 0;
+}
+extern "C" int msdr_chain_set_prefilter(msdr_chain *c, uint32_t D1, uint32_t num_taps, const int16_t *taps) { return chain_set_prefilter(c, false, D1, num_taps, taps); }
+extern "C" int msdr_chain_set_prefilter_f32(msdr_chain *c, uint32_t D1, uint32_t num_taps, const float *taps) { return chain_set_prefilter(c, true, D1, num_taps, taps); }
+extern "C" int msdr_chain_get_prefilter(msdr_chain *c, uint32_t *D1, uint32_t *num_taps)
+{
+    if (!c) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null chain");
+    if (D1) *D1 = c->pre_d1;
+    if (num_taps) *num_taps = c->pre_ntaps;
     return 0;
 }
 
@@ -5900,6 +6010,7 @@ extern "C" int msdr_chain_set_complex_input(msdr_chain *c, int on, int dir)
     const bool want = on != 0;
     const int want_dir = want ? dir : 0;
     if (want == c->cx_on && want_dir == c->cx_dir) return 0;
+    if (want && chain_pre(c)) return fail(MSDR_STATUS_ARGUMENT_ERROR, "complex input: not while a prefilter is set (msdr_chain_set_prefilter: the two-stage kernels take real input); nothing changed");
     if (!c->hist_clear)
         return fail(MSDR_STATUS_ARGUMENT_ERROR, "complex input: the switch needs a clear FIR history (before the first msdr_chain_process, or directly after msdr_chain_reset / msdr_chain_init_fir); nothing changed");
     c->cx_on = want; c->cx_dir = want_dir;
@@ -6180,7 +6291,7 @@ extern "C" int msdr_chain_set_anr(msdr_chain *c, const int32_t *anr_on, int32_t 
         c->anr_gen++;
         return 0;
     }
-    if (c->decim > 1 && !c->bank_post) {          // msdr_chain_set_decimation: the LMS filter belongs to the full rate (msdr_chain_set_bank_post: to fs / D)
+    if (chain_rate_div(c) > 1 && !c->bank_post) {          // msdr_chain_set_decimation / set_prefilter: the LMS filter belongs to the full rate (msdr_chain_set_bank_post: to fs / D)
         bool any = anr_on ? false : anr_on_all > 0;
         if (anr_on) for (uint32_t ch = 0; ch < c->channels; ch++) any = any || anr_on[ch] > 0;
         if (any) return fail(MSDR_STATUS_ARGUMENT_ERROR, "this chain decimates (msdr_chain_set_decimation): no LMS channels; nothing changed");

@@ -102,6 +102,16 @@ hipError_t launch_chain_q15pcn_gain(hipStream_t stream, int num_cus, bool cx, Pc
 hipError_t launch_chain_f32pcn_gain(hipStream_t stream, int num_cus, int time_segments, bool cx, PcfnGainParams p, PcLaunch *geo);
 hipError_t launch_chain_q15pcnd_gain(hipStream_t stream, int num_cus, bool cx, PcndGainParams p, PcLaunch *geo);
 hipError_t launch_chain_f32pcnd_gain(hipStream_t stream, int num_cus, int time_segments, bool cx, PcfndGainParams p, PcLaunch *geo);
+// ---- msdr_chain_pre.hip ----
+// chain_q15pcn2_kernel<CPW, AL> / chain_f32pcn2_kernel<CPW, AL> and their *_full twins (msdr_chain_pre.hiph): the decimating kernels with a
+// chain-wide prefilter (p.pre_taps, p.pre_np, p.pre_dec) in front of the channel pair, which decimates by p.dec >= 1; p.n a multiple of
+// p.pre_dec * p.dec.  The launcher fills p.nout, p.opl, p.pre_chunk, p.nseg, p.seg_len and p.nw from pre_geometry (msdr_prepc_geometry.h) and
+// picks the full twin where p.meter, p.iq or p.agc is set; geo->tile is in final outputs.  chain_pre_fits: whether the smallest geometry of
+// (np1, D1, np2, D2) -- padded tap counts -- fits 64 KB of LDS; chain_pre_hist_len: the raw history such a chain carries.
+bool chain_pre_fits(bool f32, int np1, int D1, int np2, int D2);
+int chain_pre_hist_len(int np1, int D1, int np2);
+hipError_t launch_chain_q15pcn2(hipStream_t stream, int num_cus, Pcn2Params p, PcLaunch *geo);
+hipError_t launch_chain_f32pcn2(hipStream_t stream, int num_cus, int time_segments, Pcfn2Params p, PcLaunch *geo);
 // ---- msdr_chain_meter.hip ----
 // meter_reduce_kernel<T> (msdr_chain_meter.hiph): d_meter[ch] = the sum of part[ch][0 .. nseg) in that order -- the S-meter of a call that the
 // per-receiver kernels above ran in nseg > 1 time segments (their launchers call it; uint64_t sums for Q15, double for F32)

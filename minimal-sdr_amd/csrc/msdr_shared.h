@@ -226,6 +226,19 @@ typedef GainParams<PcfnCxParams> PcfnGainParams;
 typedef GainParams<PcndCxParams> PcndGainParams;
 typedef GainParams<PcfndCxParams> PcfndGainParams;
 
+// chain_q15pcn2_kernel / chain_f32pcn2_kernel (msdr_chain_pre.hiph; msdr_chain_set_prefilter): the decimating gain twin's block -- a null
+// meter / iq / agc skips that part, cx_dir is not read -- with the chain-wide prefilter in front.  `dec` is the SECOND factor (>= 1), nout
+// n / (pre_dec * dec), and the history is pre_hist_len samples of raw IF (msdr_prepc_geometry.h).  A block of its own again.
+template <typename P>
+struct PreParams : P {
+    const void *pre_taps;      // [pre_np] the prefilter row in CMSIS order, front-padded with zeros: int16 (Q15) / float (F32)
+    int pre_np;                // a multiple of 8 (Q15) / 4 (F32)
+    int pre_dec;               // D1: 2, 4, 8, 16 or 32
+    int pre_chunk;             // intermediates per stage-1 chunk (the launcher's: pre_chunk(D1, channels per wave))
+};
+typedef PreParams<PcndGainParams> Pcn2Params;
+typedef PreParams<PcfndGainParams> Pcfn2Params;
+
 // chain_f32pcb_kernel (msdr_chain_f32pcb.hiph): a whole block-cadence call of the fp32 chain with per-channel settings in one launch
 struct PcbParams {
     const int16_t *x;          // [channels][n] IF samples

@@ -370,6 +370,21 @@ public:
     // samples are the tick's outputs as [channels()][AUDIO_BLOCK_SAMPLES / D], densely, and the rest of the block is not written.  No node of
     // this runtime knows D; connect only consumers of the caller's that do (readIq, readLevels, readSpectrum follow D by themselves)
     int setDecimation(uint32_t D) { return chain ? msdr_chain_set_decimation(chain, D) : MSDR_STATUS_ARGUMENT_ERROR; }
+    // two-stage decimation (msdr_chain_set_prefilter[_f32]; after setNco, before the first tick or directly after init_FIR()): ONE real row of n
+    // taps in CMSIS order decimates every receiver's mixed stream by D1 in front of its channel pair, which then runs at fs / D1 and decimates
+    // by setDecimation's factor.  The block behind this node holds AUDIO_BLOCK_SAMPLES / (D1 * D) samples per receiver, as setDecimation's
+    // note says of D; readLevels, readIq and readSpectrum follow the product by themselves.  D1 == 1 or n == 0: off
+    int setPrefilter(uint32_t D1, const int16_t *taps, uint32_t n) { return chain ? msdr_chain_set_prefilter(chain, D1, n, taps) : MSDR_STATUS_ARGUMENT_ERROR; }
+    int setPrefilter(uint32_t D1, const float *taps, uint32_t n) { return chain ? msdr_chain_set_prefilter_f32(chain, D1, n, taps) : MSDR_STATUS_ARGUMENT_ERROR; }
+    // input samples per output of the bank: setPrefilter's factor times setDecimation's
+    int rateDivisor(uint32_t *div)
+    {
+        uint32_t D = 1, D1 = 1;
+        if (int rc = msdr_chain_get_decimation(chain, &D)) return rc;
+        if (int rc = msdr_chain_get_prefilter(chain, &D1, nullptr)) return rc;
+        *div = D * D1;
+        return 0;
+    }
     // one queue_adc feeds the bank (msdr_chain_set_input_rows): receiver c hears row rows[c] of the incoming block.  The block stays
     // [AudioGPU.channels()][AUDIO_BLOCK_SAMPLES]; with a map in force the node reads only its first n_inputs rows (so n_inputs <= channels()).
     // n_inputs == 0: every receiver hears its own row again
@@ -401,8 +416,8 @@ public:
         if (!chain || !d_meter || !dbfs) return MSDR_STATUS_ARGUMENT_ERROR;
         const uint32_t ch = AudioGPU.channels();
         std::vector<uint64_t> raw(ch);
-        uint32_t D = 1;          // (setDecimation: the tick's sums run over AUDIO_BLOCK_SAMPLES / D outputs)
-        if (int rc = msdr_chain_get_decimation(chain, &D)) return rc;
+        uint32_t D = 1;          // (setDecimation, setPrefilter: the tick's sums run over AUDIO_BLOCK_SAMPLES / D outputs)
+        if (int rc = rateDivisor(&D)) return rc;
         if (int rc = msdr_memcpy_d2h(AudioGPU.context(), raw.data(), d_meter, (size_t)ch * 8)) return rc;
         for (uint32_t c = 0; c < ch; c++) {
             double s;
@@ -438,7 +453,7 @@ public:
     {
         if (!chain || !d_iq || !pairs) return MSDR_STATUS_ARGUMENT_ERROR;
         uint32_t D = 1;
-        if (int rc = msdr_chain_get_decimation(chain, &D)) return rc;
+        if (int rc = rateDivisor(&D)) return rc;
         if (int rc = msdr_memcpy_d2h(AudioGPU.context(), pairs, d_iq, iqBytes())) return rc;
         if (n_out) *n_out = AUDIO_BLOCK_SAMPLES / D;
         return 0;

@@ -40,6 +40,7 @@ FLAVOUR_COMPLEX_IN = 0x800000
 FLAVOUR_GAIN = 0x1000000
 FLAVOUR_BANK_POST = 0x2000000
 FLAVOUR_SPECTRUM = 0x4000000
+FLAVOUR_PREFILTER = 0x8000000
 SPECTRUM_BINS = 64
 AGC_STATE_WORDS = 32
 MAX_DECIMATION_Q15, MAX_DECIMATION_F32 = 60, 59
@@ -120,6 +121,9 @@ def load_library(path=None):
                        ("msdr_chain_get_nco", [_p, C.c_uint32, _p, _p]),
                        ("msdr_chain_set_decimation", [_p, C.c_uint32]),
                        ("msdr_chain_get_decimation", [_p, _p]),
+                       ("msdr_chain_set_prefilter", [_p, C.c_uint32, C.c_uint32, _p]),
+                       ("msdr_chain_set_prefilter_f32", [_p, C.c_uint32, C.c_uint32, _p]),
+                       ("msdr_chain_get_prefilter", [_p, _p, _p]),
                        ("msdr_chain_get_geometry", [_p, _p]),
                        ("msdr_chain_set_meter", [_p, _p]),
                        ("msdr_chain_get_meter", [_p, _p]),
@@ -991,6 +995,22 @@ class Chain(_Instance):
         d = C.c_uint32(0)
         _ck(self.ctx.lib.msdr_chain_get_decimation(self.h, C.byref(d)))
         return d.value
+
+    def set_prefilter(self, D1, taps):
+        """two-stage decimation: ONE real row `taps` in CMSIS order (int16 on Q15 chains, even count; float32 on F32), the same for the I and
+        the Q stream of every receiver, decimates the mixed stream by D1 (2, 4, 8, 16 or 32) in front of the channel pair, which runs at
+        fs / D1 and decimates by set_decimation's factor; d_audio is [channels, n // (D1 * D)].  Over a clear history only (before the first
+        process(), or directly after reset() / init_fir()); D1 = 1 or no taps: off (msdr_chain_set_prefilter / _f32)."""
+        f32 = self.arith == ARITH_F32
+        t = np.ascontiguousarray(np.zeros(0) if taps is None else taps, np.float32 if f32 else np.int16).ravel()
+        fn = self.ctx.lib.msdr_chain_set_prefilter_f32 if f32 else self.ctx.lib.msdr_chain_set_prefilter
+        _ck(fn(self.h, C.c_uint32(D1), C.c_uint32(t.size), _hp(t) if t.size else None))
+
+    def prefilter(self):
+        """(D1, num_taps) of the prefilter in force, (1, 0) while off (msdr_chain_get_prefilter)"""
+        d, n = C.c_uint32(0), C.c_uint32(0)
+        _ck(self.ctx.lib.msdr_chain_get_prefilter(self.h, C.byref(d), C.byref(n)))
+        return d.value, n.value
 
     def set_meter(self, d_meter):
         """The S-meter: from the next process() on every call overwrites d_meter[channels] -- a device buffer of 8-byte entries (DeviceArray /
