@@ -49,13 +49,15 @@ def ran(info, e):
     assert info["lds_bytes"] == e["lds"], (info, e)
 
 
-def run_entry(ctx, chain, e, adtype, pdtype=None, mdtype=None, flavour=None, x=None, calls=None, ran=ran, feed=None, read=(0, 2)):
+def run_entry(ctx, chain, e, adtype, pdtype=None, mdtype=None, flavour=None, x=None, calls=None, ran=ran, feed=None, read=(0, 2), after=None, no_audio=False):
     """the entry's three calls -> (audio [ch, outputs], pairs [ch, outputs, 2] or None, meters [3, ch] or None); every buffer lies between guard
     stretches of the sentinel, and everything outside the written rows must still hold it.  flavour(info): a check of the family's own.
     The census of the sliding-window kernels (tests/pc_census_cases.py: no "D" in an entry, audio of n samples per row) hands in its own stream
     x, its calls' lengths, its reading of info() (ran; None: an instance without an info call; read: behind which calls) and, for an input map,
     feed(the call's columns of x) -> what is uploaded.  The census of the complex-input twins (tests/cx_census_cases.py) hands in a stream of
-    pairs, x [rows, n, 2]: a call's columns are then n pairs per row, and nothing else changes."""
+    pairs, x [rows, n, 2]: a call's columns are then n pairs per row, and nothing else changes.  The census of the two-stage kernels
+    (tests/pre_census_cases.py) reads the receivers' gain records behind every call -- after(k) runs there -- and makes I/Q-only calls
+    (no_audio: a null audio pointer; the guarded audio buffer is still made and must stay the sentinel from end to end)."""
     ch, D = e["channels"], e.get("D", 1)
     x = cases.data(e)["x"] if x is None else x
     audio, pairs, meters, lo = [], [], [], 0
@@ -73,9 +75,10 @@ def run_entry(ctx, chain, e, adtype, pdtype=None, mdtype=None, flavour=None, x=N
             m_buf = ctx.to_device(fresh(METER_GUARD + ch + METER_GUARD, mdtype))
             chain.set_meter(m_buf.offset(8 * METER_GUARD))
         part = np.ascontiguousarray(x[:, lo:lo + n])
-        chain.process(ctx.to_device(part if feed is None else feed(part)), a_buf.offset(guard * a_flat.itemsize), n)
+        chain.process(ctx.to_device(part if feed is None else feed(part)), None if no_audio else a_buf.offset(guard * a_flat.itemsize), n)
         back = a_buf.download()
         assert untouched(back[:guard]) and untouched(back[guard + ch * nout:]), (k, "audio: written outside the batch")
+        assert not no_audio or untouched(back), (k, "audio: written by an I/Q-only call")
         audio.append(back[guard:guard + ch * nout].reshape(ch, nout))
         if pdtype is not None:
             back = q_buf.download().reshape(-1, 2)
@@ -92,6 +95,8 @@ def run_entry(ctx, chain, e, adtype, pdtype=None, mdtype=None, flavour=None, x=N
             ran(info, e)
             if flavour is not None:
                 flavour(info)
+        if after is not None:
+            after(k)
         lo += n
     assert lo == x.shape[1]
     if pdtype is not None:
