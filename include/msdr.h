@@ -1096,6 +1096,17 @@ int msdr_chain_get_info(msdr_chain *chain, msdr_chain_info *info);
  * created with MSDR_MFW_GEOM=0 in the environment); 1 = envelope tables behind the exact Fs/4 mixer, 256 taps, two-section cascade with a
  * row-local section; 2 = the same with 512 taps.  msdr_chain_info is as it was: `kernel`, `env_scan` and `flavour` do not tell the two apart. */
 int msdr_chain_get_geometry(msdr_chain *chain, uint32_t *id);
+/* Behind the exact Fs/4 mixer at an even rotation, with one low-pass for I and Q, the envelope table's Q block is its I block moved one
+ * column: the wave-stream kernels then run Q on the I accumulator's tap fragments over the odd samples (one fragment read feeds both
+ * accumulators) and realign the result, which arrives one sample late, behind the FIR burst.  The table builder confirms the relation on the
+ * numbers of every table it builds (create and every live update); any other table -- odd rotation, hI != hQ, ... -- keeps its own fragments.
+ * *on = 1 where the last call's envelope launch on the wave-stream kernels met only such tables and so ran that way, else 0 (also before
+ * the first call, on every other kernel path, and on a chain created with MSDR_MFW_IQ=0 in the environment).  Same products, some sums in
+ * another order: the results differ from the unshared path's in the last bits.  The kernels with a constant run geometry
+ * (msdr_chain_get_geometry 1 / 2) exist in this form only: a 256- or 512-tap Fs/4 envelope chain with hI != hQ, or one created under
+ * MSDR_MFW_IQ=0, runs the header-reading kernel instead (geometry 0), about 2 % slower per call than the constant-geometry kernel it had
+ * before this form existed (profiles/mfw_geom/README.md). */
+int msdr_chain_get_iq_shared(msdr_chain *chain, uint32_t *on);
 /* Which kernel ran the serial recurrences (introspection for tests: tests/q15_ladder_cases.py is the table of every branch below, and
  * tests/test_gpu_q15_ladders.py holds each of them to the oracle bit for bit).  Each getter returns a static string -- the kernel's name
  * with its template arguments, set in the branch that made the launch and handed to the launch's error check as well -- "" before the

@@ -28,6 +28,7 @@
 #include "msdr_cascade_state.h"
 #include "msdr_kstack.h"
 #include "msdr_sparse24.h"
+#include "msdr_iqshare.h"
 
 #include <algorithm>
 #include <atomic>
@@ -2487,6 +2488,10 @@ struct msdr_chain {
     // geometry its header has, 0 = none (empty: MSDR_MFW_GEOM=0 at create time, or no matrix-core tables); the table sets each of the two
     // launches' units use (chain_mfw_units); what the last call's launches ran with (msdr_chain_get_geometry)
     std::vector<uint8_t> mf_tab_geom;
+    // the same per table: its header's qlag (Q on accumulator 0's fragments, msdr_iqshare.h); whether the last call's envelope launches ran
+    // that way (msdr_chain_get_iq_shared)
+    std::vector<uint8_t> mf_tab_qlag;
+    uint32_t last_iq = 0;
     std::vector<int> part_fsets[2];
     uint32_t last_geom = 0;
     char *d_mf_tab;
@@ -3092,6 +3097,10 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
         // create time keeps every run dense (A/B runs, tests)
         bool sparse_on = !fr;
         if (const char *e = getenv("MSDR_MFW_SPARSE")) sparse_on = sparse_on && atoi(e) != 0;
+        // Q on accumulator 0's tap fragments where a table allows it (MfmaTableHeader::qlag); MSDR_MFW_IQ=0 at create time keeps every
+        // envelope table on its own fragments (A/B runs, tests)
+        bool iq_on = !fr;
+        if (const char *e = getenv("MSDR_MFW_IQ")) iq_on = iq_on && atoi(e) != 0;
         const bool ok = true;
         std::vector<double> M[2];
         M[0].resize((size_t)KIv * 32); M[1].resize((size_t)KIv * 32);
@@ -3436,6 +3445,14 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
                         xsteps = std::max(xsteps, ns + T.h.xsteps);        // (for now: the steps this table takes in all)
                     }
                     merged_min[v == 2] = std::min(merged_min[v == 2], nmerged);
+                    // envelope table, de-interleaved: may Q run on accumulator 0's fragments (msdr_iqshare.h)?  Decided on the matrices, the
+                    // runs and the merged steps as they stand now (clearing every merged step below keeps the two accumulators alike)
+                    if (iq_on && v == 2 && !fr) {
+                        int rj[2][2], rc_[2][2], rs[2][2];
+                        for (int o = 0; o < 2; o++)
+                            for (int src = 0; src < 2; src++) { rj[o][src] = T.h.run[o][src].j0; rc_[o][src] = T.h.run[o][src].cnt; rs[o][src] = T.h.sp[o][src]; }
+                        T.h.qlag = iqshare_check(M[0].data(), M[1].data(), KI, scale, rj, rc_, rs) ? 1 : 0;
+                    }
                 }
         }
         // the LDS region holds the largest table, merged steps included: xsteps = what that adds to the dense steps.  Where it would cost a
@@ -3485,6 +3502,8 @@ static int chain_create_impl(msdr_ctx *ctx, const msdr_chain_config *cfg, msdr_c
                 if (const char *e = getenv("MSDR_MFW_GEOM")) geom_on = atoi(e) != 0;
                 c->mf_tab_geom.clear();
                 if (geom_on && !fr) for (const Tab &T : tabs) c->mf_tab_geom.push_back((uint8_t)mw_geom_of(T.h, H));
+                c->mf_tab_qlag.clear();
+                for (const Tab &T : tabs) c->mf_tab_qlag.push_back((uint8_t)T.h.qlag);
                 // wave-stream variant: waves per workgroup that put the most waves on a CU (<= 16: the kernel's <= 128 VGPRs allow
                 // 4 per SIMD) under the 160 KB of LDS -- counted in whole waves per SIMD.  A SIMD's tile rate is the same from two waves
                 // on (profiles/r03/c3_trims.txt), so a workgroup is as slow as its fullest SIMD: 13 waves (4 + 3 + 3 + 3) ran 4 % behind
@@ -4180,6 +4199,7 @@ struct ChainLaunch {
     uint32_t flavour;            // MSDR_FLAVOUR_* of the launches, set where each one is made
     uint32_t env_scan;           // how the folded envelope flavour of chain_mfw_kernel scanned its row states
     int merged_steps;            // chain_mfw_kernel: k-steps per tile that went into merged steps (the least over the launches), -1 = no such launch
+    uint32_t iq;                 // chain_mfw_kernel: 1 = the envelope launch ran Q on accumulator 0's tap fragments (MfmaTableHeader::qlag on every table it met)
     uint32_t geom;               // chain_mfw_kernel: id of the constant run geometry a launch ran with (MwGeom), 0 = every launch read the table headers
     const char *node_kname;      // the kernel that runs the biquad nodes of this call ("": no nodes, fp32 chains)
 };
@@ -4294,7 +4314,7 @@ static int chain_prepare(msdr_chain *c, ChainDecision &d, const ChainTiles &t, c
     r.kname = ""; r.node_kname = "";
     r.grid = (unsigned)(c->channels * r.nseg); r.block = kThreads; r.tile = t.tile;
     r.lds_bytes = t.mfw ? mw_lds_bytes(c->mf_halo, c->mf_bsteps + c->mf_xsteps, c->mfw_nw, c->mf_fr) : d.path == kPathFold ? fold_lds_bytes(p.ntaps_pad) : chain_lds_bytes(p.ntaps_pad);
-    r.flavour = 0; r.env_scan = 0; r.merged_steps = -1; r.geom = 0;
+    r.flavour = 0; r.env_scan = 0; r.merged_steps = -1; r.geom = 0; r.iq = 0;
 
     switch (d.path) {
     case kPathMfb:
@@ -4510,6 +4530,17 @@ static int chain_launch_mfw(msdr_chain *c, const ChainDecision &, const ChainTil
             }
         }
         r.geom = std::max(r.geom, (uint32_t)geom);
+        // Q on accumulator 0's fragments: a workgroup goes by its own table's header (the constant-geometry kernels always do: mw_geom_is
+        // asks for the flag); the call reports it where every table this launch's units use carries the flag
+        if (part == 1 && !c->mf_fr) {
+            const int P = std::max(q.fold_period, 1);
+            bool all = !c->part_fsets[part].empty();
+            for (size_t k = 0; k < c->part_fsets[part].size() && all; k++) {
+                const size_t ti = (size_t)c->part_fsets[part][k] * P + q.fold_rot;
+                all = ti < c->mf_tab_qlag.size() && c->mf_tab_qlag[ti] != 0;
+            }
+            r.iq = all ? 1u : 0u;
+        }
         (void)launch_chain_mfw(c->ctx->stream, (int)c->nstages, part == 1, fold, c->mf_fr, rowlocal, g, r.block, r.lds_bytes, q, geom);
         const int part_merged = mw_merges_steps((int)c->nstages, part == 1, fold, c->mf_fr, rowlocal) ? c->mf_merged[part] : 0;
         r.merged_steps = r.merged_steps < 0 ? part_merged : std::min(r.merged_steps, part_merged);
@@ -4893,7 +4924,7 @@ extern "C" int msdr_chain_process(msdr_chain *c, const int16_t *d_if, void *d_au
     c->info.time_segments = (uint32_t)r.nseg; c->info.warmup = (uint32_t)p.warm; c->info.tile = (uint32_t)r.tile;
     c->info.taps_padded = path_per_channel(d.path) ? (uint32_t)c->pc_np : c->ntaps_pad;
     c->info.mfma_ksteps = d.mf ? (uint32_t)(c->mf_bsteps - std::max(r.merged_steps, 0)) : path_qm(d.path) ? (uint32_t)c->qm_bsteps : 0u;
-    c->last_geom = r.geom;
+    c->last_geom = r.geom; c->last_iq = r.iq;
     return 0;
 }
 
@@ -5290,7 +5321,7 @@ static int chain_rebuild(msdr_chain *c, const ChainCfgStore &edited, void **stea
     n->gen = c->gen; n->dh_cache = c->dh_cache; n->dh_gen = c->dh_gen;
     n->floor_d = used_d; n->floor_sig = used_sig; n->floor_gen = c->gen;
     n->timing = c->timing; n->events.swap(c->events); n->timed_ms = c->timed_ms; n->timed_launches = c->timed_launches;
-    n->info = c->info; n->last_geom = c->last_geom;
+    n->info = c->info; n->last_geom = c->last_geom; n->last_iq = c->last_iq;
     n->osc_pending.swap(c->osc_pending); n->force_generic = c->force_generic;
     // per-channel taps survive every rebuild; the channels still on a shared tap set follow that set's (possibly new) coefficients
     n->rebuild_gen = c->rebuild_gen + 1;
@@ -6322,6 +6353,12 @@ extern "C" int msdr_chain_get_geometry(msdr_chain *c, uint32_t *id)
 {
     if (!c || !id) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
     *id = c->last_geom;
+    return 0;
+}
+extern "C" int msdr_chain_get_iq_shared(msdr_chain *c, uint32_t *on)
+{
+    if (!c || !on) return fail(MSDR_STATUS_ARGUMENT_ERROR, "null argument");
+    *on = c->last_iq;
     return 0;
 }
 extern "C" int msdr_chain_get_info(msdr_chain *c, msdr_chain_info *info)

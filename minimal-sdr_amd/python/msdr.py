@@ -125,6 +125,7 @@ def load_library(path=None):
                        ("msdr_chain_set_prefilter_f32", [_p, C.c_uint32, C.c_uint32, _p]),
                        ("msdr_chain_get_prefilter", [_p, _p, _p]),
                        ("msdr_chain_get_geometry", [_p, _p]),
+                       ("msdr_chain_get_iq_shared", [_p, _p]),
                        ("msdr_chain_set_meter", [_p, _p]),
                        ("msdr_chain_get_meter", [_p, _p]),
                        ("msdr_meter_dbfs", [C.c_double, C.c_uint64, C.c_double]),
@@ -1217,6 +1218,12 @@ class Chain(_Instance):
         """msdr_chain_get_geometry: the constant run geometry the last process() ran with on the wave-stream kernels, 0 = read from the table headers"""
         g = C.c_uint32(0)
         _ck(self.ctx.lib.msdr_chain_get_geometry(self.h, C.byref(g)))
+        return g.value
+
+    def iq_shared(self):
+        """msdr_chain_get_iq_shared: 1 where the last process() ran its envelope launch with Q on accumulator 0's tap fragments"""
+        g = C.c_uint32(0)
+        _ck(self.ctx.lib.msdr_chain_get_iq_shared(self.h, C.byref(g)))
         return g.value
 
     def enable_timing(self, on=True):
