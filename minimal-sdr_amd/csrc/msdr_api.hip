@@ -5097,7 +5097,9 @@ extern "C" int msdr_chain_reset(msdr_chain *c)
     }
     if (c->d_spec_tail) {          // msdr_chain_set_spectrum: the window and showSpectrum's counter start over (with the other clears, in front of the host's own state)
         HIP_TRY(fill_dev(c->ctx, c->d_spec_tail, 0, (size_t)c->channels * kCfftBins * (c->arith == MSDR_ARITH_F32 ? 8 : 4)));
+#if !(defined(MSDR_MUTATE) && MSDR_MUTATE == 7)    /* `make mutants`, never the product: mutant 7 leaves showSpectrum's counter as it was */
         c->spec_counter = 0;
+#endif
     }
     if (!c->osc_pending.empty() || c->force_generic) {          // no sample of an earlier oscillator table is left in a cleared history
         HIP_TRY(hipStreamSynchronize(c->ctx->stream));
@@ -5818,7 +5820,11 @@ extern "C" int msdr_chain_set_nco_channels(msdr_chain *c, uint32_t first_channel
     }
     for (uint32_t k = 0; k < count; k++) {
         const uint32_t ch = first_channel + k;
+#if defined(MSDR_MUTATE) && MSDR_MUTATE == 6       /* `make mutants`, never the product: a phase-continuous retune rebases the phase one sample late, at nco_T + 1 */
+        c->h_nco_base[ch] = phase ? nco_base_for(phase[k], step[k], c->nco_T) : nco_rebase(c->h_nco_base[ch], c->nco_T + 1, c->h_nco_step[ch], step[k]);
+#else
         c->h_nco_base[ch] = phase ? nco_base_for(phase[k], step[k], c->nco_T) : nco_rebase(c->h_nco_base[ch], c->nco_T, c->h_nco_step[ch], step[k]);
+#endif
         c->h_nco_step[ch] = step[k];
     }
     if (int rc = chain_nco_upload(c, first_channel, count)) { hipFree(snap); return rc; }
